@@ -7,14 +7,21 @@ BN, fp32) over one batch of 16 synthetic CelebA-shaped samples (32x32 -> 256x256
 independent images, no data-path collective - SURVEY.md 8e); `value` = all images processed / max-over-ranks time.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--batch 16] [--dtype fp32|bf16|f16] [--graph] [--no-cpu-baseline]
+                    [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 `--gpus N` (N > 1) without a torchrun environment starts that command itself, as a child process, before anything
 touches the GPU, and relays its JSON line.  `--dtype bf16|f16` runs BASELINE configs[4]'s reduced-precision path
 (fp32 stays the parity configuration and the default).
 
-Prints ONE JSON line (rank 0) carrying `roofline` (dominant 3x3-conv kernel by time, per-launch HIP-event
-timing inside the timed region) and `cpu_baseline` (the CPU oracle timed on this host's cores, rank 0, N=1 only).
+Inference (the default mode) sets up, runs W warm-up steps and times ONE fenced region of exactly K steps: `value` and
+`ms_per_step` come from that region alone.  `--dump-outputs DIR` then writes what the last timed step returned
+(`DIR/<name>.npy`, float32).  Everything else moves behind `--full`: the median over >= `--min-time` s of further K-step
+regions with event-sampled steps (`value_one_lane`), the throughput form, `roofline` / `kernels` / `attention`,
+`cpu_baseline` (the CPU oracle timed on this host's cores, rank 0, N=1 only), the `lp` and `train` objects and the
+library's own RCCL communicator check.
+
+Prints ONE JSON line (rank 0).
 """
 import argparse
 import csv
@@ -116,6 +123,33 @@ def replay_on(step, pool, k, lanes=1):
     bs = [pool[(k * lanes + j) % len(pool)] for j in range(lanes)]
     return step.replay([b["cap"] for b in bs], [b["lens_dev"] for b in bs], [b["LR"] for b in bs],
                        [b["LRb"] for b in bs], num_words=[b["T"] for b in bs])
+
+
+DUMP_LIMIT_BYTES = 64 * 10 ** 6   # --dump-outputs: all files together
+
+
+def host_outputs(out, name=""):
+    """What one step returned (dict / list of tensors, nested) as {name: float32 ndarray} on the host: `fine_2` = out["fine"][2]."""
+    if torch.is_tensor(out):
+        return {name: out.detach().to("cpu", torch.float32).numpy()}
+    items = out.items() if isinstance(out, dict) else enumerate(out) if isinstance(out, (list, tuple)) else ()
+    res = {}
+    for k, v in items:
+        res.update(host_outputs(v, "%s_%s" % (name, k) if name else str(k)))
+    return res
+
+
+def dump_outputs(arrs, d, limit=DUMP_LIMIT_BYTES):
+    """{name: float32 array} -> d/<name>.npy.  Above `limit` bytes in all, every array keeps the same share of its elements,
+    flattened, at indices drawn from a fixed seed (the same ones on every run with the same arguments)."""
+    os.makedirs(d, exist_ok=True)
+    total = sum(a.nbytes for a in arrs.values())
+    keep = 1.0 if total <= limit else 0.99 * limit / total
+    for name, a in sorted(arrs.items()):
+        if keep < 1.0:
+            idx = np.random.default_rng(0).choice(a.size, size=max(1, int(a.size * keep)), replace=False)
+            a = a.reshape(-1)[np.sort(idx)]
+        np.save(os.path.join(d, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
 
 
 def load_weights():
@@ -975,7 +1009,7 @@ def main():
     ap.add_argument("--lanes", type=int, default=3,
                     help="inference: consecutive steps alternate between this many stream lanes (1 = one step at a time)")
     ap.add_argument("--extras", default="lp,train",
-                    help="default run (fp32 inference, eager): also time, in this process after the headline region, the "
+                    help="--full (fp32 inference): also time, in this process after the headline region, the "
                          "reduced-precision hipGraph configurations (`lp` object: BASELINE configs[4]) and the train steps "
                          "(`train` object: configs[2]); '' or 'none' = headline only")
     ap.add_argument("--branch-num", type=int, default=4,
@@ -983,13 +1017,23 @@ def main():
                          "else = the x16 generators of models16.py (trainer_objective.py:74-87: 32 -> 512, weight-tied stages, "
                          "a fourth attention at 256^2 = 65 536 pixels), seeded random-init weights (no x16 checkpoint ships)")
     ap.add_argument("--min-time", type=float, default=0.5,
-                    help="every timed figure is the median over enough fenced K-step regions for this many seconds of timed work")
-    ap.add_argument("--repeats", type=int, default=0, help="number of fenced K-step regions per figure (0 = from --min-time)")
+                    help="inference --full and --mode train: the median figures are taken over enough fenced K-step regions for "
+                         "this many seconds of timed work")
+    ap.add_argument("--repeats", type=int, default=0,
+                    help="inference --full and --mode train: number of fenced K-step regions per median figure (0 = from --min-time)")
     ap.add_argument("--profile-every", type=int, default=20,
-                    help="bracket every launch of every Nth timed step with HIP events for the roofline (0 = never); "
-                         "two events per launch cost ~9 %% of a step, so the timed region samples instead of paying "
-                         "it on every step")
+                    help="--full: bracket every launch of every Nth step of the last median region with HIP events for the "
+                         "roofline (0 = never); two events per launch cost ~9 %% of a step, so the region samples instead of "
+                         "paying it on every step")
+    ap.add_argument("--full", action="store_true",
+                    help="inference: after the headline region, also measure everything the headline does not need (median "
+                         "regions, throughput form, roofline, attention, CPU baseline, the lp / train objects, RCCL check)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="inference: write the tensors the last timed step returned to DIR/<name>.npy (float32; a fixed, "
+                         "seeded sample of each when all of them exceed %d MB)" % (DUMP_LIMIT_BYTES // 10 ** 6))
     args = ap.parse_args()
+    if args.dump_outputs and args.mode != "infer":
+        raise SystemExit("--dump-outputs applies to the inference bench")
     if args.mode == "infer" and not (args.graph or args.eager or args.serial):
         for gl in (4, 3, 2):
             if args.steps % gl == 0:
@@ -1057,7 +1101,7 @@ def main():
             raise SystemExit("--steps must be a multiple of --graph-lanes (a replay runs that many steps)")
         pipe.capture(cap, lens, LR, LRb)                   # the one-lane step
     multi = None
-    if glanes > 1:
+    if glanes > 1 and args.full:
         from tgsr_amd.trainer import GraphedStep
         multi = GraphedStep(pipe, cap, lens, LR, LRb, lanes=glanes)   # `glanes` independent batches in one graph
 
@@ -1081,66 +1125,83 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
-    # Consecutive steps are independent batches: they alternate between `--lanes` stream lanes (each lane = the two
-    # streams of SRPipeline), so the small kernels and tails of one step fill the dispatch gaps of the previous one
-    # (~60 dependent launches leave the GPU idle ~10 % of a single-lane step).  Every step still runs completely; the
-    # sampled steps run alone (lanes drained before and after) so that a launch is timed in isolation.
-    nlanes = 1 if (args.serial or args.graph) else max(1, args.lanes)
-    lanes = [torch.cuda.Stream(device=dev) for _ in range(nlanes)] if nlanes > 1 else []
-    if lanes:
-        torch.cuda.synchronize()            # weight packs / caches of the warm-up steps are complete before fanning out
-    for ln in lanes:                        # untimed: every lane allocates its activation buffers once
-        with torch.cuda.stream(ln):
-            step()
-    if args.graph and args.profile_every > 0:
-        step(eager=True)                    # untimed: the event-sampled steps run eagerly and own a buffer set too
-    prof, nprof = [], [0]
     K = args.steps
-
-    # ---- the strict figure (BASELINE's metric: batch B per GPU, ONE step in flight): K steps issued one at a time, replayed
-    # from the one-lane hipGraph (or eager / serial as selected).  The event-sampled steps (every launch bracketed by HIP
-    # events on its stream, eager and single-stream so that a launch is timed alone) sit inside the LAST timed region only;
-    # the reported time is the median over the regions.
-    def region_one(r, last):
-        for k in range(K):
-            sample = last and args.profile_every > 0 and (K - 1 - k) % args.profile_every == 0
-            if sample:
-                ops.profile, pipe.overlap = prof, False
-                nprof[0] += 1
-                step(eager=True)
-                ops.profile, pipe.overlap = None, not args.serial
-            else:
-                step()
+    # ---- the headline (BASELINE's metric: batch B per GPU, ONE step in flight): ONE fenced region of exactly K steps issued one
+    # at a time, replayed from the one-lane hipGraph (or eager / serial as selected), max over ranks; nothing else runs inside it.
+    # --dump-outputs: what the last of them returned (a replay returns views of the graph's static outputs: copied before
+    # anything else runs)
     pipe.overlap = not args.serial
-    fence()
-    t0 = time.perf_counter()
-    region_one(0, False)
-    fence()
-    reps = _bcast_int(reps_for(time.perf_counter() - t0, args), dist, dev)
-    ts_local = []
-    dt1, ts1 = time_regions(lambda r: region_one(r, r == reps - 1), fence, reps, dist, dev, local=ts_local)
-    ranks = ranks_object(rank, world, dist, dev, ts_local)
+    last = [None]
 
-    # ---- the throughput form: several independent batches in flight (parallel branches of one hipGraph, or eager stream lanes)
-    dtm = None
-    if multi is not None:
-        def region_multi(r):
-            for k in range(K // glanes):    # one replay = `glanes` steps on `glanes` different batches, other ones every replay
-                replay_on(multi, pool, r * (K // glanes) + k, glanes)
-        dtm, _tsm = time_regions(region_multi, fence, reps, dist, dev)
-    elif lanes:
-        def region_lanes(r):
+    def region_head(r):
+        for k in range(K):
+            last[0] = step()
+    ts_local = []
+    dt, ts0 = time_regions(region_head, fence, 1, dist, dev, local=ts_local)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(host_outputs(last[0]), args.dump_outputs)
+    last[0] = None
+
+    prof, nprof = [], 0
+    dt1, ts1, reps, dtm = dt, ts0, 1, None
+    nlanes = 1 if (args.serial or args.graph) else max(1, args.lanes)
+    lanes = []
+    if args.full:
+        # Consecutive steps are independent batches: they alternate between `--lanes` stream lanes (each lane = the two
+        # streams of SRPipeline), so the small kernels and tails of one step fill the dispatch gaps of the previous one
+        # (~60 dependent launches leave the GPU idle ~10 % of a single-lane step).  Every step still runs completely; the
+        # sampled steps run alone (lanes drained before and after) so that a launch is timed in isolation.
+        lanes = [torch.cuda.Stream(device=dev) for _ in range(nlanes)] if nlanes > 1 else []
+        if lanes:
+            torch.cuda.synchronize()            # weight packs / caches of the warm-up steps are complete before fanning out
+        for ln in lanes:                        # untimed: every lane allocates its activation buffers once
+            with torch.cuda.stream(ln):
+                step()
+        if args.graph and args.profile_every > 0:
+            step(eager=True)                    # untimed: the event-sampled steps run eagerly and own a buffer set too
+        npr = [0]
+
+        # ---- the one-lane figure as a median: K steps issued one at a time as in the headline, over enough fenced regions for
+        # >= --min-time s.  The event-sampled steps (every launch bracketed by HIP events on its stream, eager and single-stream
+        # so that a launch is timed alone) sit inside the LAST region only.
+        def region_one(r, last):
             for k in range(K):
-                with torch.cuda.stream(lanes[k % nlanes]):
+                sample = last and args.profile_every > 0 and (K - 1 - k) % args.profile_every == 0
+                if sample:
+                    ops.profile, pipe.overlap = prof, False
+                    npr[0] += 1
+                    step(eager=True)
+                    ops.profile, pipe.overlap = None, not args.serial
+                else:
                     step()
-        dtm, _tsm = time_regions(region_lanes, fence, reps, dist, dev)
-    ops.profile = None
-    nprof = nprof[0]
-    dt = dt1
+        pipe.overlap = not args.serial
+        fence()
+        t0 = time.perf_counter()
+        region_one(0, False)
+        fence()
+        reps = _bcast_int(reps_for(time.perf_counter() - t0, args), dist, dev)
+        ts_local = []
+        dt1, ts1 = time_regions(lambda r: region_one(r, r == reps - 1), fence, reps, dist, dev, local=ts_local)
+
+        # ---- the throughput form: several independent batches in flight (parallel branches of one hipGraph, or eager stream lanes)
+        if multi is not None:
+            def region_multi(r):
+                for k in range(K // glanes):    # one replay = `glanes` steps on `glanes` different batches, other ones every replay
+                    replay_on(multi, pool, r * (K // glanes) + k, glanes)
+            dtm, _tsm = time_regions(region_multi, fence, reps, dist, dev)
+        elif lanes:
+            def region_lanes(r):
+                for k in range(K):
+                    with torch.cuda.stream(lanes[k % nlanes]):
+                        step()
+            dtm, _tsm = time_regions(region_lanes, fence, reps, dist, dev)
+        ops.profile = None
+        nprof = npr[0]
+    ranks = ranks_object(rank, world, dist, dev, ts_local)
     form_multi = multi is not None
 
     extras = {}
-    want = [e for e in args.extras.replace("none", "").split(",") if e]
+    want = [e for e in args.extras.replace("none", "").split(",") if e] if args.full else []
     if want and args.dtype == "fp32" and not args.serial:
         # driver-visible measurements of the other BASELINE configurations, same process, after the headline region
         pipe.overlap = True
@@ -1214,9 +1275,11 @@ def main():
                           "storage": "fp32 NCHW" if args.dtype == "fp32" else
                           "%s channels-last (zero-bordered), fp32 accumulate; inputs / outputs fp32" % args.dtype,
                           "sampled_steps": nprof,
-                          "timing": "median of %d fenced regions of exactly K = %d steps (barrier + synchronize on both sides of "
-                                    "each, max over ranks per region; >= %.1f s of timed work in all); regions, s: %s"
-                                    % (reps, K, args.min_time, [round(t, 5) for t in ts1]),
+                          "timing": "`value`: ONE fenced region of exactly K = %d steps (barrier + synchronize on both sides, max "
+                                    "over ranks), %.5f s%s"
+                                    % (K, ts0[0], "" if not args.full else
+                                       "; `value_one_lane` (--full): median of %d more such regions (>= %.1f s of timed work in "
+                                       "all); regions, s: %s" % (reps, args.min_time, [round(t, 5) for t in ts1])),
                           "repeats": reps,
                           "batches": "%d different resident synthetic batches (captions, caption lengths, images) cycled "
                                      "through the steps: every timed step - every lane of a hipGraph replay - runs on another "
@@ -1225,10 +1288,11 @@ def main():
                                      % len(pool),
                           **({"throughput_form": tform} if tform else {}),
                           "note": ("`value` = the strict figure of BASELINE's metric: K steps of batch %d issued ONE AT A TIME "
-                                   "(%s), %d event-sampled eager single-stream step(s) inside the last region.  "
-                                   "`throughput_form` (not the headline): the same K steps with several independent batches in "
-                                   "flight, measured right after with the same fencing"
-                                   % (B, "replays of the one-lane hipGraph" if args.graph else "eager launches", nprof))},
+                                   "(%s)%s"
+                                   % (B, "replays of the one-lane hipGraph" if args.graph else "eager launches", "" if not args.full else
+                                      "; `value_one_lane`: the same with %d event-sampled eager single-stream step(s) inside its "
+                                      "last region.  `throughput_form` (not the headline): the same K steps with several "
+                                      "independent batches in flight, measured right after with the same fencing" % nprof))},
                "roofline": roof, "kernels": kern}
         # the whole step against SURVEY.md 8(d)'s compulsory conv-path bytes (173.9 MB per image at the reference's layer
         # boundaries in fp32, half of that with 2-byte storage) and 21.07 GFLOP per image: the "fraction of the HBM
@@ -1249,11 +1313,11 @@ def main():
             "hbm_frac_one_lane": round(res["value_one_lane"] / world * mb_img * 1e6 / (PEAK_HBM_GBS * 1e9), 4)}
         if att is not None:
             res["attention"] = att
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and not args.no_cpu_baseline and args.full:
             res["cpu_baseline"] = cpu_baseline(weights, B, x16_pipe=pipe if x16 else None)
         res.update(extras)
         res["ranks"] = ranks
-    direct = rccl_direct_evidence(world, dist, dev)
+    direct = rccl_direct_evidence(world, dist, dev) if args.full else None
     if rank == 0:
         if direct is not None:
             res["ranks"]["rccl_direct"] = direct

@@ -284,3 +284,22 @@ def test_split_form_eligibility_is_host_arithmetic():
         assert L.tgsr_conv4x4s2_ws_elems(0, 32, 64, 128, 128, 128) == 128 * 1024 * 3 // 2
     finally:
         L.tgsr_dconv_set_split(was)
+
+
+def test_bench_dump_outputs_names_dtype_and_size_cap(tmp_path):
+    """bench.py --dump-outputs: one float32 .npy per returned tensor, named after its place in the result; above the size cap
+    every array keeps the same seeded sample of its elements, the same on every run."""
+    import bench
+    out = {"fine": [torch.arange(6.0).view(2, 3), torch.ones(2, 2, dtype=torch.float64)], "mask": torch.tensor([True, False]),
+           "att": [None]}
+    arrs = bench.host_outputs(out)
+    assert sorted(arrs) == ["fine_0", "fine_1", "mask"] and all(a.dtype == np.float32 for a in arrs.values())
+    bench.dump_outputs(arrs, str(tmp_path / "all"))
+    assert np.array_equal(np.load(tmp_path / "all" / "fine_0.npy"), np.arange(6.0, dtype=np.float32).reshape(2, 3))
+    assert np.array_equal(np.load(tmp_path / "all" / "mask.npy"), np.array([1.0, 0.0], dtype=np.float32))
+    big = {"a": np.random.default_rng(1).standard_normal(4000).astype(np.float32), "b": np.zeros(1000, np.float32)}
+    for d in ("s1", "s2"):
+        bench.dump_outputs(big, str(tmp_path / d), limit=4000)
+    a1, a2 = np.load(tmp_path / "s1" / "a.npy"), np.load(tmp_path / "s2" / "a.npy")
+    assert np.array_equal(a1, a2) and a1.nbytes + np.load(tmp_path / "s1" / "b.npy").nbytes <= 4000
+    assert np.isin(a1, big["a"]).all() and a1.size == int(4000 * 0.99 * 4000 / 20000)

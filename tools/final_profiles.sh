@@ -10,29 +10,29 @@ OUT=$ROOT/gpurun_out
 mkdir -p $OUT
 cd $ROOT
 if [ "$PART" != "prof" ]; then
-python3 bench.py > $OUT/${TAG}_bench_fp32.json 2> $OUT/${TAG}_bench_fp32.err
-python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline --extras none > $OUT/${TAG}_bench_fp32_driver_flags.json 2> $OUT/${TAG}_bench_fp32_driver_flags.err
-python3 bench.py --eager --no-cpu-baseline --extras none > $OUT/${TAG}_bench_fp32_eager_lanes3.json 2> $OUT/${TAG}_bench_fp32_eager.err
+python3 bench.py --full > $OUT/${TAG}_bench_fp32.json 2> $OUT/${TAG}_bench_fp32.err
+python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --extras none > $OUT/${TAG}_bench_fp32_driver_flags.json 2> $OUT/${TAG}_bench_fp32_driver_flags.err
+python3 bench.py --full --eager --no-cpu-baseline --extras none > $OUT/${TAG}_bench_fp32_eager_lanes3.json 2> $OUT/${TAG}_bench_fp32_eager.err
 echo "fp32 done"
-python3 bench.py --dtype bf16 --graph > $OUT/${TAG}_bench_bf16_graph.json 2> $OUT/${TAG}_bench_bf16_graph.err
+python3 bench.py --full --dtype bf16 --graph > $OUT/${TAG}_bench_bf16_graph.json 2> $OUT/${TAG}_bench_bf16_graph.err
 echo "bf16 graph done"
-python3 bench.py --dtype f16 --graph --no-cpu-baseline > $OUT/${TAG}_bench_f16_graph.json 2> $OUT/${TAG}_bench_f16_graph.err
-python3 bench.py --dtype bf16 --eager --no-cpu-baseline > $OUT/${TAG}_bench_bf16_eager_lanes3.json 2> $OUT/${TAG}_bench_bf16_eager.err
-python3 bench.py --dtype bf16 --graph --batch 8 --no-cpu-baseline > $OUT/${TAG}_bench_bf16_graph_b8.json 2> $OUT/${TAG}_bench_bf16_graph_b8.err
-python3 bench.py --dtype bf16 --graph --batch 64 --steps 10 --no-cpu-baseline > $OUT/${TAG}_bench_bf16_graph_b64.json 2> $OUT/${TAG}_bench_bf16_graph_b64.err
-python3 bench.py --dtype bf16 --graph --graph-lanes 4 --no-cpu-baseline > $OUT/${TAG}_bench_bf16_graph_lanes4.json 2> $OUT/${TAG}_bench_bf16_graph_lanes4.err
-python3 bench.py --dtype bf16 --graph --graph-lanes 8 --batch 8 --steps 48 --no-cpu-baseline > $OUT/${TAG}_bench_bf16_graph_b8_lanes8.json 2> $OUT/${TAG}_bench_bf16_graph_b8_lanes8.err
-python3 bench.py --dtype bf16 --graph --batch 128 --steps 6 --no-cpu-baseline > $OUT/${TAG}_bench_bf16_graph_b128.json 2> $OUT/${TAG}_bench_bf16_graph_b128.err
+python3 bench.py --full --dtype f16 --graph --no-cpu-baseline > $OUT/${TAG}_bench_f16_graph.json 2> $OUT/${TAG}_bench_f16_graph.err
+python3 bench.py --full --dtype bf16 --eager --no-cpu-baseline > $OUT/${TAG}_bench_bf16_eager_lanes3.json 2> $OUT/${TAG}_bench_bf16_eager.err
+python3 bench.py --full --dtype bf16 --graph --batch 8 --no-cpu-baseline > $OUT/${TAG}_bench_bf16_graph_b8.json 2> $OUT/${TAG}_bench_bf16_graph_b8.err
+python3 bench.py --full --dtype bf16 --graph --batch 64 --steps 10 --no-cpu-baseline > $OUT/${TAG}_bench_bf16_graph_b64.json 2> $OUT/${TAG}_bench_bf16_graph_b64.err
+python3 bench.py --full --dtype bf16 --graph --graph-lanes 4 --no-cpu-baseline > $OUT/${TAG}_bench_bf16_graph_lanes4.json 2> $OUT/${TAG}_bench_bf16_graph_lanes4.err
+python3 bench.py --full --dtype bf16 --graph --graph-lanes 8 --batch 8 --steps 48 --no-cpu-baseline > $OUT/${TAG}_bench_bf16_graph_b8_lanes8.json 2> $OUT/${TAG}_bench_bf16_graph_b8_lanes8.err
+python3 bench.py --full --dtype bf16 --graph --batch 128 --steps 6 --no-cpu-baseline > $OUT/${TAG}_bench_bf16_graph_b128.json 2> $OUT/${TAG}_bench_bf16_graph_b128.err
 echo "lp variants done"
 python3 bench.py --mode train --steps 10 > $OUT/${TAG}_bench_train.json 2> $OUT/${TAG}_bench_train.err
 python3 bench.py --mode train --gan --steps 10 > $OUT/${TAG}_bench_train_gan.json 2> $OUT/${TAG}_bench_train_gan.err
 python3 bench.py --mode train --gan --damsm-encoder --steps 10 --no-cpu-baseline > $OUT/${TAG}_bench_train_gan_damsm.json 2> $OUT/${TAG}_bench_train_gan_damsm.err
 echo "train done"
-python3 bench.py --branch-num 5 --steps 12 --warmup 3 > $OUT/${TAG}_bench_x16_fp32.json 2> $OUT/${TAG}_bench_x16_fp32.err
-python3 bench.py --branch-num 5 --dtype f16 --graph --steps 12 --warmup 3 --no-cpu-baseline > $OUT/${TAG}_bench_x16_f16_graph.json 2> $OUT/${TAG}_bench_x16_f16.err
-python3 bench.py --branch-num 5 --dtype bf16 --graph --steps 12 --warmup 3 --no-cpu-baseline > $OUT/${TAG}_bench_x16_bf16_graph.json 2> $OUT/${TAG}_bench_x16_bf16.err
+python3 bench.py --full --branch-num 5 --steps 12 --warmup 3 > $OUT/${TAG}_bench_x16_fp32.json 2> $OUT/${TAG}_bench_x16_fp32.err
+python3 bench.py --full --branch-num 5 --dtype f16 --graph --steps 12 --warmup 3 --no-cpu-baseline > $OUT/${TAG}_bench_x16_f16_graph.json 2> $OUT/${TAG}_bench_x16_f16.err
+python3 bench.py --full --branch-num 5 --dtype bf16 --graph --steps 12 --warmup 3 --no-cpu-baseline > $OUT/${TAG}_bench_x16_bf16_graph.json 2> $OUT/${TAG}_bench_x16_bf16.err
 echo "x16 done"
-TGSR_BENCH_REHEARSAL=1 python3 bench.py --gpus 2 --steps 10 --no-cpu-baseline > $OUT/${TAG}_bench_rehearsal_2ranks.json 2> $OUT/${TAG}_bench_rehearsal.err || echo "rehearsal failed"
+TGSR_BENCH_REHEARSAL=1 python3 bench.py --full --gpus 2 --steps 10 --no-cpu-baseline > $OUT/${TAG}_bench_rehearsal_2ranks.json 2> $OUT/${TAG}_bench_rehearsal.err || echo "rehearsal failed"
 fi
 if [ "$PART" != "bench" ]; then
 # (counter passes incl. FETCH_SIZE / WRITE_SIZE for the train steps as well: `train.roofline.traffic`)

@@ -7,5 +7,5 @@ timeout -k 10 900 python -m pytest tests -m gpu -x -q > $OUT/gputest_full.log 2>
 rc=$?
 echo "pytest rc=$rc"; tail -n 8 $OUT/gputest_full.log | cut -c1-200
 [ $rc -eq 0 ] || exit $rc
-timeout -k 10 400 python bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err; echo "bench rc=$?"
+timeout -k 10 400 python bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err; echo "bench rc=$?"
 tail -c 1500 $OUT/bench_default.json

@@ -5,7 +5,7 @@ OUT=gpurun_out/r06
 mkdir -p $OUT
 timeout -k 10 900 python -m pytest tests/test_hip_variants.py tests/test_hip_gan.py tests/test_hip_dp.py tests/test_hip_train.py -x -q -k "variants or graph_replayed or gloo or conv_bn_leaky_block or single_rank or pack_cache" > $OUT/t3.log 2>&1
 echo "pytest rc=$?"; tail -n 25 $OUT/t3.log
-timeout -k 10 600 python bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err; echo "bench rc=$?"
+timeout -k 10 600 python bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err; echo "bench rc=$?"
 python - <<'PY'
 import json
 try:
