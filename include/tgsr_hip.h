@@ -458,6 +458,29 @@ int tgsr_gconv(int dgrad, const float* A, const float* S, int64_t s_bstride, int
                int KH, int KW, int stride, int padh, int padw, const float* bias, int relu, int accumulate, const float* mask,
                float* out, int64_t o_bstride, float* ws, void* stream);
 int tgsr_gconv_pack(const float* w, const float* scale, float* out, int Cout, int Cin, int KK, int dgrad, void* stream);
+/*
+ * Training mode (pretrain_DAMSM.py:49-51 runs the frozen trunk with batch-statistics BatchNorm), one conv + BN + ReLU layer in two
+ * launches (three where K is split):
+ * tgsr_gconv_stats: tgsr_gconv(dgrad = 0, bias = NULL, relu = 0, accumulate = 0, mask = NULL) - the raw convolution, bit-identical to
+ *   that call in the same arithmetic form, into its channel slice - that also writes stat_partial [M][nslots][2]: per output channel
+ *   and slot of slot_px pixels (the GEMM's N tile, or 2048 pixels when K is split and the slab finish takes them; the last slot holds
+ *   the rest) the pair (sum, sum of squared deviations from the slot's mean), pixels past N excluded, fixed slots and order (no
+ *   atomics).  nslots / slot_px = tgsr_gconv_stats_nslots / tgsr_gconv_stats_slot_pixels(B, M, PH, PW, K); ws as for tgsr_gconv.
+ * tgsr_bn_train_relu_slice_from_stats: in place over C channels of HW pixels based at the slice (samples bstride floats apart):
+ *   y = relu((y - mean) * scale + beta) with the batch statistics combined from stat_partial (Chan's formula, double precision, a
+ *   fixed order); writes stats [4][C] (mean,
+ *   invstd, scale, shift), updates running_mean / running_var (momentum, unbiased variance; both NULL: none) and
+ *   num_batches_tracked (nullable) once.
+ */
+int tgsr_gconv_stats_nslots(int B, int M, int PH, int PW, int K);
+int tgsr_gconv_stats_slot_pixels(int B, int M, int PH, int PW, int K);
+int tgsr_gconv_stats(const float* A, const float* S, int64_t s_bstride, int B, int Hs, int Ws, int M, int K, int PH, int PW, int KH,
+                     int KW, int stride, int padh, int padw, float* out, int64_t o_bstride, float* ws, float* stat_partial,
+                     void* stream);
+int tgsr_bn_train_relu_slice_from_stats(float* y, int64_t bstride, int B, int C, int HW, const float* gamma, const float* beta,
+                                        float eps, float momentum, float* running_mean, float* running_var,
+                                        const float* stat_partial, int nslots, int slot_px, float* stats,
+                                        int64_t* num_batches_tracked, void* stream);
 int tgsr_maxpool3s2_fwd(const float* x, int64_t x_bstride, int B, int C, int H, int W, float* out, int64_t o_bstride, void* stream);
 int tgsr_maxpool3s2_bwd(const float* x, int64_t x_bstride, const float* dy, int64_t dy_bstride, int B, int C, int H, int W, float* dx,
                         int64_t dx_bstride, int accumulate, const float* mask, void* stream);

@@ -110,6 +110,10 @@ SIGNATURES = {
     "tgsr_gconv_ws_elems": (_i64, [_i, _i, _i, _i, _i]),
     "tgsr_gconv": (_i, [_i, _vp, _vp, _i64, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _i, _i, _vp, _vp, _i64, _vp, _vp]),
     "tgsr_gconv_pack": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    "tgsr_gconv_stats_nslots": (_i, [_i, _i, _i, _i, _i]),
+    "tgsr_gconv_stats_slot_pixels": (_i, [_i, _i, _i, _i, _i]),
+    "tgsr_gconv_stats": (_i, [_vp, _vp, _i64, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _i64, _vp, _vp, _vp]),
+    "tgsr_bn_train_relu_slice_from_stats": (_i, [_vp, _i64, _i, _i, _i, _vp, _vp, _f, _f, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp]),
     "tgsr_maxpool3s2_fwd": (_i, [_vp, _i64, _i, _i, _i, _i, _vp, _i64, _vp]),
     "tgsr_maxpool3s2_bwd": (_i, [_vp, _i64, _vp, _i64, _i, _i, _i, _i, _vp, _i64, _i, _vp, _vp]),
     "tgsr_avgpool3": (_i, [_vp, _i64, _i, _i, _i, _i, _vp, _i64, _i, _vp, _vp]),

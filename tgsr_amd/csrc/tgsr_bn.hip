@@ -334,6 +334,84 @@ __global__ __launch_bounds__(kBnThreads) void bn_fin_act_fwd_kernel(
   }
 }
 
+// Training-mode BatchNorm + ReLU of one conv + BN + ReLU layer of the Inception trunk, in place on a channel slice: y holds the raw
+// convolution (tgsr_gconv_stats) at channels [coff, coff + C) of a wider tensor, samples `bstride` floats apart; grid (C, nsplit).
+// The partials are (sum, sum of squared deviations from the slot's own mean) over slots of slot_px pixels (the last one holds the
+// rest): every workgroup combines its channel's by Chan's formula in double precision - mean = sum / n, M2 = sum_t M2_t +
+// n_t (mean_t - mean)^2 - each thread a strided share, the thread sums meeting in a fixed tree (every workgroup of the channel
+// gets the same bits); slice 0 publishes mean / invstd / scale / shift and updates the running statistics (momentum, unbiased
+// variance, as bn_affine_thread0), and each workgroup then writes relu((raw - mean) * scale + beta) over its range of the channel.
+__global__ __launch_bounds__(kBnThreads) void bn_relu_slice_kernel(float* __restrict__ y, int64_t bstride, int B, int C, int HW,
+                                                                   const float* __restrict__ partial, int nslots, int slot_px,
+                                                                   const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                                   float eps, float momentum, float* running_mean, float* running_var,
+                                                                   float* stats, long long* num_batches_tracked, int nsplit) {
+  __shared__ double red[kBnThreads];
+  __shared__ float bc[3];
+  const int c = blockIdx.x, sp = blockIdx.y, tid = threadIdx.x;
+  const int total = B * HW;
+  const float2* pp = reinterpret_cast<const float2*>(partial + (int64_t)c * nslots * 2);
+  auto tree = [&](double v) {
+    __syncthreads();                       // (the previous tree's readers are done)
+    red[tid] = v;
+    __syncthreads();
+#pragma unroll
+    for (int w = kBnThreads / 2; w >= 1; w >>= 1) {
+      if (tid < w) red[tid] += red[tid + w];
+      __syncthreads();
+    }
+    return red[0];
+  };
+  double s = 0.0;
+  for (int t = tid; t < nslots; t += kBnThreads) s += (double)pp[t].x;
+  const double mean = tree(s) / (double)total;
+  double q = 0.0;
+  for (int t = tid; t < nslots; t += kBnThreads) {
+    const float2 v = pp[t];
+    const int nt = min(slot_px, total - t * slot_px);
+    const double d = (double)v.x / (double)nt - mean;
+    q += (double)v.y + (double)nt * d * d;
+  }
+  const double m2 = tree(q);
+  if (tid == 0) {
+    const double var = m2 / (double)total;
+    const float is = (float)(1.0 / sqrt(var + (double)eps));
+    const float sc = gamma[c] * is;
+    bc[0] = sc;
+    bc[1] = (float)mean;
+    bc[2] = beta[c];
+    if (sp == 0) {
+      stats[c] = (float)mean;
+      stats[C + c] = is;
+      stats[2 * C + c] = sc;
+      stats[3 * C + c] = beta[c] - (float)mean * sc;
+      if (running_mean) {
+        const double unb = total > 1 ? var * ((double)total / (double)(total - 1)) : var;
+        running_mean[c] = (1.f - momentum) * running_mean[c] + momentum * (float)mean;
+        running_var[c] = (1.f - momentum) * running_var[c] + momentum * (float)unb;
+      }
+      if (c == 0 && num_batches_tracked) *num_batches_tracked += 1;
+    }
+  }
+  __syncthreads();
+  const float sv = bc[0], mv = bc[1], bv = bc[2];
+  const int per = (total + nsplit - 1) / nsplit;
+  const int lo = sp * per, hi = min(total, lo + per);
+  float* yc = y + (int64_t)c * HW;
+  int e = lo + tid;
+  int b = e / HW, p = e - b * HW;
+  for (; e < hi; e += kBnThreads) {
+    float* o = yc + b * bstride + p;
+    const float v = (*o - mv) * sv + bv;
+    *o = v > 0.f ? v : 0.f;
+    p += kBnThreads;
+    while (p >= HW) {
+      p -= HW;
+      ++b;
+    }
+  }
+}
+
 // Backward, pass 2 with the finalize folded in: grid (Co, nsplit) - the partials of bn_act_bwd_reduce_kernel on the same grid
 // FUSED (as the forward's: one workgroup per channel, no GLU): pass 1 runs inside this kernel, the same sums in the same order.
 template <bool GLU, bool FUSED = false>
@@ -543,6 +621,23 @@ extern "C" int tgsr_bn_train_fwd_from_stats(const float* raw, int B, int C, int 
   return bn_train_fwd(raw, B, C, HW, gamma, beta, eps, momentum, running_mean, running_var, glu, residual, res_bstride,
                       const_cast<float*>(stat_partial), nslots, mean, invstd, scale, shift, out, out_bstride,
                       num_batches_tracked, stream);
+}
+
+// y: the raw convolution, based at the first channel of its slice of a wider tensor (tgsr_gconv_stats wrote it and stat_partial
+// [C][nslots][2], slots of slot_px pixels); in place: y = relu(batch_norm_train(y)).  stats [4][C]: mean, invstd, scale, shift.
+extern "C" int tgsr_bn_train_relu_slice_from_stats(float* y, int64_t bstride, int B, int C, int HW, const float* gamma,
+                                                   const float* beta, float eps, float momentum, float* running_mean,
+                                                   float* running_var, const float* stat_partial, int nslots, int slot_px,
+                                                   float* stats, int64_t* num_batches_tracked, void* stream) {
+  if (!y || !gamma || !beta || !stat_partial || !stats || B < 1 || C < 1 || HW < 1 || nslots < 1 || slot_px < 1) return TGSR_EINVAL;
+  if ((int64_t)(nslots - 1) * slot_px >= (int64_t)B * HW || (int64_t)nslots * slot_px < (int64_t)B * HW) return TGSR_EINVAL;
+  if ((running_mean == nullptr) != (running_var == nullptr)) return TGSR_EINVAL;
+  if ((int64_t)B * HW >= (1ll << 31) - kBnThreads || bstride < (int64_t)C * HW) return TGSR_EUNSUPPORTED;
+  const int nsplit = tgsr_bn_train_nsplit(B, C, HW);
+  hipLaunchKernelGGL(bn_relu_slice_kernel, dim3(C, nsplit), dim3(kBnThreads), 0, as_stream(stream), y, bstride, B, C, HW,
+                     stat_partial, nslots, slot_px, gamma, beta, eps, momentum, running_mean, running_var, stats,
+                     reinterpret_cast<long long*>(num_batches_tracked), nsplit);
+  return note_launch(hipGetLastError(), "bn_relu_slice_kernel");
 }
 
 extern "C" int tgsr_bn_train_bwd(const float* dout, const float* raw, int B, int C, int HW, const float* scale,

@@ -40,7 +40,10 @@ struct IgArgs {
   unsigned gmKK, gmKW;        // q / KK = (q * gmKK) >> 16 for q < 64;  t / KW likewise
   int64_t s_bstride, o_bstride;          // batch strides (elements) of S and of the output (channel slices of wider tensors)
   const float* gbias;
-  const float* gmask;         // nullable, laid out like the output: the contribution is kept where gmask > 0
+  union {
+    const float* gmask;       // nullable, laid out like the output: the contribution is kept where gmask > 0
+    float* gstat;             // STATS (no mask): BatchNorm statistics partials [M][gridDim.x][2]
+  };
   int grelu, gacc;
 };
 
@@ -410,7 +413,10 @@ __global__ __launch_bounds__(256) void ig6_pack_dgrad_kernel(const float* __rest
 }
 
 // APRE: the A operand arrives pre-split as the LDS images (forward / data gradient; ig6_split_rows_kernel / ig6_pack_dgrad_kernel).
-template <int MODE, bool WIDE = false, bool APRE = false>
+// STATS (kFwdG, one slab, no bias / ReLU / mask / accumulate: the raw convolution of a training-mode layer): the epilogue also writes
+// the tile's BatchNorm statistics, one (sum, sum of squares) pair per output channel into slot blockIdx.x of a.gstat
+// [M][gridDim.x][2] (gemm_tile_stats).
+template <int MODE, bool WIDE = false, bool APRE = false, bool STATS = false>
 __global__ __launch_bounds__(256, 2) void dconv_igemm6_kernel(IgArgs a) {
   constexpr bool WG = MODE == kWgrad4 || MODE == kWgrad3;
   constexpr bool KG = MODE == kFwdG || MODE == kDgradG;    // generic taps: k = (channel, tap) in KKs, KK a launch argument
@@ -768,12 +774,16 @@ __global__ __launch_bounds__(256, 2) void dconv_igemm6_kernel(IgArgs a) {
           if (a.nsplit <= 1) {
             if (a.gbias) v += a.gbias[m];
             if (a.grelu) v = v > 0.f ? v : 0.f;
-            if (a.gmask && !(a.gmask[obase + m * mstride] > 0.f)) v = 0.f;
+            if (!STATS && a.gmask && !(a.gmask[obase + m * mstride] > 0.f)) v = 0.f;
             if (a.gacc) v += ob[obase + m * mstride];
           }
         } else if (a.act) v = v > 0.f ? v : 0.2f * v;
         ob[obase + m * mstride] = v;
       }
+  }
+  if constexpr (STATS) {
+    static_assert(MODE == kFwdG && !APRE, "the statistics epilogue serves the generic-tap forward");
+    gemm_tile_stats<WIDE>(acc, m0, n0, a.M, a.N, a.gstat, gridDim.x, blockIdx.x, reinterpret_cast<float*>(&a_s[0][0]));
   }
 }
 
@@ -1115,6 +1125,37 @@ int ig6_gconv_launch(int dgrad, const float* A, const float* S, int64_t s_bstrid
     else hipLaunchKernelGGL((dconv_igemm6_kernel<kFwdG, false, false>), grid, dim3(256), 0, s, a);
   }
   return note_launch(hipGetLastError(), "dconv_igemm6_kernel<generic taps>");
+}
+
+// The forward above in its statistics form (one slab: the caller splits K through ig6_gconv_launch and takes the statistics in its
+// slab finish): the raw convolution into its channel slice plus st [M][nslots][2], nslots = the grid's N tiles.
+int ig6_gconv_stats_launch(const float* A, const float* S, int64_t s_bstride, int64_t s_bytes, int B, int Hs, int Ws, int M, int K,
+                           int PH, int PW, int KH, int KW, int stride, int padh, int padw, float* out, int64_t o_bstride, float* st,
+                           int nslots, hipStream_t s) {
+  const int KK = KH * KW;
+  if (!g_ig_split || KK > 25 || K % kIgKC != 0 || (stride != 1 && stride != 2)) return TGSR_EUNSUPPORTED;
+  const int64_t a_bytes = (int64_t)M * K * 4;
+  if ((reinterpret_cast<uintptr_t>(A) & 15) || s_bytes >= (1ll << 31) || a_bytes >= (1ll << 32)) return TGSR_EUNSUPPORTED;
+  const int64_t N = (int64_t)B * PH * PW;
+  if (N >= (1ll << 31)) return TGSR_EUNSUPPORTED;
+  IgArgs a = {};
+  a.A = A; a.S = S; a.out = out;
+  a.M = M; a.N = (int)N; a.K = K; a.C = K / KK; a.Hs = Hs; a.Ws = Ws; a.PH = PH; a.PW = PW; a.OH = PH; a.OW = PW;
+  a.nsplit = 1; a.chunks_per_split = K / kIgKC;
+  a.slab_stride = 0;
+  a.act = 0;
+  a.a_bytes = a_bytes; a.s_bytes = s_bytes;
+  a.gKH = KH; a.gKW = KW; a.gKK = KK; a.gst = stride; a.gpadh = padh; a.gpadw = padw;
+  a.gmKK = (unsigned)((65536 + KK - 1) / KK); a.gmKW = (unsigned)((65536 + KW - 1) / KW);
+  a.s_bstride = s_bstride; a.o_bstride = o_bstride;
+  a.gbias = nullptr; a.grelu = 0; a.gacc = 0;
+  a.gstat = st;                                            // (the union's gmask: none)
+  const bool wide = M <= 64;
+  const dim3 grid(wide ? (unsigned)((N + 255) / 256) : (unsigned)((N + 127) / 128), wide ? (unsigned)((M + 63) / 64) : (unsigned)((M + 127) / 128), 1);
+  if ((int)grid.x != nslots) return TGSR_EINVAL;
+  if (wide) hipLaunchKernelGGL((dconv_igemm6_kernel<kFwdG, true, false, true>), grid, dim3(256), 0, s, a);
+  else hipLaunchKernelGGL((dconv_igemm6_kernel<kFwdG, false, false, true>), grid, dim3(256), 0, s, a);
+  return note_launch(hipGetLastError(), "dconv_igemm6_kernel<generic taps, stats>");
 }
 
 }  // namespace tgsr

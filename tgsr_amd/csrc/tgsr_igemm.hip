@@ -30,7 +30,10 @@ struct GcArgs {
   int64_t s_bstride, o_bstride;      // batch strides (elements) of S and out
   int KH, KW, SH, PADH, PADW;
   int relu, accumulate;
-  const float* mask;     // nullable; laid out like `out`: the contribution is kept where mask > 0 (the ReLU of the tensor whose gradient this is)
+  union {
+    const float* mask;   // nullable; laid out like `out`: the contribution is kept where mask > 0 (the ReLU of the tensor whose gradient this is)
+    float* st;           // STATS (no mask): BatchNorm statistics partials [M][gridDim.x][2]
+  };
   int nsplit, chunks_per_split;
   int64_t slab_stride;
 };
@@ -38,7 +41,9 @@ struct GcArgs {
 constexpr int kGcKC = 16;
 
 // DG = false: forward gather; true: data-gradient gather.  WIDE: a 64 (M) x 256 (N) tile for M <= 64, else 128 x 128.
-template <bool DG, bool WIDE>
+// STATS (forward, nsplit == 1, no bias / ReLU / mask / accumulate: the raw convolution): the epilogue also writes the tile's BatchNorm
+// statistics, one (sum, sum of squares) pair per output channel into slot blockIdx.x of a.st [M][gridDim.x][2] (gemm_tile_stats).
+template <bool DG, bool WIDE, bool STATS = false>
 __global__ __launch_bounds__(256) void gconv_igemm_kernel(GcArgs a) {
   constexpr int MB = WIDE ? 64 : 128, NB = WIDE ? 256 : 128, PA = MB + 4, PB = NB + 4, NLA = MB / 16, NLB = WIDE ? 16 : 8;
   __shared__ float a_s[2][kGcKC * PA];
@@ -184,12 +189,13 @@ __global__ __launch_bounds__(256) void gconv_igemm_kernel(GcArgs a) {
         if (!slabs) {
           if (a.bias) v += a.bias[m];
           if (a.relu) v = v > 0.f ? v : 0.f;
-          if (a.mask && !(a.mask[o - a.out] > 0.f)) v = 0.f;
+          if (!STATS && a.mask && !(a.mask[o - a.out] > 0.f)) v = 0.f;
           if (a.accumulate) v += *o;
         }
         *o = v;
       }
   }
+  if constexpr (STATS) gemm_tile_stats<WIDE>(acc, m0, n0, a.M, a.N, a.st, gridDim.x, blockIdx.x, &a_s[0][0]);
 }
 
 // Data gradient with respect to an IMAGE (Cin <= 4: Conv2d_1a_3x3, 3 -> 32, 3x3 / stride 2): as a GEMM it is M = 3 rows of a 64-row
@@ -256,6 +262,52 @@ __global__ __launch_bounds__(256) void gconv_finish_kernel(const float* __restri
     if (mask && !(mask[(int64_t)b * o_bstride + r] > 0.f)) v = 0.f;
     if (accumulate) v += *o;
     *o = v;
+  }
+}
+
+// The statistics form of the slab finish (a training-mode layer split over K): grid (nslots, M), workgroup (slot, m) owns the
+// pixels n = b hw + r in [slot kGcStatR, (slot + 1) kGcStatR) of channel m: it sums their slabs in gconv_finish_kernel's order
+// (the same raw bits), writes them into the output's channel slice, and writes st[m][slot] = (sum, sum of squared deviations from
+// the range's mean) - the pair gemm_tile_stats writes, the second pass over the values it has just written itself.
+constexpr int kGcStatR = 2048;
+
+__device__ __forceinline__ float gc_block_sum(float v, float* red) {
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return (red[0] + red[1]) + (red[2] + red[3]);
+}
+
+__global__ __launch_bounds__(256) void gconv_finish_stats_kernel(const float* __restrict__ slabs, int nsplit, int64_t slab_stride,
+                                                                 float* __restrict__ out, int M, int hw, int N, int64_t o_bstride,
+                                                                 float* __restrict__ st, int nslots) {
+  __shared__ float red[4];
+  const int slot = blockIdx.x, m = blockIdx.y;
+  const int lo = slot * kGcStatR, hi = min(N, lo + kGcStatR);
+  float s = 0.f;
+  for (int n = lo + (int)threadIdx.x; n < hi; n += 256) {
+    const int b = n / hw, r = n - b * hw;
+    const int64_t e = ((int64_t)b * M + m) * hw + r;
+    float v = 0.f;
+    for (int zz = 0; zz < nsplit; ++zz) v += slabs[(int64_t)zz * slab_stride + e];
+    out[(int64_t)b * o_bstride + (int64_t)m * hw + r] = v;
+    s += v;
+  }
+  s = gc_block_sum(s, red);
+  const float mu = s / (float)(hi - lo);
+  float q = 0.f;
+  for (int n = lo + (int)threadIdx.x; n < hi; n += 256) {           // (the values this thread wrote above)
+    const int b = n / hw, r = n - b * hw;
+    const float d = out[(int64_t)b * o_bstride + (int64_t)m * hw + r] - mu;
+    q += d * d;
+  }
+  q = gc_block_sum(q, red);
+  if (threadIdx.x == 0) {
+    float* p = st + ((int64_t)m * nslots + slot) * 2;
+    p[0] = s;
+    p[1] = q;
   }
 }
 
@@ -475,6 +527,10 @@ __global__ __launch_bounds__(256) void bilinear_bwd_kernel(const float* __restri
 int ig6_gconv_launch(int dgrad, const float* A, const float* S, int64_t s_bstride, int64_t s_bytes, int B, int Hs, int Ws, int M, int K,
                      int PH, int PW, int KH, int KW, int stride, int padh, int padw, const float* bias, int relu, int accumulate,
                      const float* mask, float* out, int64_t o_bstride, float* slabs, int nsplit, int chunks_per_split, hipStream_t s);
+// ... and its statistics form (forward, one slab: the raw convolution plus one (sum, sum of squares) pair per channel and N tile)
+int ig6_gconv_stats_launch(const float* A, const float* S, int64_t s_bstride, int64_t s_bytes, int B, int Hs, int Ws, int M, int K,
+                           int PH, int PW, int KH, int KW, int stride, int padh, int padw, float* out, int64_t o_bstride, float* st,
+                           int nslots, hipStream_t s);
 
 static int g_gconv_form = [] {              // TGSR_GCONV_SPLIT=0: the fp32-MFMA kernel of this file everywhere
   const char* e = getenv("TGSR_GCONV_SPLIT");
@@ -591,6 +647,86 @@ extern "C" int tgsr_gconv(int dgrad, const float* A, const float* S, int64_t s_b
   hipLaunchKernelGGL(gconv_finish_kernel, dim3(gc_grid(total)), dim3(256), 0, s, ws, ns, a.slab_stride, bias, out, M, PH * PW, total,
                      o_bstride, relu, accumulate, mask);
   return note_launch(hipGetLastError(), "gconv_finish_kernel");
+}
+
+// The K split tgsr_gconv / tgsr_gconv_stats use for a forward shape: (slabs, chunks per slab).
+static void gc_split(int M, int N, int K, int& ns, int& cps) {
+  const int chunks = (K + kGcKC - 1) / kGcKC;
+  ns = tgsr_gconv_nsplit(M, N, K);
+  cps = (chunks + ns - 1) / ns;
+  ns = (chunks + cps - 1) / cps;
+}
+
+// Statistics slots per channel of tgsr_gconv_stats: one per N tile of the GEMM, or per kGcStatR pixels when K is split.
+extern "C" int tgsr_gconv_stats_nslots(int B, int M, int PH, int PW, int K) {
+  const int64_t N64 = (int64_t)B * PH * PW;
+  if (B < 1 || M < 1 || PH < 1 || PW < 1 || K < 1 || N64 >= (1ll << 31)) return 0;
+  const int N = (int)N64;
+  int ns, cps;
+  gc_split(M, N, K, ns, cps);
+  if (ns > 1) return (N + kGcStatR - 1) / kGcStatR;
+  return M <= 64 ? (N + 255) / 256 : (N + 127) / 128;
+}
+
+// Pixels per statistics slot of tgsr_gconv_stats (the last slot holds the remainder): the GEMM's N tile, or kGcStatR when K is split.
+extern "C" int tgsr_gconv_stats_slot_pixels(int B, int M, int PH, int PW, int K) {
+  const int64_t N64 = (int64_t)B * PH * PW;
+  if (B < 1 || M < 1 || PH < 1 || PW < 1 || K < 1 || N64 >= (1ll << 31)) return 0;
+  int ns, cps;
+  gc_split(M, (int)N64, K, ns, cps);
+  return ns > 1 ? kGcStatR : (M <= 64 ? 256 : 128);
+}
+
+// Training-mode forward of a conv + BatchNorm layer, first half: the raw convolution (no bias, no ReLU) into its channel slice
+// and its batch statistics, st [M][nslots][2] (nslots = tgsr_gconv_stats_nslots), for tgsr_bn_train_relu_slice_from_stats.
+// The raw values are bit-identical to tgsr_gconv(dgrad = 0, bias = NULL, relu = 0) in the same arithmetic form.
+extern "C" int tgsr_gconv_stats(const float* A, const float* S, int64_t s_bstride, int B, int Hs, int Ws, int M, int K, int PH,
+                                int PW, int KH, int KW, int stride, int padh, int padw, float* out, int64_t o_bstride, float* ws,
+                                float* stat_partial, void* stream) {
+  if (!A || !S || !out || !stat_partial || B < 1 || M < 1 || K < 1 || Hs < 1 || Ws < 1 || PH < 1 || PW < 1) return TGSR_EINVAL;
+  if (KH < 1 || KW < 1 || KH * KW > 64 || KH > 255 || KW > 255 || (stride != 1 && stride != 2) || padh < 0 || padw < 0) return TGSR_EUNSUPPORTED;
+  if (K % (KH * KW)) return TGSR_EINVAL;
+  const int64_t N64 = (int64_t)B * PH * PW;
+  if (N64 >= (1ll << 31) || (int64_t)M * K >= (1ll << 31)) return TGSR_EUNSUPPORTED;
+  const int N = (int)N64;
+  int ns, cps;
+  gc_split(M, N, K, ns, cps);
+  if (ns > 1 && !ws) return TGSR_EINVAL;
+  const int nslots = tgsr_gconv_stats_nslots(B, M, PH, PW, K);
+  hipStream_t s = as_stream(stream);
+  GcArgs a;
+  a.A = A; a.S = S; a.bias = nullptr; a.out = ns > 1 ? ws : out;
+  a.M = M; a.N = N; a.K = K; a.Hs = Hs; a.Ws = Ws; a.PH = PH; a.PW = PW;
+  a.s_bstride = s_bstride; a.o_bstride = o_bstride;
+  a.KH = KH; a.KW = KW; a.SH = stride; a.PADH = padh; a.PADW = padw;
+  a.relu = 0; a.accumulate = 0;
+  a.st = ns > 1 ? nullptr : stat_partial;                // (the union's mask: none)
+  a.nsplit = ns; a.chunks_per_split = cps; a.slab_stride = (int64_t)B * M * PH * PW;
+  const bool wide = M <= 64;
+  const dim3 grid((N + (wide ? 255 : 127)) / (wide ? 256 : 128), (M + (wide ? 63 : 127)) / (wide ? 64 : 128), ns);
+  int rc6 = TGSR_EUNSUPPORTED;
+  if (g_gconv_form) {
+    const int64_t s_bytes = ((int64_t)(B - 1) * s_bstride + (int64_t)(K / (KH * KW)) * Hs * Ws) * 4;
+    rc6 = ns > 1 ? ig6_gconv_launch(0, A, S, s_bstride, s_bytes, B, Hs, Ws, M, K, PH, PW, KH, KW, stride, padh, padw, nullptr, 0, 0,
+                                    nullptr, out, o_bstride, ws, ns, cps, s)
+                 : ig6_gconv_stats_launch(A, S, s_bstride, s_bytes, B, Hs, Ws, M, K, PH, PW, KH, KW, stride, padh, padw, out,
+                                          o_bstride, stat_partial, nslots, s);
+    if (rc6 != TGSR_OK && rc6 != TGSR_EUNSUPPORTED) return rc6;
+  }
+  if (rc6 == TGSR_OK) {
+    if (ns == 1) return TGSR_OK;
+  } else if (ns > 1) {                       // K split: the slabs of tgsr_gconv, then the statistics finish below
+    if (wide) hipLaunchKernelGGL((gconv_igemm_kernel<false, true>), grid, dim3(256), 0, s, a);
+    else hipLaunchKernelGGL((gconv_igemm_kernel<false, false>), grid, dim3(256), 0, s, a);
+  } else {
+    if (wide) hipLaunchKernelGGL((gconv_igemm_kernel<false, true, true>), grid, dim3(256), 0, s, a);
+    else hipLaunchKernelGGL((gconv_igemm_kernel<false, false, true>), grid, dim3(256), 0, s, a);
+  }
+  int rc = note_launch(hipGetLastError(), "gconv_igemm_kernel<stats>");
+  if (rc || ns == 1) return rc;
+  hipLaunchKernelGGL(gconv_finish_stats_kernel, dim3(nslots, M), dim3(256), 0, s, ws, ns, a.slab_stride, out, M, PH * PW, N, o_bstride,
+                     stat_partial, nslots);
+  return note_launch(hipGetLastError(), "gconv_finish_stats_kernel");
 }
 
 extern "C" int tgsr_gconv_pack(const float* w, const float* scale, float* out, int Cout, int Cin, int KK, int dgrad, void* stream) {

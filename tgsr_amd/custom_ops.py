@@ -505,6 +505,17 @@ gconv = _define("gconv(bool dgrad, Tensor A, Tensor S, int s_coff, int s_ch, Ten
                 "int padh, int padw, Tensor? bias, bool relu, bool accumulate, Tensor(b!)? ws, Tensor? mask) -> ()",
                 lambda dg, A, S, sc, sch, out, oc, kh, kw, st, ph, pw, bias, relu, acc, ws, mask:
                 ops.gconv(dg, A, S, sc, sch, out, oc, kh, kw, st, ph, pw, bias, relu, acc, ws, mask), lambda *a: None)
+# training mode (batch-statistics BatchNorm): the raw convolution + its statistics partials, then BN + ReLU in place on the slice
+gconv_stats = _define("gconv_stats(Tensor A, Tensor S, int s_coff, int s_ch, Tensor(a!) out, int o_coff, int kh, int kw, int stride, "
+                      "int padh, int padw, Tensor(b!)? ws, Tensor(c!) stat_partial) -> ()",
+                      lambda A, S, sc, sch, out, oc, kh, kw, st, ph, pw, ws, part:
+                      (ops.gconv_stats(A, S, sc, sch, out, oc, kh, kw, st, ph, pw, ws, part), None)[1], lambda *a: None)
+bn_train_relu_slice_from_stats = _define(
+    "bn_train_relu_slice_from_stats(Tensor(a!) y, int coff, Tensor gamma, Tensor beta, float eps, float momentum, "
+    "Tensor(b!)? running_mean, Tensor(c!)? running_var, Tensor(d!)? num_batches_tracked, Tensor stat_partial, int slot_px, "
+    "Tensor(e!) stats) -> ()",
+    lambda y, coff, g, b, eps, mom, rm, rv, nbt, part, spx, stats:
+    (ops.bn_train_relu_slice_from_stats(y, coff, g, b, eps, mom, rm, rv, nbt, part, spx, stats), None)[1], lambda *a: None)
 maxpool3s2 = _define("maxpool3s2(Tensor x, Tensor(a!) out, int o_coff) -> ()", lambda x, out, oc: ops.maxpool3s2(x, out, oc),
                      lambda *a: None)
 maxpool3s2_bwd = _define("maxpool3s2_bwd(Tensor x, Tensor dy, int dy_coff, Tensor(a!) dx, bool accumulate, Tensor? mask) -> ()",

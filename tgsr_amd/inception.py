@@ -48,6 +48,7 @@ class _Layer:
         self.stride = conv.stride[0]
         self.ph, self.pw = conv.padding
         self.key = None
+        self.ukey = None
         self.refresh()
 
     def _key(self):
@@ -79,6 +80,20 @@ class _Layer:
                     self.cls.append((py, px, C.gconv_pack(wc, scale, True), wc.shape[2], wc.shape[3], (py + self.ph - ky0) // 2,
                                      (px + self.pw - kx0) // 2))
         self.key = k
+
+    def refresh_train(self):
+        """The training-mode pack: the filter with UNIT scale (batch-statistics BatchNorm normalises the raw convolution after the
+        fact), keyed on the conv weight alone - the running statistics change every batch and do not enter it."""
+        w = self.conv.weight
+        k = (w.data_ptr(), w._version)
+        if k != self.ukey:
+            self.wu = C.gconv_pack(w.detach(), None, False)
+            self.ukey = k
+
+    def bn_train_ok(self):
+        """Batch-statistics BatchNorm this walk reproduces: affine, tracked running statistics, an exponential average."""
+        bn = self.bn
+        return bn.affine and bn.track_running_stats and bn.momentum is not None and bn.num_batches_tracked is not None
 
     def class_dgrad_ok(self, H, W):
         """The class form covers unpadded layers on input sizes the forward uses completely ((H - k) even: no trailing row / column
@@ -113,6 +128,7 @@ class InceptionTrunk:
                     if hasattr(sub, "conv") and hasattr(sub, "bn"):
                         self.layers[name + "." + bname] = _Layer(sub)
         self.tape = None
+        self.train = False                     # the walk in progress normalises with batch statistics (forward(train=True))
         self.nstreams = TRUNK_STREAMS
         self.bwd_stream = None                 # see TrunkFn.backward
         self._side = None                      # the side streams (created on first use, distinct from the caller's)
@@ -193,6 +209,24 @@ class InceptionTrunk:
             dst = self._new(B, L.cout, OH, OW, x.device)
         y = self.tensors[dst]
         ws = self._ws(ops_ws(B, L.cout, OH, OW, L.cin * L.kh * L.kw), x.device, s)
+        if self.train:
+            # batch-statistics BatchNorm: the raw convolution straight into its slice with its statistics partials, then BN + ReLU in
+            # place over the slice (the partials live until the next walk opens: stream s still reads them - see _ws)
+            bn = L.bn
+            from . import ops
+            K = L.cin * L.kh * L.kw
+            part = torch.empty(L.cout, ops.gconv_stats_nslots(B, L.cout, OH, OW, K), 2, dtype=torch.float32, device=x.device)
+            stats = torch.empty(4, L.cout, dtype=torch.float32, device=x.device)
+            self._ws_old += [part, stats]
+            with self._run(s):
+                C.gconv_stats(L.wu, x, 0, L.cin, y, coff, L.kh, L.kw, L.stride, L.ph, L.pw, ws, part)
+                C.bn_train_relu_slice_from_stats(y, coff, bn.weight, bn.bias, bn.eps, bn.momentum, bn.running_mean, bn.running_var,
+                                                 bn.num_batches_tracked, part, ops.gconv_stats_slot_pixels(B, L.cout, OH, OW, K), stats)
+            # the kernel wrote the running statistics through raw pointers: tell autograd's version counters, which the eval
+            # packs (_Layer.refresh) key on
+            torch.autograd.graph.increment_version(bn.running_mean)
+            torch.autograd.graph.increment_version(bn.running_var)
+            return dst
         with self._run(s):
             C.gconv(False, L.wf, x, 0, L.cin, y, coff, L.kh, L.kw, L.stride, L.ph, L.pw, L.shift, True, False, ws, None)
         self.tape.append(("conv", L, src, dst, coff, s))
@@ -293,10 +327,20 @@ class InceptionTrunk:
 
     # ------------------------------------------------------------------ the walk
     @torch.no_grad()
-    def forward(self, x):
+    def forward(self, x, train=False):
+        """train=True: the trunk in training mode (pretrain_DAMSM.py:49-51) - every BatchNorm normalises with the batch's statistics
+        and updates its running statistics and num_batches_tracked, as nn.BatchNorm2d.train() does; no tape is kept (no gradient
+        reaches the image through batch statistics here)."""
         if not (x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and x.shape[1] == 3):
             raise TgsrError("InceptionTrunk: a HIP fp32 image batch [B, 3, H, W] expected, got %s %s" % (x.dtype, tuple(x.shape)))
-        self.refresh()
+        if train:
+            for L in self.layers.values():
+                if not L.bn_train_ok():
+                    raise TgsrError("InceptionTrunk: training mode needs affine BatchNorm with running statistics and a momentum")
+                L.refresh_train()
+        else:
+            self.refresh()
+        self.train = bool(train)
         self.tensors, self.tape = [], []
         self._open_streams(x.device)
         self.in_hw = (x.shape[2], x.shape[3])
@@ -315,7 +359,11 @@ class InceptionTrunk:
         for name in self.MIXED[8:]:
             t = self.marks[name] = self._block(name, t)
         self.last_id = t
-        return self.tensors[self.feat_id], C.plane_mean(self.tensors[t])                      # F.avg_pool2d(x, 8) on the 8 x 8 map
+        out = self.tensors[self.feat_id], C.plane_mean(self.tensors[t])                       # F.avg_pool2d(x, 8) on the 8 x 8 map
+        if self.train:
+            self.tensors = self.tape = None
+            self.train = False
+        return out
 
     @torch.no_grad()
     def backward(self, d_features, d_pooled):

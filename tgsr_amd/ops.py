@@ -1486,6 +1486,78 @@ def gconv(dgrad: bool, A: torch.Tensor, S: torch.Tensor, s_coff: int, s_ch: int,
 
 
 
+def gconv_stats_nslots(B: int, M: int, PH: int, PW: int, K: int) -> int:
+    """Statistics slots per channel gconv_stats writes for this forward shape (stat_partial is [M, nslots, 2])."""
+    return int(_lib.lib().tgsr_gconv_stats_nslots(B, M, PH, PW, K))
+
+
+def gconv_stats_slot_pixels(B: int, M: int, PH: int, PW: int, K: int) -> int:
+    """Pixels per statistics slot of gconv_stats for this forward shape (the last slot holds the remainder)."""
+    return int(_lib.lib().tgsr_gconv_stats_slot_pixels(B, M, PH, PW, K))
+
+
+def gconv_stats(A: torch.Tensor, S: torch.Tensor, s_coff: int, s_ch: int, out: torch.Tensor, o_coff: int, kh: int, kw: int,
+                stride: int, padh: int, padw: int, ws: Optional[torch.Tensor], stat_partial: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The raw forward convolution (gconv without bias / ReLU, the same bits) into channels [o_coff, o_coff + A.shape[0]) of out, and
+    its BatchNorm batch statistics: per output channel and slot of gconv_stats_slot_pixels pixels the pair (sum, sum of squared
+    deviations from the slot's mean), stat_partial [M, nslots, 2] (allocated when None).  Returns stat_partial."""
+    _need_hip(A, S, out, ws, stat_partial)
+    M, K = A.shape
+    B, Hs, Ws = S.shape[0], S.shape[2], S.shape[3]
+    PH, PW = out.shape[2], out.shape[3]
+    if K != s_ch * kh * kw or s_coff + s_ch > S.shape[1] or o_coff + M > out.shape[1] or out.shape[0] != B:
+        raise TgsrError("gconv_stats: A %s against %d channels of %s -> channels %d.. of %s" % (tuple(A.shape), s_ch, tuple(S.shape),
+                                                                                                o_coff, tuple(out.shape)))
+    if PH != (Hs + 2 * padh - kh) // stride + 1 or PW != (Ws + 2 * padw - kw) // stride + 1:
+        raise TgsrError("gconv_stats: %dx%d / stride %d / pad (%d, %d) does not map %s to %s" % (kh, kw, stride, padh, padw,
+                                                                                                tuple(S.shape), tuple(out.shape)))
+    need = gconv_ws_elems(B, M, PH, PW, K)
+    if need and (ws is None or ws.numel() < need):
+        raise TgsrError("gconv_stats: %d floats of workspace needed" % need)
+    ns = gconv_stats_nslots(B, M, PH, PW, K)
+    if stat_partial is None:
+        stat_partial = torch.empty(M, ns, 2, dtype=torch.float32, device=out.device)
+    elif tuple(stat_partial.shape) != (M, ns, 2) or stat_partial.dtype != torch.float32 or not stat_partial.is_contiguous():
+        raise TgsrError("gconv_stats: stat_partial %s, expected (%d, %d, 2) fp32" % (tuple(stat_partial.shape), M, ns))
+    sp, sbs = _slice_ptr(S, s_coff)
+    op, obs = _slice_ptr(out, o_coff)
+    check(_lib.lib().tgsr_gconv_stats(_p(A.contiguous()), sp, sbs, B, Hs, Ws, M, K, PH, PW, kh, kw, stride, padh, padw, op, obs, _p(ws),
+                                      _p(stat_partial), _stream()), "tgsr_gconv_stats")
+    return stat_partial
+
+
+def bn_train_relu_slice_from_stats(y: torch.Tensor, coff: int, gamma: torch.Tensor, beta: torch.Tensor, eps: float, momentum: float,
+                                   running_mean: Optional[torch.Tensor], running_var: Optional[torch.Tensor],
+                                   nbt: Optional[torch.Tensor], stat_partial: torch.Tensor, slot_px: int,
+                                   stats: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """In place over channels [coff, coff + C) of y (C = stat_partial.shape[0], the raw convolution gconv_stats wrote there, slots
+    of slot_px pixels): y = relu(batch_norm(y, training=True)), the batch statistics combined from stat_partial; running_mean /
+    running_var (momentum,
+    unbiased variance) and nbt (num_batches_tracked, += 1) updated in place.  Returns stats [4, C] = mean, invstd, scale, shift."""
+    _need_hip(y, gamma, beta, running_mean, running_var, nbt, stat_partial, stats)
+    if stat_partial.dim() != 3 or stat_partial.shape[2] != 2 or stat_partial.dtype != torch.float32 or not stat_partial.is_contiguous():
+        raise TgsrError("bn_train_relu_slice_from_stats: stat_partial %s" % (tuple(stat_partial.shape),))
+    C = stat_partial.shape[0]
+    if coff < 0 or coff + C > y.shape[1] or gamma.numel() != C or beta.numel() != C:
+        raise TgsrError("bn_train_relu_slice_from_stats: %d channels at %d of %s" % (C, coff, tuple(y.shape)))
+    for t in (running_mean, running_var):
+        if t is not None and (t.numel() != C or t.dtype != torch.float32 or not t.is_contiguous()):
+            raise TgsrError("bn_train_relu_slice_from_stats: running statistics of %d fp32 channels expected" % C)
+    if nbt is not None and nbt.dtype != torch.int64:
+        raise TgsrError("bn_train_relu_slice_from_stats: num_batches_tracked must be int64")
+    if stats is None:
+        stats = torch.empty(4, C, dtype=torch.float32, device=y.device)
+    elif tuple(stats.shape) != (4, C) or not stats.is_contiguous() or stats.dtype != torch.float32:
+        raise TgsrError("bn_train_relu_slice_from_stats: stats must be a dense fp32 [4, %d]" % C)
+    yp, ybs = _slice_ptr(y, coff)
+    check(_lib.lib().tgsr_bn_train_relu_slice_from_stats(yp, ybs, y.shape[0], C, y.shape[2] * y.shape[3], _p(_f32(gamma, "gamma").contiguous()),
+                                                         _p(_f32(beta, "beta").contiguous()), float(eps), float(momentum),
+                                                         _p(running_mean), _p(running_var), _p(stat_partial), stat_partial.shape[1],
+                                                         int(slot_px), _p(stats), _p(nbt), _stream()),
+          "tgsr_bn_train_relu_slice_from_stats")
+    return stats
+
+
 def sum_stack(stack: torch.Tensor, n: int, out: torch.Tensor):
     """out = ((stack[0] + stack[1]) + ...) + stack[n - 1]: the first n slices of a dense stack [N, ...] summed in order (tgsr_sum_stack)."""
     _need_hip(stack, out)

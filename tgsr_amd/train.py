@@ -785,20 +785,30 @@ class SRTrainer:
 class DAMSMTrainer:
     """pretrain_DAMSM.py:48-125, 262-284: joint training of RNN_ENCODER and the CNN_ENCODER heads on
     words_loss + sent_loss.  Every gradient comes from HIP kernels: DAMSM backward (tgsr_damsm_words_bwd), LSTM BPTT
-    (tgsr_bilstm_bwd) and the GEMMs of the heads; the Inception trunk is the caller's frozen module
-    (CNN_ENCODER(trunk=...)) or pre-extracted features via `step_features`.  Like the reference: a fresh
+    (tgsr_bilstm_bwd) and the GEMMs of the heads; the Inception trunk is the Inception blocks themselves (`inception=`: walked
+    in training mode on the library's kernels), the caller's frozen module (CNN_ENCODER(trunk=...)) or pre-extracted features
+    via `step_features`.  Like the reference: a fresh
     Adam(lr, betas (0.5, 0.999)) per epoch, lr x 0.98 per epoch down to ENCODER_LR / 10, gradient-norm clip
     RNN_GRAD_CLIP on the text encoder only.  Data parallel: one flat gradient bucket, one all-reduce per step; the
     contrastive losses are those of the GLOBAL batch (features and embeddings all-gathered, parallel.gather_damsm_batch;
     `gather_negatives=False` / TGSR_DP_GATHER_NEGATIVES=0: the local shard's negatives only - SURVEY section 8e (2))."""
 
-    def __init__(self, n_words, device="cuda", trunk=None, lr=None, gather_negatives=None):
+    def __init__(self, n_words, device="cuda", trunk=None, lr=None, gather_negatives=None, inception=None):
+        """`inception`: the Inception-v3 blocks (torchvision's attribute names, e.g. a loaded `models.inception_v3()`): `step(imgs,
+        ...)` then walks raw images through the frozen trunk in training mode on the library's kernels (batch-statistics
+        BatchNorm, running statistics drifting as in pretrain_DAMSM.py:49-51, 70) and `evaluate` in eval mode; `snapshot` saves
+        the drifted statistics with the heads.  Default: `trunk` (a callable images -> (features, pooled)), else nn.Identity."""
+        if trunk is not None and inception is not None:
+            raise ValueError("DAMSMTrainer: pass `trunk` or `inception`, not both")
         self.device = torch.device(device)
         from . import parallel as _par
         self.gather_negatives = _par.GATHER_NEGATIVES if gather_negatives is None else bool(gather_negatives)
         self.text_encoder = RNN_ENCODER(n_words, nhidden=cfg.TEXT.EMBEDDING_DIM).to(self.device).train()
-        self.image_encoder = CNN_ENCODER(cfg.TEXT.EMBEDDING_DIM,
-                                         trunk=trunk if trunk is not None else torch.nn.Identity()).to(self.device)
+        if inception is not None:
+            self.image_encoder = CNN_ENCODER(cfg.TEXT.EMBEDDING_DIM, inception=inception).to(self.device)
+        else:
+            self.image_encoder = CNN_ENCODER(cfg.TEXT.EMBEDDING_DIM,
+                                             trunk=trunk if trunk is not None else torch.nn.Identity()).to(self.device)
         self.image_encoder.train()
         for p in self.image_encoder.frozen_parameters():
             p.requires_grad = False                                  # util.py:274-275

@@ -512,6 +512,10 @@ class CNN_ENCODER(nn.Module):
             from .inception import InceptionTrunk, TrunkFn
             if self._hip_trunk is None:
                 self._hip_trunk = InceptionTrunk(self)
+            if self.training:
+                # training mode (pretrain_DAMSM.py:49-51, 70): batch-statistics BatchNorm, running statistics updated; no gradient to
+                # the image is wanted (_hip_trunk_ok), so no tape
+                return self._hip_trunk.forward(x, train=True)
             return TrunkFn.apply(x, self._hip_trunk)
         import torch.nn.functional as F
         x = F.interpolate(x, size=(299, 299), mode='bilinear', align_corners=False)   # nn.Upsample(size=(299, 299), 'bilinear')
@@ -529,11 +533,15 @@ class CNN_ENCODER(nn.Module):
     _hip_trunk = None
 
     def _hip_trunk_ok(self, x):
-        """The HIP walk serves the frozen trunk in eval mode on fp32 HIP images (TGSR_TRUNK=torch: the torch modules, e.g. on
-        MIOpen).  In training mode (pretrain_DAMSM.py:49-50 puts the whole encoder in train mode: the trunk's BatchNorm then
-        normalises with batch statistics) the blocks run as the torch modules they are."""
+        """The HIP walk serves the frozen trunk on fp32 HIP images (TGSR_TRUNK=torch: the torch modules, e.g. on MIOpen).  In
+        training mode (pretrain_DAMSM.py:49-50 puts the whole encoder in train mode: the trunk's BatchNorm then normalises with batch
+        statistics) it serves when no gradient to the image is wanted - what pre-training runs: frozen trunk, images without grad -
+        and every BatchNorm is affine with running statistics and a momentum; otherwise the blocks run as the torch modules they
+        are (no batch-statistics BatchNorm backward is built here)."""
         import os
-        if os.environ.get("TGSR_TRUNK", "hip") == "torch" or self.training or not (x.is_cuda and x.dtype == torch.float32):
+        if os.environ.get("TGSR_TRUNK", "hip") == "torch" or not (x.is_cuda and x.dtype == torch.float32):
+            return False
+        if self.training and torch.is_grad_enabled() and x.requires_grad:
             return False
         if self._hip_trunk is None:
             first = getattr(self, _INCEPTION_BLOCKS[0], None)
@@ -541,6 +549,11 @@ class CNN_ENCODER(nn.Module):
                 return False                                  # not torchvision's layout (e.g. a stub): walk the modules
             if any(p.requires_grad for p in self.frozen_parameters()):
                 return False
+        if self.training:
+            for name in _INCEPTION_BLOCKS:
+                for m in getattr(self, name).modules():
+                    if isinstance(m, nn.BatchNorm2d) and not (m.affine and m.track_running_stats and m.momentum is not None):
+                        return False
         return True
 
     def heads(self, features, pooled):
