@@ -35,6 +35,7 @@ extern "C" {
 /* Activation selectors for tgsr_conv_to3_fwd. */
 #define TGSR_ACT_NONE 0 /* y = conv                                  (GET_IMAGE_G_noAct, util.py:909-919) */
 #define TGSR_ACT_TANH_AXPY 1 /* y = tanh(conv) + alpha * addend      (conv_output + a*SRb, model.py:224,280) */
+#define TGSR_ACT_IDENT_AXPY 2 /* y = conv + alpha * addend           (useAct=False, model.py:226; tgsr_lp_conv_to3_map_fwd only) */
 
 /* ABI version of this header; tgsr_abi_version() must return the same number. */
 #define TGSR_ABI_VERSION 2
@@ -818,6 +819,19 @@ int tgsr_lp_head_combine(int nscales, int B, const int* H, const int* W, const f
                          float alpha, void* stream);
 
 /*
+ * tgsr_lp_head_combine for NetG_highweight's other three forms (model.py:212-298: weightmap x useAct):
+ *   high[s] = act(sum of partial_high[s]) + a[s] * low[s],   act = tanh (high_tanh != 0) or the identity (useAct=False,
+ *   model.py:226);  a[s] = amap[s][y][x] (weightmap=True: model.py:277, 286, 294, broadcast over batch and channels) or
+ *   alpha where amap == NULL or amap[s] == NULL.
+ * amap: HOST array of nscales device pointers (or NULL), each a dense fp32 [H[s]][W[s]] map, 16-byte aligned.  Every other
+ * argument and rule as tgsr_lp_head_combine; with amap == NULL and high_tanh = 1 the results are its results bit for bit.
+ * Replaces `one * conv_output(out_k) + a_k * SRb_k` with a_k a map (model.py:277-297) and the bare-conv heads of useAct=False.
+ */
+int tgsr_lp_head_combine_map(int nscales, int B, const int* H, const int* W, const float* const* partial_low,
+                             const float* const* partial_high, float* const* low, float* const* high,
+                             const float* const* amap, int low_tanh, int high_tanh, float alpha, void* stream);
+
+/*
  * The two 3-channel stems on the fp32 LR image: conv3x3 3 -> 2C + BatchNorm(eval) affine + GLU, written as C channels
  * of an lp image (im2f util.py:741-744, convin model.py:228).  x [B][3][H][W] fp32 dense, w [2C][3][3][3] fp32 (torch
  * layout, NOT rounded: 27 MACs per output run on the VALU), scale / shift [2C].  C % 8 == 0.
@@ -854,6 +868,17 @@ int tgsr_lp_upconv_glu_att_fwd(int dtype, const void* x, int x_cpitch, int B, in
 int tgsr_lp_pack_to3_weight(int dtype, const float* w, void* wpack, int Cin, int K, void* stream);
 int tgsr_lp_conv_to3_fwd(int dtype, const void* x, int x_cpitch, int B, int Cin, int H, int W, const void* wpack, int K,
                          int act, const float* addend, float alpha, float* out, void* stream);
+
+/*
+ * tgsr_lp_conv_to3_fwd for NetG_highweight's other forms (model.py:212-298: weightmap x useAct), the stand-alone head:
+ *   out = act(conv) + a * addend,  act = tanh (TGSR_ACT_TANH_AXPY) or the identity (TGSR_ACT_IDENT_AXPY, useAct=False,
+ *   model.py:226);  a = amap[y][x] (weightmap=True: model.py:277, 286, 294) or alpha when amap == NULL.
+ * amap: dense fp32 [H][W] (broadcast over batch and channels) or NULL; act = TGSR_ACT_NONE takes no map.  Every other
+ * argument and rule as tgsr_lp_conv_to3_fwd; with amap == NULL and act in {NONE, TANH_AXPY} the results are its results bit
+ * for bit.
+ */
+int tgsr_lp_conv_to3_map_fwd(int dtype, const void* x, int x_cpitch, int B, int Cin, int H, int W, const void* wpack, int K,
+                             int act, const float* addend, float alpha, const float* amap, float* out, void* stream);
 
 /*
  * GlobalAttentionGeneral.forward (GlobalAttention.py:87-130) on lp images: h = channels [0, idf) of an lp image,

@@ -14,7 +14,7 @@ ABI_VERSION = 2
 
 OK, EINVAL, EUNSUPPORTED, ELAUNCH = 0, -1, -2, -3
 EPI_AFFINE, EPI_AFFINE_GLU = 0, 1
-ACT_NONE, ACT_TANH_AXPY = 0, 1
+ACT_NONE, ACT_TANH_AXPY, ACT_IDENT_AXPY = 0, 1, 2
 DT_BF16, DT_F16 = 1, 2
 
 _vp, _i, _i64, _f, _d = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_float, ctypes.c_double
@@ -167,9 +167,11 @@ SIGNATURES = {
     "tgsr_lp_head_partial_elems": (_i64, [_i, _i, _i, _i]),
     "tgsr_lp_upconv_glu_head_fwd": (_i, [_i, _vp, _i, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _i, _i, _vp, _i, _vp, _vp]),
     "tgsr_lp_head_combine": (_i, [_i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _f, _vp]),
+    "tgsr_lp_head_combine_map": (_i, [_i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _f, _vp]),
     "tgsr_lp_stem_fwd": (_i, [_i, _vp, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _i, _i, _vp]),
     "tgsr_lp_pack_to3_weight": (_i, [_i, _vp, _vp, _i, _i, _vp]),
     "tgsr_lp_conv_to3_fwd": (_i, [_i, _vp, _i, _i, _i, _i, _i, _vp, _i, _i, _vp, _f, _vp, _vp]),
+    "tgsr_lp_conv_to3_map_fwd": (_i, [_i, _vp, _i, _i, _i, _i, _i, _vp, _i, _i, _vp, _f, _vp, _vp, _vp]),
     "tgsr_lp_word_attention_fwd": (_i, [_i, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _i, _i, _vp, _vp]),
 }
 

@@ -663,7 +663,11 @@ __device__ __forceinline__ void head_gather(const float* part, int b, int y, int
     }
 }
 
-__global__ __launch_bounds__(256) void lp_head_combine_kernel(LpCombineArgs a) {
+// The combine of one thread (4 pixels).  HIGH_TANH: tanh or identity on the high head's sum (useAct, model.py:223-226);
+// MAP: the low image is weighted by the per-scale map amap[s][y][x] instead of alpha (weightmap=True: model.py:277, 286,
+// 294), one float4 per thread beside the stores.  lp_head_combine_kernel is the shipped form <true, false>.
+template <bool HIGH_TANH, bool MAP>
+__device__ __forceinline__ void head_combine(const LpCombineArgs& a, const float* const* amap) {
   // thread = 4 consecutive pixels of a row (W % 64 == 0): 6 float4 stores instead of 24 scalar ones
   const int64_t i = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * 4;
   if (i >= a.total) return;
@@ -702,12 +706,26 @@ __global__ __launch_bounds__(256) void lp_head_combine_kernel(LpCombineArgs a) {
     float hi[4][3];
 #pragma unroll
     for (int p = 0; p < 4; ++p) head_gather<2>(sc.ph, b, y, x + p, sc.tiles_y, sc.tiles_x, hi[p]);
+    float4 w = make_float4(a.alpha, a.alpha, a.alpha, a.alpha);
+    if (MAP && amap[k]) w = *reinterpret_cast<const float4*>(amap[k] + (int64_t)y * sc.W + x);
+    auto act = [](float v) { return HIGH_TANH ? lp_fast_tanh(v) : v; };
 #pragma unroll
     for (int c = 0; c < 3; ++c)
       *reinterpret_cast<float4*>(sc.high + oi + c * HW) =
-          make_float4(lp_fast_tanh(hi[0][c]) + a.alpha * lo[0][c], lp_fast_tanh(hi[1][c]) + a.alpha * lo[1][c],
-                      lp_fast_tanh(hi[2][c]) + a.alpha * lo[2][c], lp_fast_tanh(hi[3][c]) + a.alpha * lo[3][c]);
+          make_float4(act(hi[0][c]) + w.x * lo[0][c], act(hi[1][c]) + w.y * lo[1][c], act(hi[2][c]) + w.z * lo[2][c],
+                      act(hi[3][c]) + w.w * lo[3][c]);
   }
+}
+
+__global__ __launch_bounds__(256) void lp_head_combine_kernel(LpCombineArgs a) { head_combine<true, false>(a, nullptr); }
+
+// the other NetG_highweight forms: tgsr_lp_head_combine_map
+struct LpCombineMaps {
+  const float* amap[4];    // [H][W] fp32 per scale, or null: alpha
+};
+template <bool HIGH_TANH, bool MAP>
+__global__ __launch_bounds__(256) void lp_head_combine_map_kernel(LpCombineArgs a, LpCombineMaps m) {
+  head_combine<HIGH_TANH, MAP>(a, m.amap);
 }
 
 // wpack[k16][column group 2][combo 8][cb 2][lane 64][8] <- pre-summed sub-pixel taps of w[64][Cin][3][3].
@@ -1056,11 +1074,11 @@ extern "C" int tgsr_lp_upconv_glu_att_fwd(int dtype, const void* x, int x_cpitch
                           head_partial ? head_wpack : nullptr, head_k, head_partial, stream, &f);
 }
 
-extern "C" int tgsr_lp_head_combine(int nscales, int B, const int* H, const int* W, const float* const* partial_low,
-                                    const float* const* partial_high, float* const* low, float* const* high, int low_tanh,
-                                    float alpha, void* stream) {
+static int lp_combine_args(int nscales, int B, const int* H, const int* W, const float* const* partial_low,
+                           const float* const* partial_high, float* const* low, float* const* high, int low_tanh, float alpha,
+                           LpCombineArgs* out) {
   if (nscales < 1 || nscales > 4 || B < 1 || !H || !W || !partial_low || !partial_high || !low || !high) return TGSR_EINVAL;
-  LpCombineArgs a;
+  LpCombineArgs& a = *out;
   a.nscales = nscales; a.B = B; a.low_tanh = low_tanh; a.alpha = alpha;
   int64_t total = 0;
   for (int k = 0; k < nscales; ++k) {
@@ -1074,8 +1092,39 @@ extern "C" int tgsr_lp_head_combine(int nscales, int B, const int* H, const int*
   for (int k = nscales; k < 4; ++k) a.s[k] = a.s[0];
   a.total = total;
   if (total >= (1ll << 31) * 256) return TGSR_EUNSUPPORTED;
-  hipLaunchKernelGGL(lp_head_combine_kernel, dim3((unsigned)((total / 4 + 255) / 256)), dim3(256), 0, as_stream(stream), a);
+  return TGSR_OK;
+}
+
+extern "C" int tgsr_lp_head_combine(int nscales, int B, const int* H, const int* W, const float* const* partial_low,
+                                    const float* const* partial_high, float* const* low, float* const* high, int low_tanh,
+                                    float alpha, void* stream) {
+  LpCombineArgs a;
+  const int rc = lp_combine_args(nscales, B, H, W, partial_low, partial_high, low, high, low_tanh, alpha, &a);
+  if (rc) return rc;
+  hipLaunchKernelGGL(lp_head_combine_kernel, dim3((unsigned)((a.total / 4 + 255) / 256)), dim3(256), 0, as_stream(stream), a);
   return note_launch(hipGetLastError(), "lp_head_combine_kernel");
+}
+
+extern "C" int tgsr_lp_head_combine_map(int nscales, int B, const int* H, const int* W, const float* const* partial_low,
+                                        const float* const* partial_high, float* const* low, float* const* high,
+                                        const float* const* amap, int low_tanh, int high_tanh, float alpha, void* stream) {
+  LpCombineArgs a;
+  const int rc = lp_combine_args(nscales, B, H, W, partial_low, partial_high, low, high, low_tanh, alpha, &a);
+  if (rc) return rc;
+  LpCombineMaps m;
+  bool any = false;
+  for (int k = 0; k < 4; ++k) {
+    m.amap[k] = (amap && k < nscales) ? amap[k] : nullptr;
+    if (reinterpret_cast<uintptr_t>(m.amap[k]) & 15) return TGSR_EUNSUPPORTED;
+    any = any || m.amap[k];
+  }
+  const dim3 grid((unsigned)((a.total / 4 + 255) / 256));
+  hipStream_t s = as_stream(stream);
+  if (high_tanh && any) hipLaunchKernelGGL((lp_head_combine_map_kernel<true, true>), grid, dim3(256), 0, s, a, m);
+  else if (high_tanh) hipLaunchKernelGGL((lp_head_combine_map_kernel<true, false>), grid, dim3(256), 0, s, a, m);
+  else if (any) hipLaunchKernelGGL((lp_head_combine_map_kernel<false, true>), grid, dim3(256), 0, s, a, m);
+  else hipLaunchKernelGGL((lp_head_combine_map_kernel<false, false>), grid, dim3(256), 0, s, a, m);
+  return note_launch(hipGetLastError(), "lp_head_combine_map_kernel");
 }
 
 extern "C" int tgsr_lp_from_nchw(int dtype, const float* x, void* out, int B, int C, int H, int W, int cpitch, int coff,

@@ -139,6 +139,7 @@ struct LpTo3Args {
   float alpha;
   float* out;            // [B][3][H][W] fp32
   int B, H, W, tiles_x, tiles_y;
+  const float* amap;     // MAP: [H][W] fp32 weight map multiplying the addend in place of alpha (NetG_highweight(weightmap=True))
 };
 
 // Workgroup = 4 waves = 8 rows x 32 columns of outputs; wave w owns rows 2w, 2w+1.
@@ -151,7 +152,9 @@ struct LpTo3Args {
 // Halo tile [(8 + K - 1) x 48 pixels][32 ch] by LDS-DMA, 16-byte slots swizzled by (column >> 1) & 3 (ds_read_b128 of 16
 // neighbouring pixels x 4 channel groups conflict free; checked by simulation).  Pixels further than one outside the
 // image (K = 5, or the tile's spare columns) are fetched from the image's top-left border pixel, zero by the layout rule.
-template <class T, int K, int ACT>
+// ACT: TGSR_ACT_NONE, TGSR_ACT_TANH_AXPY or TGSR_ACT_IDENT_AXPY (useAct=False heads, model.py:226); MAP: the addend is
+// multiplied by amap[y][x] instead of alpha (model.py:277, 286, 294).  The shipped heads are the MAP = false instantiations.
+template <class T, int K, int ACT, bool MAP = false>
 __global__ __launch_bounds__(256) void lp_to3_kernel(LpTo3Args a) {
   constexpr int P = K / 2, TR = 8 + 2 * P, TC = 48, NPIX = TR * TC, VP = 52;
   constexpr int TILE_SLOTS = NPIX * 4, TILE_INSTR = (TILE_SLOTS + 63) / 64;
@@ -227,7 +230,12 @@ __global__ __launch_bounds__(256) void lp_to3_kernel(LpTo3Args a) {
 #pragma unroll
       for (int dx = 0; dx < K; ++dx) o += v[(c * K + dx) * VP + x + dx];
       const int64_t oi = (((int64_t)b * 3 + c) * a.H + y) * a.W + x0 + x;
-      if (ACT == TGSR_ACT_TANH_AXPY) o = tanhf(o) + (a.addend ? a.alpha * a.addend[oi] : 0.f);
+      if (ACT == TGSR_ACT_TANH_AXPY && !MAP) {
+        o = tanhf(o) + (a.addend ? a.alpha * a.addend[oi] : 0.f);
+      } else if (ACT != TGSR_ACT_NONE) {
+        const float s = MAP ? a.amap[(int64_t)y * a.W + x0 + x] : a.alpha;
+        o = (ACT == TGSR_ACT_TANH_AXPY ? tanhf(o) : o) + (a.addend ? s * a.addend[oi] : 0.f);
+      }
       a.out[oi] = o;
     }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");          // the V image is rewritten for the next row
@@ -371,30 +379,51 @@ extern "C" int tgsr_lp_pack_to3_weight(int dtype, const float* w, void* wpack, i
   return note_launch(hipGetLastError(), "lp_pack_to3_kernel");
 }
 
+template <class T, int K>
+static void launch_to3_k(const LpTo3Args& a, int act, dim3 grid, hipStream_t s) {
+  const bool map = a.amap != nullptr;
+  if (act == TGSR_ACT_NONE) hipLaunchKernelGGL((lp_to3_kernel<T, K, TGSR_ACT_NONE>), grid, dim3(256), 0, s, a);
+  else if (act == TGSR_ACT_TANH_AXPY && !map) hipLaunchKernelGGL((lp_to3_kernel<T, K, TGSR_ACT_TANH_AXPY>), grid, dim3(256), 0, s, a);
+  else if (act == TGSR_ACT_TANH_AXPY) hipLaunchKernelGGL((lp_to3_kernel<T, K, TGSR_ACT_TANH_AXPY, true>), grid, dim3(256), 0, s, a);
+  else if (!map) hipLaunchKernelGGL((lp_to3_kernel<T, K, TGSR_ACT_IDENT_AXPY>), grid, dim3(256), 0, s, a);
+  else hipLaunchKernelGGL((lp_to3_kernel<T, K, TGSR_ACT_IDENT_AXPY, true>), grid, dim3(256), 0, s, a);
+}
+
 template <class T>
 static int launch_to3(const LpTo3Args& a, int K, int act, hipStream_t s) {
   const dim3 grid((unsigned)(a.B * a.tiles_x * a.tiles_y));
-  if (K == 3 && act == TGSR_ACT_NONE) hipLaunchKernelGGL((lp_to3_kernel<T, 3, TGSR_ACT_NONE>), grid, dim3(256), 0, s, a);
-  else if (K == 3) hipLaunchKernelGGL((lp_to3_kernel<T, 3, TGSR_ACT_TANH_AXPY>), grid, dim3(256), 0, s, a);
-  else if (act == TGSR_ACT_NONE) hipLaunchKernelGGL((lp_to3_kernel<T, 5, TGSR_ACT_NONE>), grid, dim3(256), 0, s, a);
-  else hipLaunchKernelGGL((lp_to3_kernel<T, 5, TGSR_ACT_TANH_AXPY>), grid, dim3(256), 0, s, a);
+  if (K == 3) launch_to3_k<T, 3>(a, act, grid, s);
+  else launch_to3_k<T, 5>(a, act, grid, s);
   return note_launch(hipGetLastError(), "lp_to3_kernel");
 }
 
-extern "C" int tgsr_lp_conv_to3_fwd(int dtype, const void* x, int x_cpitch, int B, int Cin, int H, int W, const void* wpack,
-                                    int K, int act, const float* addend, float alpha, float* out, void* stream) {
+static int lp_to3(int dtype, const void* x, int x_cpitch, int B, int Cin, int H, int W, const void* wpack, int K, int act,
+                  const float* addend, float alpha, const float* amap, float* out, void* stream) {
   if (!x || !wpack || !out || B < 1 || H < 1 || W < 1) return TGSR_EINVAL;
-  if (act != TGSR_ACT_NONE && act != TGSR_ACT_TANH_AXPY) return TGSR_EINVAL;
   if (Cin != 32 || (K != 3 && K != 5) || W % 32 != 0 || H % 8 != 0 || x_cpitch < 32 || x_cpitch % 8 != 0 ||
       (reinterpret_cast<uintptr_t>(x) & 15) || (reinterpret_cast<uintptr_t>(wpack) & 15))
     return TGSR_EUNSUPPORTED;
   LpTo3Args a;
   a.x = static_cast<const char*>(x); a.xcp = x_cpitch; a.wpack = static_cast<const char*>(wpack);
   a.addend = addend; a.alpha = alpha; a.out = out; a.B = B; a.H = H; a.W = W;
-  a.tiles_x = W / 32; a.tiles_y = H / 8;
+  a.tiles_x = W / 32; a.tiles_y = H / 8; a.amap = amap;
   if (dtype == TGSR_DT_BF16) return launch_to3<BF16>(a, K, act, as_stream(stream));
   if (dtype == TGSR_DT_F16) return launch_to3<F16>(a, K, act, as_stream(stream));
   return TGSR_EINVAL;
+}
+
+extern "C" int tgsr_lp_conv_to3_fwd(int dtype, const void* x, int x_cpitch, int B, int Cin, int H, int W, const void* wpack,
+                                    int K, int act, const float* addend, float alpha, float* out, void* stream) {
+  if (act != TGSR_ACT_NONE && act != TGSR_ACT_TANH_AXPY) return TGSR_EINVAL;
+  return lp_to3(dtype, x, x_cpitch, B, Cin, H, W, wpack, K, act, addend, alpha, nullptr, out, stream);
+}
+
+extern "C" int tgsr_lp_conv_to3_map_fwd(int dtype, const void* x, int x_cpitch, int B, int Cin, int H, int W,
+                                        const void* wpack, int K, int act, const float* addend, float alpha, const float* amap,
+                                        float* out, void* stream) {
+  if (act != TGSR_ACT_NONE && act != TGSR_ACT_TANH_AXPY && act != TGSR_ACT_IDENT_AXPY) return TGSR_EINVAL;
+  if (amap && act == TGSR_ACT_NONE) return TGSR_EINVAL;                  // a map multiplies the addend: no addend term, no map
+  return lp_to3(dtype, x, x_cpitch, B, Cin, H, W, wpack, K, act, addend, alpha, amap, out, stream);
 }
 
 extern "C" int tgsr_lp_word_attention_fwd(int dtype, const void* h, int h_cpitch, const float* src, const uint8_t* mask,

@@ -674,3 +674,26 @@ def _lp_head_combine(sizes_h, sizes_w, partial_low, partial_high, low, high, low
 
 lp_head_combine = _define("lp_head_combine(int[] H, int[] W, Tensor[] partial_low, Tensor[] partial_high, Tensor(a!)[] low, "
                           "Tensor(b!)[] high, bool low_tanh, float alpha) -> ()", _lp_head_combine, lambda *a: None)
+
+
+# NetG_highweight's other forms (weightmap x useAct, model.py:212-298): the weight map a_k in place of alpha, tanh or the identity
+lp_conv_to3_map = _define("lp_conv_to3_map(Tensor x, Tensor wpack, int K, bool tanh, Tensor? addend, float alpha, Tensor? amap) "
+                          "-> Tensor",
+                          lambda x, wp, K, th, add, alpha, amap: _lp().conv_to3_map(x, wp, K, tanh=th, addend=add, alpha=alpha,
+                                                                                    amap=amap),
+                          lambda x, wp, K, th, add, alpha, amap:
+                          x.new_empty(x.shape[0], 3, x.shape[1] - 2, x.shape[2] - 2, dtype=torch.float32))
+
+
+def _lp_head_combine_map(sizes_h, sizes_w, partial_low, partial_high, low, high, amap, low_tanh, high_tanh, alpha):
+    n = len(sizes_h)
+    none = lambda t: None if (t is None or t.numel() == 0) else t          # noqa: E731  (an empty tensor stands for "absent")
+    maps = [none(t) for t in amap[:n]] if len(amap) else None
+    _lp().head_combine(low[0].shape[0], list(zip(sizes_h, sizes_w)), [none(t) for t in partial_low[:n]],
+                       [none(t) for t in partial_high[:n]], list(low[:n]), [none(t) for t in high[:n]], low_tanh, alpha,
+                       amap=maps, high_tanh=high_tanh)
+
+
+lp_head_combine_map = _define("lp_head_combine_map(int[] H, int[] W, Tensor[] partial_low, Tensor[] partial_high, "
+                              "Tensor(a!)[] low, Tensor(b!)[] high, Tensor[] amap, bool low_tanh, bool high_tanh, float alpha) -> ()",
+                              _lp_head_combine_map, lambda *a: None)

@@ -267,6 +267,40 @@ def conv_to3(x: torch.Tensor, wpack: torch.Tensor, K: int, tanh_axpy: bool = Fal
     return out
 
 
+def _map(amap: Optional[torch.Tensor], H: int, W: int, what: str):
+    """A weight map [H, W] fp32 contiguous (NetG_highweight(weightmap=True)'s a_k), or None."""
+    if amap is None:
+        return None
+    if amap.dtype != torch.float32 or not amap.is_contiguous() or tuple(amap.shape) != (H, W):
+        raise TgsrError("%s: weight map %s %s, expected a contiguous float32 (%d, %d)" % (what, tuple(amap.shape), amap.dtype, H, W))
+    return amap
+
+
+def conv_to3_map(x: torch.Tensor, wpack: torch.Tensor, K: int, tanh: bool = True, addend: Optional[torch.Tensor] = None,
+                 alpha: float = 0.0, amap: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """tgsr_lp_conv_to3_map_fwd: act(KxK conv of channels [0,32) of an lp image) + a * addend -> fp32 NCHW, act = tanh or
+    the identity (NetG_highweight(useAct=False)), a = amap[y][x] (weightmap=True; [H, W] fp32) or alpha."""
+    _need_hip(x, wpack, addend, amap, out)
+    B, H, W, xcp = _img(x, "x")
+    amap = _map(amap, H, W, "lp.conv_to3_map")
+    if addend is not None:
+        addend = addend.contiguous()
+        if addend.dtype != torch.float32 or tuple(addend.shape) != (B, 3, H, W):
+            raise TgsrError("lp.conv_to3_map: addend %s" % (tuple(addend.shape),))
+    if out is None:
+        out = torch.empty(B, 3, H, W, dtype=torch.float32, device=x.device)
+    from . import ops
+    e0 = ops._ev() if ops.profile is not None else None
+    rc = _lib.lib().tgsr_lp_conv_to3_map_fwd(DT[x.dtype], _p(x), xcp, B, 32, H, W, _p(wpack), K,
+                                             _lib.ACT_TANH_AXPY if tanh else _lib.ACT_IDENT_AXPY, _p(addend), float(alpha),
+                                             _p(amap), _p(out), _stream())
+    check(rc, "tgsr_lp_conv_to3_map_fwd")
+    if ops.profile is not None:
+        nbytes = B * H * W * (2 * 32 + 4 * 3 * (2 if addend is not None else 1)) + (4 * H * W if amap is not None else 0)
+        ops.profile.append(("lp_to3_kernel", 2.0 * B * H * W * 3 * 32 * K * K, nbytes, e0, ops._ev()))
+    return out
+
+
 def word_attention(h_img: torch.Tensor, src: torch.Tensor, mask: Optional[torch.Tensor], T: int,
                    correct_mask: bool = False, c_coff: int = 32, attn: Optional[torch.Tensor] = None,
                    need_attn: bool = True):
@@ -405,12 +439,17 @@ def upconv_glu_head(x: torch.Tensor, wpack: torch.Tensor, cin: int, cout: int, s
     return out, partial
 
 
-def head_combine(B: int, sizes, partial_low, partial_high, low, high, low_tanh: bool, alpha: float):
+def head_combine(B: int, sizes, partial_low, partial_high, low, high, low_tanh: bool, alpha: float, amap=None,
+                 high_tanh: bool = True):
     """tgsr_lp_head_combine over len(sizes) <= 4 scales: sizes[s] = (H, W); partial_low / partial_high / low / high lists
-    (entries may be None as the header describes).  One launch."""
+    (entries may be None as the header describes).  One launch.  NetG_highweight's other forms (tgsr_lp_head_combine_map):
+    amap = a list of per-scale [H, W] fp32 weight maps (entries may be None: alpha) and / or high_tanh=False (useAct=False)."""
     n = len(sizes)
     ts = [t for lst in (partial_low, partial_high, low, high) for t in lst if t is not None]
-    _need_hip(*ts)
+    maps = None if amap is None else [_map(m, H, W, "lp.head_combine") for m, (H, W) in zip(amap, sizes)]
+    if maps is not None and len(maps) != n:
+        raise TgsrError("lp.head_combine: %d weight maps for %d scales" % (len(maps), n))
+    _need_hip(*ts, *(maps or ()))
     L = _lib.lib()
     for t in ts:
         if t.dtype != torch.float32 or not t.is_contiguous():
@@ -428,10 +467,16 @@ def head_combine(B: int, sizes, partial_low, partial_high, low, high, low_tanh: 
     ptr = lambda lst: arr_p(*[None if t is None else t.data_ptr() for t in lst])      # noqa: E731
     from . import ops
     e0 = ops._ev() if ops.profile is not None else None
-    rc = L.tgsr_lp_head_combine(n, B, arr_i(*[s[0] for s in sizes]), arr_i(*[s[1] for s in sizes]), ptr(partial_low),
-                                ptr(partial_high), ptr(low), ptr(high), 1 if low_tanh else 0, float(alpha), _stream())
-    check(rc, "tgsr_lp_head_combine")
+    if maps is None and high_tanh:
+        rc = L.tgsr_lp_head_combine(n, B, arr_i(*[s[0] for s in sizes]), arr_i(*[s[1] for s in sizes]), ptr(partial_low),
+                                    ptr(partial_high), ptr(low), ptr(high), 1 if low_tanh else 0, float(alpha), _stream())
+        check(rc, "tgsr_lp_head_combine")
+    else:
+        rc = L.tgsr_lp_head_combine_map(n, B, arr_i(*[s[0] for s in sizes]), arr_i(*[s[1] for s in sizes]), ptr(partial_low),
+                                        ptr(partial_high), ptr(low), ptr(high), None if maps is None else ptr(maps),
+                                        1 if low_tanh else 0, 1 if high_tanh else 0, float(alpha), _stream())
+        check(rc, "tgsr_lp_head_combine_map")
     if ops.profile is not None:
-        nbytes = 4 * sum(t.numel() for t in ts)
+        nbytes = 4 * sum(t.numel() for t in ts + [m for m in (maps or ()) if m is not None])
         ops.profile.append(("lp_head_combine_kernel", 0.0, nbytes, e0, ops._ev()))
     return low, high

@@ -43,6 +43,11 @@ FUSE_ATT = os.environ.get("TGSR_LP_FUSE_ATT", "1") != "0"
 # 32.0 k without; profiles/HISTORY.md 3.17).  OFF by default; TGSR_LP_CHAIN=1 switches it on (the tests do).
 CHAIN = os.environ.get("TGSR_LP_CHAIN", "0") == "1"
 CHAIN_MAX_PIXELS = 64 * 64
+# the x16 weight-map form fixes its LR at 16 x 16 (maps of 32..256 pixels, models16.py:120-123); the lp kernels need image
+# widths that are multiples of 32 from the LR on (include/tgsr_hip.h: "every layer ... at LR >= 32")
+X16_WEIGHTMAP_REFUSAL = ("the reduced-precision path does not build the x16 NetG_highweight(weightmap=True): its maps "
+                         "(32..256 pixels, models16.py:120-123) fix the LR at 16 x 16, below the 32-pixel width every lp kernel "
+                         "needs; use dtype='fp32' for that form")
 
 
 def trunk_dtype_of(dtype):
@@ -135,9 +140,8 @@ class LpExecutor:
         dt, GL, GH = self.dtype, self.netGL, self.netGH
         if GL.training or GH.training:
             raise RuntimeError("the reduced-precision path is inference only: call .eval() on the generators")
-        if getattr(GH, "weightmap", False) or not getattr(GH, "useAct", True):
-            raise NotImplementedError("the reduced-precision path builds NetG_highweight's shipped heads (weightmap=False, "
-                                      "useAct=True: trainer_objective.py:58, 88); the fp32 path runs the other two forms")
+        if getattr(GH, "weightmap", False) and hasattr(GL, "h_net4"):
+            raise ValueError(X16_WEIGHTMAP_REFUSAL)
 
         def res(rb, dt=dt):
             return (_Conv(rb.block[0], rb.block[1], dt), _Conv(rb.block[3], rb.block[4], dt))
@@ -170,6 +174,10 @@ class LpExecutor:
         self.gh_up = [once(u, lambda m: _UpConv(m[1], m[2], dt)) for u in ups]
         self.gh_mid = [once(m_, lambda m: (_Conv(m[0], m[1], dt), _Conv(m[3], m[4], dt))) for m_ in mids]
         self.gh_head = lp.pack_to3_weight(GH.conv_output[0].weight, dt)
+        # NetG_highweight's form (model.py:212-298): tanh or bare conv5x5 heads, the scalar `a` or the maps a1..a3.  The maps
+        # are NOT captured here: high_heads reads the parameters at every call (an in-place update reaches the next step)
+        self.gh_tanh = bool(getattr(GH, "useAct", True))
+        self.gh_weightmap = bool(getattr(GH, "weightmap", False))
         self.key = key
 
     # ------------------------------------------------------------------ activation buffers
@@ -309,23 +317,39 @@ class LpExecutor:
         return feats
 
     def high_heads(self, feats, SRb, pend=None):
-        """NetG_highweight's heads: `tanh(conv5x5(out_k)) + a * SRb_k`.  Scales whose heads were computed inside their
-        upBlocks (partial sums) are finished here by one combine launch - together with the low-frequency images `SRb`
-        whose partial sums `low(..., defer_heads=True)` handed back as `pend` (pend[k] is None / pend is None: SRb[k] is a
-        finished image)."""
-        alpha = self.netGH.alpha() if self.x16 else self.netGH._a      # x16: `a` is a parameter (models16.py:126)
+        """NetG_highweight's heads: `act(conv5x5(out_k)) + a_k * SRb_k` (act = tanh, or the identity for useAct=False;
+        a_k = the scalar `a`, or the map a1..a3 for weightmap=True, model.py:264-298).  Scales whose heads were computed
+        inside their upBlocks (partial sums) are finished here by one combine launch - together with the low-frequency
+        images `SRb` whose partial sums `low(..., defer_heads=True)` handed back as `pend` (pend[k] is None / pend is None:
+        SRb[k] is a finished image)."""
+        GH = self.netGH
+        alpha = 0.0 if self.gh_weightmap else (GH.alpha() if self.x16 else GH._a)   # x16: `a` is a parameter (models16.py:126)
+        maps = None
+        if self.gh_weightmap:
+            maps = []
+            for k, (amap, sr) in enumerate(zip(GH.maps(), SRb)):
+                if tuple(amap.shape) != tuple(sr.shape[2:]):          # the fp32 module's refusal (model.NetG_highweight._head)
+                    raise ValueError("NetG_highweight(weightmap=True): a%d is %s but scale %d of this input is %s (the maps are "
+                                     "sized for 32 x 32 inputs, model.py:236-239)" % (k + 1, tuple(amap.shape), k,
+                                                                                    tuple(sr.shape[2:])))
+                maps.append(amap.detach())
+        shipped = maps is None and self.gh_tanh
         pend = [None] * len(SRb) if pend is None else list(pend)
         if len(pend) != len(SRb):
             raise ValueError("high_heads: %d pending entries for %d low-frequency images" % (len(pend), len(SRb)))
-        fine, sizes, pl, ph, lo, hi = [], [], [], [], [], []
+        fine, sizes, pl, ph, lo, hi, mp = [], [], [], [], [], [], []
         for k, (f, sr) in enumerate(zip(feats, SRb)):
             fused_h = isinstance(f, _Partial)
             pk = pend[k]
+            amap = None if maps is None else maps[k]
             if not fused_h:
                 if pk is not None:          # the low image must exist before an unfused 5x5 head can add it: combine it alone
                     _combine([tuple(sr.shape[2:])], [pk], [None], [sr], [None], self.gl_head_tanh, alpha)
                     pk = None
-                fine.append(C.lp_conv_to3(f, self.gh_head, 5, True, sr, float(alpha)))
+                if shipped:
+                    fine.append(C.lp_conv_to3(f, self.gh_head, 5, True, sr, float(alpha)))
+                else:
+                    fine.append(C.lp_conv_to3_map(f, self.gh_head, 5, self.gh_tanh, sr, float(alpha), amap))
             else:
                 fine.append(torch.empty(f.B, 3, f.H, f.W, dtype=torch.float32, device=sr.device))
             if fused_h or pk is not None:
@@ -334,17 +358,23 @@ class LpExecutor:
                 ph.append(f.t if fused_h else None)
                 lo.append(sr)
                 hi.append(fine[-1] if fused_h else None)
+                mp.append(amap)
         if sizes:
-            _combine(sizes, pl, ph, lo, hi, self.gl_head_tanh, alpha)
+            _combine(sizes, pl, ph, lo, hi, self.gl_head_tanh, alpha, None if maps is None else mp, self.gh_tanh)
         return fine
 
 
-def _combine(sizes, pl, ph, lo, hi, low_tanh, alpha):
-    """torch.ops.tgsr.lp_head_combine (tensor lists cannot hold None: an empty tensor stands for an absent entry)."""
+def _combine(sizes, pl, ph, lo, hi, low_tanh, alpha, maps=None, high_tanh=True):
+    """torch.ops.tgsr.lp_head_combine (tensor lists cannot hold None: an empty tensor stands for an absent entry); the
+    shipped heads (no maps, tanh) through it, NetG_highweight's other forms through lp_head_combine_map."""
     e = lo[0].new_empty(0)
-    C.lp_head_combine([s[0] for s in sizes], [s[1] for s in sizes], [e if t is None else t for t in pl],
-                      [e if t is None else t for t in ph], list(lo), [e if t is None else t for t in hi], bool(low_tanh),
-                      float(alpha))
+    opt = lambda lst: [e if t is None else t for t in lst]       # noqa: E731
+    if maps is None and high_tanh:
+        C.lp_head_combine([s[0] for s in sizes], [s[1] for s in sizes], opt(pl), opt(ph), list(lo), opt(hi), bool(low_tanh),
+                          float(alpha))
+    else:
+        C.lp_head_combine_map([s[0] for s in sizes], [s[1] for s in sizes], opt(pl), opt(ph), list(lo), opt(hi),
+                              [] if maps is None else opt(maps), bool(low_tanh), bool(high_tanh), float(alpha))
 
 
 class _Partial:

@@ -46,7 +46,7 @@ GRAPH_G_SETTLED = GRAPH_G_WARMUP + 2 * GRAPH_G_TRIALS + 1
 
 class SRTrainer:
     def __init__(self, n_words, device="cuda", low="lr", lr=None, ema_decay=0.999, image_encoder=None,
-                 discriminators=False, d_lr=None, gather_negatives=None):
+                 discriminators=False, d_lr=None, gather_negatives=None, weightmap=False, use_act=True):
         """image_encoder: optional frozen module image [B,3,256,256] -> (region features [B,nef,17,17], cnn_code
         [B,nef]) (a CNN_ENCODER with its trunk): adds the DAMSM ranking term of generator_loss (losses.py:375-386)
         on the finest image, x TRAIN.SMOOTH.LAMBDA.
@@ -56,7 +56,10 @@ class SRTrainer:
         (generator_loss :351-391 + MSE + KL), each discriminator with its own Adam(DISCRIMINATOR_LR, betas (0.5, 0.999))
         and flat gradient bucket.  The reference defines the two loss functions but neither the discriminators nor the
         loop: architecture and update order (D first, then G on the same fake images, as in the AttnGAN
-        trainer TGSR was forked from) are the build's declaration."""
+        trainer TGSR was forked from) are the build's declaration.
+        weightmap / use_act: NetG_highweight's form (model.py:212-298).  weightmap=True trains the maps a1..a3 (64 / 128 /
+        256 pixels: 32 x 32 LR) with the other generator parameters (flat gradient bucket, Adam, EMA); use_act=False drops
+        the heads' Tanh."""
         self.device = torch.device(device)
         # data parallel: the DAMSM ranking term on the gathered global batch (parallel.GATHER_NEGATIVES, default on) or per shard
         from . import parallel as _par
@@ -75,7 +78,7 @@ class SRTrainer:
         for p in self.text_encoder.parameters():
             p.requires_grad = False
         self.netGL = G_SR_NET_low().to(self.device).train()
-        self.netGH = NetG_highweight(weightmap=False, low=low).to(self.device).train()
+        self.netGH = NetG_highweight(weightmap=bool(weightmap), low=low, useAct=bool(use_act)).to(self.device).train()
         self.params = list(self.netGL.parameters()) + list(self.netGH.parameters())
         # (BatchNorm's running statistics ride the gradient bucket's all-reduce: identical on every rank, parallel.py.)
         # Bucket layout [NetG_highweight | G_SR_NET_low | buffers]: backward runs through NetG_highweight first (its nodes

@@ -97,21 +97,35 @@ class SRPipeline:
     """The three networks of the SR path, built like trainer_objective.py:62-99: TREE.BRANCH_NUM == 4 selects the x8
     generators of model.py, anything else the x16 ones of models16.py (trainer_objective.py:74-87)."""
 
-    def __init__(self, n_words, device="cuda", low="lr", overlap=True, dtype="fp32", branch_num=None):
+    def __init__(self, n_words, device="cuda", low="lr", overlap=True, dtype="fp32", branch_num=None, weightmap=False,
+                 use_act=True):
         """dtype: "fp32" (the parity path: fp32 NCHW kernels) or "bf16" / "f16" (BASELINE configs[4]: the two generators
         run on reduced-precision channels-last images through tgsr_amd.lp_pipeline.LpExecutor; inputs, the text encoder
         and every returned tensor stay fp32).  branch_num: None = cfg.TREE.BRANCH_NUM, read at construction like the
-        reference does."""
+        reference does.
+        weightmap / use_act: NetG_highweight's form (model.py:212-298; the reference's switch, trainer_objective.py:58, 88).
+        weightmap=True: trainable per-scale maps a1..a3 (x8: 64 / 128 / 256 pixels, for 32 x 32 LR) or a1..a4 (x16: 32..256
+        pixels, for 16 x 16 LR) in place of the scalar `a`; use_act=False (x8 only, models16 has no such form): the heads are
+        the bare conv5x5, no Tanh.  fp32 runs every form; bf16 / f16 every x8 form, not the x16 weight-map one (its 16 x 16
+        LR is below the 32-pixel width of the lp kernels)."""
         self.dtype = dtype
         self._lp = None
         self.branch_num = int(cfg.TREE.BRANCH_NUM if branch_num is None else branch_num)
+        lp_dtype = dtype not in ("fp32", "f32", None)
+        if self.branch_num != 4 and not use_act:
+            raise ValueError("SRPipeline(use_act=False): the x16 NetG_highweight (models16.py:97-179) has no tanh-free form")
+        if self.branch_num != 4 and weightmap and lp_dtype:
+            from .lp_pipeline import X16_WEIGHTMAP_REFUSAL
+            raise ValueError(X16_WEIGHTMAP_REFUSAL)
         if self.branch_num == 4:                                        # trainer_objective.py:74-87
             from .model import G_SR_NET_low, NetG_highweight
+            gh_kw = {"useAct": bool(use_act)}
         else:
             from .models16 import G_SR_NET_low, NetG_highweight
+            gh_kw = {}
         self.text_encoder = RNN_ENCODER(n_words, nhidden=cfg.TEXT.EMBEDDING_DIM)
         self.netGL = G_SR_NET_low()
-        self.netGH = NetG_highweight(weightmap=False, low=low)
+        self.netGH = NetG_highweight(weightmap=bool(weightmap), low=low, **gh_kw)
         self.device = torch.device(device)
         # NetG_highweight's trunk does not depend on G_SR_NET_low (only its three heads add the low-frequency
         # images): run it on a second HIP stream so the two networks' small layers and kernel tails overlap
@@ -120,13 +134,14 @@ class SRPipeline:
         for m in (self.text_encoder, self.netGL, self.netGH):
             m.to(self.device)
             m.eval()
-        if dtype not in ("fp32", "f32", None):
+        if lp_dtype:
             from .lp_pipeline import LpExecutor
             self._lp = LpExecutor(self.netGL, self.netGH, dtype)
 
     def load_state_dicts(self, sd_E=None, sd_GL=None, sd_GH=None):
         """strict for E and GL; the x8 GH tolerates only a missing `a` (never saved by the reference, model.py:246-248);
-        the x16 GH registers `a` as a parameter (models16.py:126) and loads it."""
+        the x16 GH registers `a` as a parameter (models16.py:126) and loads it.  The weight-map forms load their maps
+        a1..a3 (x8) / a1..a4 (x16) strictly."""
         if sd_E is not None:
             self.text_encoder.load_state_dict(sd_E, strict=True)
         if sd_GL is not None:
