@@ -62,7 +62,7 @@ def test_two_rank_gradients_and_sharded_inference(tmp_path, backend):
 
     cap, lens, LR, LRb, _ = batch
     full = pipe(cap.cuda(), lens.tolist(), LR.cuda(), LRb.cuda())["fine"][2].cpu()
-    # not bitwise: the kernel selection depends on the local batch (Winograd vs direct below 256 workgroups, util._wino_pays)
+    # not bitwise: the kernel selection depends on the local batch (Winograd vs direct below 256 workgroups, ops.conv3x3_form)
     # and the shard's T_max may be shorter; the stated fp32 tolerance of the path applies
     for k in range(2):
         assert torch.allclose(full[r[k]["lo"]:r[k]["hi"]], r[k]["fine"], atol=1e-4, rtol=1e-4), \

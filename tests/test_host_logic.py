@@ -303,3 +303,474 @@ def test_bench_dump_outputs_names_dtype_and_size_cap(tmp_path):
     a1, a2 = np.load(tmp_path / "s1" / "a.npy"), np.load(tmp_path / "s2" / "a.npy")
     assert np.array_equal(a1, a2) and a1.nbytes + np.load(tmp_path / "s1" / "b.npy").nbytes <= 4000
     assert np.isin(a1, big["a"]).all() and a1.size == int(4000 * 0.99 * 4000 / 20000)
+
+
+# ---- routing: the form every conv3x3 decision site chose before ops.conv3x3_form existed, recorded case by case
+class _Addr:
+    """What the router looks at of a tensor: shape, strides, address (a dense NCHW block at `addr`)."""
+
+    def __init__(self, B, C, H, W, addr):
+        self.shape, self._strides, self._addr = (B, C, H, W), (C * H * W, H * W, W, 1), addr
+
+    def dim(self):
+        return 4
+
+    def stride(self, i=None):
+        return self._strides if i is None else self._strides[i]
+
+    def data_ptr(self):
+        return self._addr
+
+
+# (Cin, Cout, H, W) of every conv3x3 the shipped x8 and x16 generators run, eval forward and train step (forward, data gradient),
+# and one layer with an odd number of 4-channel stages: none of the shipped ones has, and only such a layer takes the LDS-fed F(4x4)
+_ROUTE_SHAPES = [(3, 64, 32, 32), (32, 32, 32, 32), (32, 32, 64, 64), (32, 32, 128, 128), (32, 32, 256, 256), (32, 64, 32, 32),
+                 (32, 64, 64, 64), (32, 64, 128, 128), (32, 64, 256, 256), (64, 32, 32, 32), (64, 32, 64, 64), (64, 32, 128, 128),
+                 (64, 32, 256, 256), (64, 64, 32, 32), (64, 64, 64, 64), (64, 64, 128, 128), (64, 64, 256, 256), (64, 128, 32, 32),
+                 (64, 128, 64, 64), (64, 128, 128, 128), (64, 128, 256, 256), (128, 64, 32, 32), (128, 64, 64, 64), (128, 64, 128, 128),
+                 (12, 64, 128, 128)]
+_ROUTE_BATCHES = (1, 2, 4, 16, 64)
+# name -> (environment of ops._Routing, util.WINOGRAD, autograd.BN_STATS_IN_CONV)
+_ROUTE_ENVS = {"default": ({}, True, True), "TGSR_WINOGRAD=0": ({}, False, True), "TGSR_WINO4=0": ({"TGSR_WINO4": "0"}, True, True),
+               "TGSR_WINO4_PIN_BATCH=16": ({"TGSR_WINO4_PIN_BATCH": "16"}, True, True),
+               "TGSR_BN_STATS_IN_CONV=0": ({}, True, False)}
+# one letter per case: the form; for the training forward with BatchNorm, a digit where the statistics ride the form's epilogue
+_ROUTE_CODE = {"direct": "d", "wino": "w", "wino4": "q", "wino4w": "Q", "upconv": "s", "upwino": "u", "upwino4": "U",
+               "wino+stats": "1", "wino4+stats": "2", "wino4w+stats": "3"}
+
+
+def _route_cases(site, shape):
+    """The cases of one decision site and layer shape, in the order of its string in _ROUTE_TABLE:
+    (environment name, x, upsample, glu, out, residual).  Sites: "eval" (util._conv_bn; upBlocks: util._UpBlock.forward), "raw"
+    (autograd._conv_raw: training forward without BatchNorm and the data gradient), "cba" (autograd._cba_forward).  Every
+    environment at every batch with aligned tensors; in the default environment also each tensor in turn 4 and 8 bytes off."""
+    cin, cout, H, W = shape
+    for env in _ROUTE_ENVS:
+        if env == "TGSR_BN_STATS_IN_CONV=0" and site != "cba":
+            continue
+        for B in _ROUTE_BATCHES:
+            for upsample in (False, True):
+                m = 2 if upsample else 1
+                for glu in ((False, True) if site == "eval" else (False,)):
+                    co = cout // 2 if glu else cout
+                    # an upBlock has no residual; the training sites have no `out`, and BatchNorm takes _cba_forward's residual
+                    for has_out, has_res in ((False, False), (True, False), (False, True), (True, True)):
+                        if (has_out and site != "eval") or (has_res and (upsample or site == "cba")):
+                            continue
+                        present = ["x"] + ["out"] * has_out + ["res"] * has_res
+                        offs = [None] + ([(t, o) for t in present for o in (4, 8)] if env == "default" else [])
+                        for off in offs:
+                            a = {t: 4096 * (i + 1) + (off[1] if off and off[0] == t else 0) for i, t in enumerate(present)}
+                            yield (env, _Addr(B, cin, H, W, a["x"]), upsample, glu,
+                                   _Addr(B, co, m * H, m * W, a["out"]) if has_out else None,
+                                   _Addr(B, co, m * H, m * W, a["res"]) if has_res else None)
+
+
+_ROUTE_TABLE = {
+    "eval 3,64,32x32":
+        "ddddddddddddddddddddddddddddddddddddddddddddddddssssssssddddddddddddddddddddddddddddddddddddddddddddddddssssssssdddddddd"
+        "ddddddddddddddddddddddddddddddddddddddddssssssssddddddddddddddddddddddddddddddddddddddddddddddddssssssssdddddddddddddddd"
+        "ddddddddddddddddddddddddddddddddssssssssddddddddddssddddddddddssddddddddddssddddddddddssddddddddddssddddddddddssdddddddd"
+        "ddssddddddddddssddddddddddssddddddddddssddddddddddssddddddddddssddddddddddssddddddddddssddddddddddss",
+    "eval 32,32,32x32":
+        "dddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddd"
+        "ddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddwddwdddwwdddwwdd"
+        "dwdwwddwdddwwdddwwdddwdwdddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddd"
+        "ddddddddddddddddddddddddddddwwwwwwwwddddddddddddddddddddddddddddddddddddddddddddddddddddwwwwwwwwdddd",
+    "eval 32,32,64x64":
+        "dddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddd"
+        "ddddddddddddddddddddddddddddddddddddddddddddddddwddwdddwwdddwwdddwdwwddwdddwwdddwwdddwdwddddddddddddddddwddwdddwwdddwwdd"
+        "dwdwwddwdddwwdddwwdddwdwdddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddd"
+        "ddddddddddddddddwwwwwwwwddddwwwwwwwwddddddddddddddddddddddddddddddddddddddddwwwwwwwwddddwwwwwwwwdddd",
+    "eval 32,32,128x128":
+        "ddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddwddwdddw"
+        "wdddwwdddwdwwddwdddwwdddwwdddwdwddddddddddddddddwddwdddwwdddwwdddwdwwddwdddwwdddwwdddwdwddddddddddddddddwddwdddwwdddwwdd"
+        "dwdwwddwdddwwdddwwdddwdwdddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddd"
+        "ddddwwwwwwwwddddwwwwwwwwddddwwwwwwwwddddddddddddddddddddddddddddwwwwwwwwddddwwwwwwwwddddwwwwwwwwdddd",
+    "eval 32,32,256x256":
+        "wddwdddwwdddwwdddwdwwddwdddwwdddwwdddwdwddddddddddddddddwddwdddwwdddwwdddwdwwddwdddwwdddwwdddwdwddddddddddddddddwddwdddw"
+        "wdddwwdddwdwwddwdddwwdddwwdddwdwddddddddddddddddwddwdddwwdddwwdddwdwwddwdddwwdddwwdddwdwddddddddddddddddwddwdddwwdddwwdd"
+        "dwdwwddwdddwwdddwwdddwdwddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddwwwwwwwwddddwwwwwwww"
+        "ddddwwwwwwwwddddwwwwwwwwddddwwwwwwwwddddwwwwwwwwddddwwwwwwwwddddwwwwwwwwddddwwwwwwwwddddwwwwwwwwdddd",
+    "eval 32,64,32x32":
+        "wddwdddwwdddwwdddwdwwddwdddwwdddwwdddwdwddddddddussusssuwddwdddwwdddwwdddwdwwddwdddwwdddwwdddwdwddddddddussusssuwddwdddw"
+        "wdddwwdddwdwwddwdddwwdddwwdddwdwddddddddussusssuwddwdddwwdddwwdddwdwwddwdddwwdddwwdddwdwddddddddussusssuwddwdddwwdddwwdd"
+        "dwdwwddwdddwwdddwwdddwdwddddddddussusssuddddddddddssddddddddddssddddddddddssddddddddddssddddddddddsswwwwwwwwdduuwwwwwwww"
+        "dduuwwwwwwwwdduuwwwwwwwwdduuwwwwwwwwdduuwwwwwwwwdduuwwwwwwwwdduuwwwwwwwwdduuwwwwwwwwdduuwwwwwwwwdduu",
+    "eval 32,64,64x64":
+        "wddwdddwwdddwwdddwdwwddwdddwwdddwwdddwdwddddddddussusssuwddwdddwwdddwwdddwdwwddwdddwwdddwwdddwdwddddddddussusssuwddwdddw"
+        "wdddwwdddwdwwddwdddwwdddwwdddwdwddddddddussusssuwddwdddwwdddwwdddwdwwddwdddwwdddwwdddwdwddddddddussusssuwddwdddwwdddwwdd"
+        "dwdwwddwdddwwdddwwdddwdwddddddddussusssuddddddddddssddddddddddssddddddddddssddddddddddssddddddddddsswwwwwwwwdduuwwwwwwww"
+        "dduuwwwwwwwwdduuwwwwwwwwdduuwwwwwwwwdduuwwwwwwwwdduuwwwwwwwwdduuwwwwwwwwdduuwwwwwwwwdduuwwwwwwwwdduu",
+    "eval 32,64,128x128":
+        "wddwdddwwdddwwdddwdwwddwdddwwdddwwdddwdwddddddddUssUsssuwddwdddwwdddwwdddwdwwddwdddwwdddwwdddwdwddddddddUssUsssuQddQdddw"
+        "QdddwQdddwdwQddQdddwQdddwQdddwdwddddddddUssUsssuQddQdddwQdddwQdddwdwQddQdddwQdddwQdddwdwddddddddUssUsssuQddQdddwQdddwQdd"
+        "dwdwQddQdddwQdddwQdddwdwddddddddUssUsssuddddddddddssddddddddddssddddddddddssddddddddddssddddddddddsswwwwwwwwdduuwwwwwwww"
+        "dduuwwwwwwwwdduuwwwwwwwwdduuwwwwwwwwdduuQQQQQQQQddUUQQQQQQQQddUUQQQQQQQQddUUQQQQQQQQddUUQQQQQQQQddUU",
+    "eval 32,64,256x256":
+        "QddQdddwQdddwQdddwdwQddQdddwQdddwQdddwdwddddddddUssUsssuQddQdddwQdddwQdddwdwQddQdddwQdddwQdddwdwddddddddUssUsssuQddQdddw"
+        "QdddwQdddwdwQddQdddwQdddwQdddwdwddddddddUssUsssuQddQdddwQdddwQdddwdwQddQdddwQdddwQdddwdwddddddddUssUsssuQddQdddwQdddwQdd"
+        "dwdwQddQdddwQdddwQdddwdwddddddddUssUsssuddddddddddssddddddddddssddddddddddssddddddddddssddddddddddsswwwwwwwwdduuwwwwwwww"
+        "dduuwwwwwwwwdduuwwwwwwwwdduuwwwwwwwwdduuQQQQQQQQddUUQQQQQQQQddUUQQQQQQQQddUUQQQQQQQQddUUQQQQQQQQddUU",
+    "eval 64,32,32x32":
+        "dddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddd"
+        "ddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddwddwdddwwdddwwdd"
+        "dwdwwddwdddwwdddwwdddwdwdddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddd"
+        "ddddddddddddddddddddddddddddwwwwwwwwddddddddddddddddddddddddddddddddddddddddddddddddddddwwwwwwwwdddd",
+    "eval 64,32,64x64":
+        "dddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddd"
+        "ddddddddddddddddddddddddddddddddddddddddddddddddwddwdddwwdddwwdddwdwwddwdddwwdddwwdddwdwddddddddddddddddwddwdddwwdddwwdd"
+        "dwdwwddwdddwwdddwwdddwdwdddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddd"
+        "ddddddddddddddddwwwwwwwwddddwwwwwwwwddddddddddddddddddddddddddddddddddddddddwwwwwwwwddddwwwwwwwwdddd",
+    "eval 64,32,128x128":
+        "ddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddwddwdddw"
+        "wdddwwdddwdwwddwdddwwdddwwdddwdwddddddddddddddddwddwdddwwdddwwdddwdwwddwdddwwdddwwdddwdwddddddddddddddddwddwdddwwdddwwdd"
+        "dwdwwddwdddwwdddwwdddwdwdddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddd"
+        "ddddwwwwwwwwddddwwwwwwwwddddwwwwwwwwddddddddddddddddddddddddddddwwwwwwwwddddwwwwwwwwddddwwwwwwwwdddd",
+    "eval 64,32,256x256":
+        "wddwdddwwdddwwdddwdwwddwdddwwdddwwdddwdwddddddddddddddddwddwdddwwdddwwdddwdwwddwdddwwdddwwdddwdwddddddddddddddddwddwdddw"
+        "wdddwwdddwdwwddwdddwwdddwwdddwdwddddddddddddddddwddwdddwwdddwwdddwdwwddwdddwwdddwwdddwdwddddddddddddddddwddwdddwwdddwwdd"
+        "dwdwwddwdddwwdddwwdddwdwddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddwwwwwwwwddddwwwwwwww"
+        "ddddwwwwwwwwddddwwwwwwwwddddwwwwwwwwddddwwwwwwwwddddwwwwwwwwddddwwwwwwwwddddwwwwwwwwddddwwwwwwwwdddd",
+    "eval 64,64,32x32":
+        "wddwdddwwdddwwdddwdwwddwdddwwdddwwdddwdwddddddddussusssuwddwdddwwdddwwdddwdwwddwdddwwdddwwdddwdwddddddddussusssuwddwdddw"
+        "wdddwwdddwdwwddwdddwwdddwwdddwdwddddddddussusssuwddwdddwwdddwwdddwdwwddwdddwwdddwwdddwdwddddddddussusssuwddwdddwwdddwwdd"
+        "dwdwwddwdddwwdddwwdddwdwddddddddussusssuddddddddddssddddddddddssddddddddddssddddddddddssddddddddddsswwwwwwwwdduuwwwwwwww"
+        "dduuwwwwwwwwdduuwwwwwwwwdduuwwwwwwwwdduuwwwwwwwwdduuwwwwwwwwdduuwwwwwwwwdduuwwwwwwwwdduuwwwwwwwwdduu",
+    "eval 64,64,64x64":
+        "wddwdddwwdddwwdddwdwwddwdddwwdddwwdddwdwddddddddussusssuwddwdddwwdddwwdddwdwwddwdddwwdddwwdddwdwddddddddussusssuwddwdddw"
+        "wdddwwdddwdwwddwdddwwdddwwdddwdwddddddddussusssuwddwdddwwdddwwdddwdwwddwdddwwdddwwdddwdwddddddddussusssuwddwdddwwdddwwdd"
+        "dwdwwddwdddwwdddwwdddwdwddddddddussusssuddddddddddssddddddddddssddddddddddssddddddddddssddddddddddsswwwwwwwwdduuwwwwwwww"
+        "dduuwwwwwwwwdduuwwwwwwwwdduuwwwwwwwwdduuwwwwwwwwdduuwwwwwwwwdduuwwwwwwwwdduuwwwwwwwwdduuwwwwwwwwdduu",
+    "eval 64,64,128x128":
+        "wddwdddwwdddwwdddwdwwddwdddwwdddwwdddwdwddddddddUssUsssuwddwdddwwdddwwdddwdwwddwdddwwdddwwdddwdwddddddddUssUsssuQddQdddw"
+        "QdddwQdddwdwQddQdddwQdddwQdddwdwddddddddUssUsssuQddQdddwQdddwQdddwdwQddQdddwQdddwQdddwdwddddddddUssUsssuQddQdddwQdddwQdd"
+        "dwdwQddQdddwQdddwQdddwdwddddddddUssUsssuddddddddddssddddddddddssddddddddddssddddddddddssddddddddddsswwwwwwwwdduuwwwwwwww"
+        "dduuwwwwwwwwdduuwwwwwwwwdduuwwwwwwwwdduuQQQQQQQQddUUQQQQQQQQddUUQQQQQQQQddUUQQQQQQQQddUUQQQQQQQQddUU",
+    "eval 64,64,256x256":
+        "QddQdddwQdddwQdddwdwQddQdddwQdddwQdddwdwddddddddUssUsssuQddQdddwQdddwQdddwdwQddQdddwQdddwQdddwdwddddddddUssUsssuQddQdddw"
+        "QdddwQdddwdwQddQdddwQdddwQdddwdwddddddddUssUsssuQddQdddwQdddwQdddwdwQddQdddwQdddwQdddwdwddddddddUssUsssuQddQdddwQdddwQdd"
+        "dwdwQddQdddwQdddwQdddwdwddddddddUssUsssuddddddddddssddddddddddssddddddddddssddddddddddssddddddddddsswwwwwwwwdduuwwwwwwww"
+        "dduuwwwwwwwwdduuwwwwwwwwdduuwwwwwwwwdduuQQQQQQQQddUUQQQQQQQQddUUQQQQQQQQddUUQQQQQQQQddUUQQQQQQQQddUU",
+    "eval 64,128,32x32":
+        "wddwdddwwdddwwdddwdwwddwdddwwdddwwdddwdwddddddddussusssuwddwdddwwdddwwdddwdwwddwdddwwdddwwdddwdwddddddddussusssuwddwdddw"
+        "wdddwwdddwdwwddwdddwwdddwwdddwdwddddddddussusssuwddwdddwwdddwwdddwdwwddwdddwwdddwwdddwdwddddddddussusssuwddwdddwwdddwwdd"
+        "dwdwwddwdddwwdddwwdddwdwddddddddussusssuddddddddddssddddddddddssddddddddddssddddddddddssddddddddddsswwwwwwwwdduuwwwwwwww"
+        "dduuwwwwwwwwdduuwwwwwwwwdduuwwwwwwwwdduuwwwwwwwwdduuwwwwwwwwdduuwwwwwwwwdduuwwwwwwwwdduuwwwwwwwwdduu",
+    "eval 64,128,64x64":
+        "wddwdddwwdddwwdddwdwwddwdddwwdddwwdddwdwddddddddussusssuwddwdddwwdddwwdddwdwwddwdddwwdddwwdddwdwddddddddussusssuwddwdddw"
+        "wdddwwdddwdwwddwdddwwdddwwdddwdwddddddddussusssuQddQdddwQdddwQdddwdwQddQdddwQdddwQdddwdwddddddddussusssuQddQdddwQdddwQdd"
+        "dwdwQddQdddwQdddwQdddwdwddddddddussusssuddddddddddssddddddddddssddddddddddssddddddddddssddddddddddsswwwwwwwwdduuwwwwwwww"
+        "dduuwwwwwwwwdduuwwwwwwwwdduuwwwwwwwwdduuQQQQQQQQdduuQQQQQQQQdduuQQQQQQQQdduuQQQQQQQQdduuQQQQQQQQdduu",
+    "eval 64,128,128x128":
+        "wddwdddwwdddwwdddwdwwddwdddwwdddwwdddwdwddddddddUssUsssuwddwdddwwdddwwdddwdwwddwdddwwdddwwdddwdwddddddddUssUsssuQddQdddw"
+        "QdddwQdddwdwQddQdddwQdddwQdddwdwddddddddUssUsssuQddQdddwQdddwQdddwdwQddQdddwQdddwQdddwdwddddddddUssUsssuQddQdddwQdddwQdd"
+        "dwdwQddQdddwQdddwQdddwdwddddddddUssUsssuddddddddddssddddddddddssddddddddddssddddddddddssddddddddddsswwwwwwwwdduuwwwwwwww"
+        "dduuwwwwwwwwdduuwwwwwwwwdduuwwwwwwwwdduuQQQQQQQQddUUQQQQQQQQddUUQQQQQQQQddUUQQQQQQQQddUUQQQQQQQQddUU",
+    "eval 64,128,256x256":
+        "QddQdddwQdddwQdddwdwQddQdddwQdddwQdddwdwddddddddUssUsssuQddQdddwQdddwQdddwdwQddQdddwQdddwQdddwdwddddddddUssUsssuQddQdddw"
+        "QdddwQdddwdwQddQdddwQdddwQdddwdwddddddddUssUsssuQddQdddwQdddwQdddwdwQddQdddwQdddwQdddwdwddddddddUssUsssuQddQdddwQdddwQdd"
+        "dwdwQddQdddwQdddwQdddwdwddddddddUssUsssuddddddddddssddddddddddssddddddddddssddddddddddssddddddddddsswwwwwwwwdduuwwwwwwww"
+        "dduuwwwwwwwwdduuwwwwwwwwdduuwwwwwwwwdduuQQQQQQQQddUUQQQQQQQQddUUQQQQQQQQddUUQQQQQQQQddUUQQQQQQQQddUU",
+    "eval 128,64,32x32":
+        "wddwdddwwdddwwdddwdwwddwdddwwdddwwdddwdwddddddddussusssuwddwdddwwdddwwdddwdwwddwdddwwdddwwdddwdwddddddddussusssuwddwdddw"
+        "wdddwwdddwdwwddwdddwwdddwwdddwdwddddddddussusssuwddwdddwwdddwwdddwdwwddwdddwwdddwwdddwdwddddddddussusssuwddwdddwwdddwwdd"
+        "dwdwwddwdddwwdddwwdddwdwddddddddussusssuddddddddddssddddddddddssddddddddddssddddddddddssddddddddddsswwwwwwwwdduuwwwwwwww"
+        "dduuwwwwwwwwdduuwwwwwwwwdduuwwwwwwwwdduuwwwwwwwwdduuwwwwwwwwdduuwwwwwwwwdduuwwwwwwwwdduuwwwwwwwwdduu",
+    "eval 128,64,64x64":
+        "wddwdddwwdddwwdddwdwwddwdddwwdddwwdddwdwddddddddussusssuwddwdddwwdddwwdddwdwwddwdddwwdddwwdddwdwddddddddussusssuwddwdddw"
+        "wdddwwdddwdwwddwdddwwdddwwdddwdwddddddddussusssuwddwdddwwdddwwdddwdwwddwdddwwdddwwdddwdwddddddddussusssuwddwdddwwdddwwdd"
+        "dwdwwddwdddwwdddwwdddwdwddddddddussusssuddddddddddssddddddddddssddddddddddssddddddddddssddddddddddsswwwwwwwwdduuwwwwwwww"
+        "dduuwwwwwwwwdduuwwwwwwwwdduuwwwwwwwwdduuwwwwwwwwdduuwwwwwwwwdduuwwwwwwwwdduuwwwwwwwwdduuwwwwwwwwdduu",
+    "eval 128,64,128x128":
+        "wddwdddwwdddwwdddwdwwddwdddwwdddwwdddwdwddddddddUssUsssuwddwdddwwdddwwdddwdwwddwdddwwdddwwdddwdwddddddddUssUsssuQddQdddw"
+        "QdddwQdddwdwQddQdddwQdddwQdddwdwddddddddUssUsssuQddQdddwQdddwQdddwdwQddQdddwQdddwQdddwdwddddddddUssUsssuQddQdddwQdddwQdd"
+        "dwdwQddQdddwQdddwQdddwdwddddddddUssUsssuddddddddddssddddddddddssddddddddddssddddddddddssddddddddddsswwwwwwwwdduuwwwwwwww"
+        "dduuwwwwwwwwdduuwwwwwwwwdduuwwwwwwwwdduuQQQQQQQQddUUQQQQQQQQddUUQQQQQQQQddUUQQQQQQQQddUUQQQQQQQQddUU",
+    "eval 12,64,128x128":
+        "wddwdddwwdddwwdddwdwwddwdddwwdddwwdddwdwddddddddussusssuwddwdddwwdddwwdddwdwwddwdddwwdddwwdddwdwddddddddussusssuwddwdddw"
+        "wdddwwdddwdwwddwdddwwdddwwdddwdwddddddddussusssuqddqdddwqdddwqdddwdwqddqdddwqdddwqdddwdwddddddddussusssuqddqdddwqdddwqdd"
+        "dwdwqddqdddwqdddwqdddwdwddddddddussusssuddddddddddssddddddddddssddddddddddssddddddddddssddddddddddsswwwwwwwwdduuwwwwwwww"
+        "dduuwwwwwwwwdduuwwwwwwwwdduuwwwwwwwwdduuqqqqqqqqdduuqqqqqqqqdduuqqqqqqqqdduuqqqqqqqqdduuqqqqqqqqdduu",
+    "raw 3,64,32x32":
+        "dddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddd",
+    "raw 32,32,32x32":
+        "ddddddddddddddddddddddddddddddddddddddddddddwddwddwwddddddddddddddddddddddddddddddwwdddddddddddddwwd",
+    "raw 32,32,64x64":
+        "dddddddddddddddddddddddddddddddddwddwddwwdddwddwddwwdddddddddddddddddddddddddddwwdwwddddddddddwwdwwd",
+    "raw 32,32,128x128":
+        "ddddddddddddddddddddddwddwddwwdddwddwddwwdddwddwddwwddddddddddddddddddddddddwwdwwdwwdddddddwwdwwdwwd",
+    "raw 32,32,256x256":
+        "wddwddwwdddwddwddwwdddwddwddwwdddwddwddwwdddwddwddwwddddddddddddddddddwwdwwdwwdwwdwwdwwdwwdwwdwwdwwd",
+    "raw 32,64,32x32":
+        "wddwddwwuddwddwddwwuddwddwddwwuddwddwddwwuddwddwddwwudddddddddddddddddwwuwwuwwuwwuwwuwwuwwuwwuwwuwwu",
+    "raw 32,64,64x64":
+        "wddwddwwuddwddwddwwuddwddwddwwuddwddwddwwuddwddwddwwudddddddddddddddddwwuwwuwwuwwuwwuwwuwwuwwuwwuwwu",
+    "raw 32,64,128x128":
+        "wddwddwwuddwddwddwwuddQddQddwwuddQddQddwwuddQddQddwwudddddddddddddddddwwuwwuwwuwwuwwuQQuQQuQQuQQuQQu",
+    "raw 32,64,256x256":
+        "QddQddwwuddQddQddwwuddQddQddwwuddQddQddwwuddQddQddwwudddddddddddddddddwwuwwuwwuwwuwwuQQuQQuQQuQQuQQu",
+    "raw 64,32,32x32":
+        "ddddddddddddddddddddddddddddddddddddddddddddwddwddwwddddddddddddddddddddddddddddddwwdddddddddddddwwd",
+    "raw 64,32,64x64":
+        "dddddddddddddddddddddddddddddddddwddwddwwdddwddwddwwdddddddddddddddddddddddddddwwdwwddddddddddwwdwwd",
+    "raw 64,32,128x128":
+        "ddddddddddddddddddddddwddwddwwdddwddwddwwdddwddwddwwddddddddddddddddddddddddwwdwwdwwdddddddwwdwwdwwd",
+    "raw 64,32,256x256":
+        "wddwddwwdddwddwddwwdddwddwddwwdddwddwddwwdddwddwddwwddddddddddddddddddwwdwwdwwdwwdwwdwwdwwdwwdwwdwwd",
+    "raw 64,64,32x32":
+        "wddwddwwuddwddwddwwuddwddwddwwuddwddwddwwuddwddwddwwudddddddddddddddddwwuwwuwwuwwuwwuwwuwwuwwuwwuwwu",
+    "raw 64,64,64x64":
+        "wddwddwwuddwddwddwwuddwddwddwwuddwddwddwwuddwddwddwwudddddddddddddddddwwuwwuwwuwwuwwuwwuwwuwwuwwuwwu",
+    "raw 64,64,128x128":
+        "wddwddwwuddwddwddwwuddQddQddwwuddQddQddwwuddQddQddwwudddddddddddddddddwwuwwuwwuwwuwwuQQuQQuQQuQQuQQu",
+    "raw 64,64,256x256":
+        "QddQddwwuddQddQddwwuddQddQddwwuddQddQddwwuddQddQddwwudddddddddddddddddwwuwwuwwuwwuwwuQQuQQuQQuQQuQQu",
+    "raw 64,128,32x32":
+        "wddwddwwuddwddwddwwuddwddwddwwuddwddwddwwuddwddwddwwudddddddddddddddddwwuwwuwwuwwuwwuwwuwwuwwuwwuwwu",
+    "raw 64,128,64x64":
+        "wddwddwwuddwddwddwwuddwddwddwwuddQddQddwwuddQddQddwwudddddddddddddddddwwuwwuwwuwwuwwuQQuQQuQQuQQuQQu",
+    "raw 64,128,128x128":
+        "wddwddwwuddwddwddwwuddQddQddwwuddQddQddwwuddQddQddwwudddddddddddddddddwwuwwuwwuwwuwwuQQuQQuQQuQQuQQu",
+    "raw 64,128,256x256":
+        "QddQddwwuddQddQddwwuddQddQddwwuddQddQddwwuddQddQddwwudddddddddddddddddwwuwwuwwuwwuwwuQQuQQuQQuQQuQQu",
+    "raw 128,64,32x32":
+        "wddwddwwuddwddwddwwuddwddwddwwuddwddwddwwuddwddwddwwudddddddddddddddddwwuwwuwwuwwuwwuwwuwwuwwuwwuwwu",
+    "raw 128,64,64x64":
+        "wddwddwwuddwddwddwwuddwddwddwwuddwddwddwwuddwddwddwwudddddddddddddddddwwuwwuwwuwwuwwuwwuwwuwwuwwuwwu",
+    "raw 128,64,128x128":
+        "wddwddwwuddwddwddwwuddQddQddwwuddQddQddwwuddQddQddwwudddddddddddddddddwwuwwuwwuwwuwwuQQuQQuQQuQQuQQu",
+    "raw 12,64,128x128":
+        "wddwddwwuddwddwddwwuddwddwddwwuddqddqddwwuddqddqddwwudddddddddddddddddwwuwwuwwuwwuwwuqquqquqquqquqqu",
+    "cba 3,64,32x32":
+        "dddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddd",
+    "cba 32,32,32x32":
+        "dddddddddddddddddddddddd1ddddddddddddddddddddddd1ddddddddd1dddddddddwd",
+    "cba 32,32,64x64":
+        "dddddddddddddddddd1ddddd1ddddddddddddddddddddd1d1ddddddd1d1dddddddwdwd",
+    "cba 32,32,128x128":
+        "dddddddddddd1ddddd1ddddd1ddddddddddddddddddd1d1d1ddddd1d1d1dddddwdwdwd",
+    "cba 32,32,256x256":
+        "1ddddd1ddddd1ddddd1ddddd1ddddddddddddddd1d1d1d1d1d1d1d1d1d1dwdwdwdwdwd",
+    "cba 32,64,32x32":
+        "1ddudd1ddudd1ddudd1ddudd1ddudddddddddddd1u1u1u1u1u1u1u1u1u1uwuwuwuwuwu",
+    "cba 32,64,64x64":
+        "1ddudd1ddudd1ddudd1ddudd1ddudddddddddddd1u1u1u1u1u1u1u1u1u1uwuwuwuwuwu",
+    "cba 32,64,128x128":
+        "1ddudd1ddudd3ddudd3ddudd3ddudddddddddddd1u1u1u1u1u3u3u3u3u3uwuwuQuQuQu",
+    "cba 32,64,256x256":
+        "3ddudd3ddudd3ddudd3ddudd3ddudddddddddddd1u1u1u1u1u3u3u3u3u3uQuQuQuQuQu",
+    "cba 64,32,32x32":
+        "dddddddddddddddddddddddd1ddddddddddddddddddddddd1ddddddddd1dddddddddwd",
+    "cba 64,32,64x64":
+        "dddddddddddddddddd1ddddd1ddddddddddddddddddddd1d1ddddddd1d1dddddddwdwd",
+    "cba 64,32,128x128":
+        "dddddddddddd1ddddd1ddddd1ddddddddddddddddddd1d1d1ddddd1d1d1dddddwdwdwd",
+    "cba 64,32,256x256":
+        "1ddddd1ddddd1ddddd1ddddd1ddddddddddddddd1d1d1d1d1d1d1d1d1d1dwdwdwdwdwd",
+    "cba 64,64,32x32":
+        "1ddudd1ddudd1ddudd1ddudd1ddudddddddddddd1u1u1u1u1u1u1u1u1u1uwuwuwuwuwu",
+    "cba 64,64,64x64":
+        "1ddudd1ddudd1ddudd1ddudd1ddudddddddddddd1u1u1u1u1u1u1u1u1u1uwuwuwuwuwu",
+    "cba 64,64,128x128":
+        "1ddudd1ddudd3ddudd3ddudd3ddudddddddddddd1u1u1u1u1u3u3u3u3u3uwuwuQuQuQu",
+    "cba 64,64,256x256":
+        "3ddudd3ddudd3ddudd3ddudd3ddudddddddddddd1u1u1u1u1u3u3u3u3u3uQuQuQuQuQu",
+    "cba 64,128,32x32":
+        "1ddudd1ddudd1ddudd1ddudd1ddudddddddddddd1u1u1u1u1u1u1u1u1u1uwuwuwuwuwu",
+    "cba 64,128,64x64":
+        "1ddudd1ddudd1ddudd3ddudd3ddudddddddddddd1u1u1u1u1u3u3u3u3u3uwuwuwuQuQu",
+    "cba 64,128,128x128":
+        "1ddudd1ddudd3ddudd3ddudd3ddudddddddddddd1u1u1u1u1u3u3u3u3u3uwuwuQuQuQu",
+    "cba 64,128,256x256":
+        "3ddudd3ddudd3ddudd3ddudd3ddudddddddddddd1u1u1u1u1u3u3u3u3u3uQuQuQuQuQu",
+    "cba 128,64,32x32":
+        "1ddudd1ddudd1ddudd1ddudd1ddudddddddddddd1u1u1u1u1u1u1u1u1u1uwuwuwuwuwu",
+    "cba 128,64,64x64":
+        "1ddudd1ddudd1ddudd1ddudd1ddudddddddddddd1u1u1u1u1u1u1u1u1u1uwuwuwuwuwu",
+    "cba 128,64,128x128":
+        "1ddudd1ddudd3ddudd3ddudd3ddudddddddddddd1u1u1u1u1u3u3u3u3u3uwuwuQuQuQu",
+    "cba 12,64,128x128":
+        "1ddudd1ddudd1ddudd2ddudd2ddudddddddddddd1u1u1u1u1u2u2u2u2u2uwuwuwuququ",
+}
+
+def test_conv3x3_form_routes_every_site_as_before(monkeypatch):
+    """ops.conv3x3_form is the one routing decision: for every case of the grid above it names the form the site it replaced
+    chose (recorded from util._conv_bn / util._UpBlock.forward / autograd._conv_raw / autograd._cba_forward before they were
+    folded into it), and every form is reached."""
+    from tgsr_amd import autograd, ops
+    seen = set()
+    for site in ("eval", "raw", "cba"):
+        for shape in _ROUTE_SHAPES:
+            key = "%s %d,%d,%dx%d" % ((site,) + shape)
+            want = _ROUTE_TABLE[key]
+            got = []
+            for env, x, upsample, glu, out, residual in _route_cases(site, shape):
+                renv, winograd, bn_stats = _ROUTE_ENVS[env]
+                monkeypatch.setattr(ops, "ROUTING", ops._Routing(env=renv))
+                form = ops.conv3x3_form(x, shape[1], upsample, glu, out, residual, winograd, site != "eval")
+                seen.add(form)
+                if site == "cba" and bn_stats and ops.FORMS[form].stats is not None:      # autograd._cba_forward's own condition
+                    form += "+stats"
+                got.append(_ROUTE_CODE[form])
+            got = "".join(got)
+            assert len(got) == len(want), key
+            bad = [i for i in range(len(got)) if got[i] != want[i]]
+            assert not bad, "%s: case %d of its grid: %s, was %s" % (key, bad[0], got[bad[0]], want[bad[0]])
+    assert seen == set(ops.FORMS)
+    # the environment variables the switches of the grid stand for are read where they were
+    assert ops._Routing(env={"TGSR_WINO4": "0"}).wino4 is False and ops._Routing(env={"TGSR_WINO4_PIN_BATCH": "16"}).pin_batch == 16
+    assert isinstance(autograd.BN_STATS_IN_CONV, bool)
+
+
+# every torch.ops.tgsr operator registered before the conv3x3 / pack definitions were generated from ops.FORMS
+_TGSR_SCHEMAS = [
+    "tgsr::adam_flat_(Tensor(a!) param, Tensor grad, Tensor(b!) exp_avg, Tensor(c!) exp_avg_sq, Tensor(d!) state, float lr, float "
+    "beta1, float beta2, float eps, float weight_decay, bool advance) -> ()",
+    "tgsr::affine_act(Tensor raw, Tensor scale, Tensor shift, int act) -> Tensor",
+    "tgsr::affine_act_bwd(Tensor dy, Tensor? out, Tensor scale, int act) -> Tensor",
+    "tgsr::avgpool3(Tensor x, Tensor(a!) out, bool accumulate, Tensor? mask) -> ()",
+    "tgsr::axpy_images(Tensor[] ts, Tensor[] ss, float alpha) -> Tensor[]",
+    "tgsr::axpy_map(Tensor t, Tensor s, Tensor amap) -> Tensor",
+    "tgsr::axpy_map_bwd(Tensor dy, Tensor s, Tensor amap, bool need_ds, bool need_da) -> (Tensor, Tensor)",
+    "tgsr::bigru_bwd(int[] cap_lens, Tensor w_hh, Tensor acts, Tensor words, Tensor d_words, Tensor? d_sent) -> (Tensor, Tensor, "
+    "Tensor, Tensor)",
+    "tgsr::bigru_table(Tensor captions, int[] cap_lens, Tensor table, Tensor w_hh, Tensor b_hn) -> (Tensor, Tensor)",
+    "tgsr::bigru_table_static(Tensor captions, Tensor cap_lens, Tensor table, Tensor w_hh, Tensor b_hn) -> (Tensor, Tensor)",
+    "tgsr::bigru_train(Tensor x, Tensor w_ih, Tensor w_hh, Tensor b_ih, Tensor b_hh, int[] cap_lens) -> (Tensor, Tensor, Tensor)",
+    "tgsr::bilinear(Tensor x, int OH, int OW) -> Tensor",
+    "tgsr::bilinear_bwd(Tensor dy, int H, int W) -> Tensor",
+    "tgsr::bilstm_bwd(int[] cap_lens, Tensor w_hh, Tensor acts, Tensor words, Tensor d_words, Tensor? d_sent) -> (Tensor, Tensor, "
+    "Tensor)",
+    "tgsr::bilstm_table(Tensor captions, int[] cap_lens, Tensor table, Tensor w_hh) -> (Tensor, Tensor)",
+    "tgsr::bilstm_table_static(Tensor captions, Tensor cap_lens, Tensor table, Tensor w_hh) -> (Tensor, Tensor)",
+    "tgsr::bilstm_train(Tensor x, Tensor w_ih, Tensor w_hh, Tensor b_ih, Tensor b_hh, int[] cap_lens) -> (Tensor, Tensor, Tensor)",
+    "tgsr::bn_train_bwd(Tensor dout, Tensor raw, Tensor stats, int act, Tensor(a!) dgamma, Tensor(b!) dbeta, Tensor(c!)? draw) -> "
+    "Tensor",
+    "tgsr::bn_train_fwd(Tensor raw, Tensor gamma, Tensor beta, float eps, float momentum, Tensor(a!)? running_mean, Tensor(b!)? "
+    "running_var, int act, Tensor? residual, Tensor(c!)? num_batches_tracked) -> (Tensor, Tensor)",
+    "tgsr::bn_train_fwd_from_stats(Tensor raw, Tensor gamma, Tensor beta, float eps, float momentum, Tensor(a!)? running_mean, "
+    "Tensor(b!)? running_var, int act, Tensor? residual, Tensor(c!)? num_batches_tracked, Tensor stat_partial) -> (Tensor, Tensor)",
+    "tgsr::bn_train_fwd_out(Tensor raw, Tensor gamma, Tensor beta, float eps, float momentum, Tensor(a!)? running_mean, Tensor(b!)? "
+    "running_var, int act, Tensor(c!)? num_batches_tracked, Tensor(d!) out, Tensor(e!) stats) -> ()",
+    "tgsr::bn_train_relu_slice_from_stats(Tensor(a!) y, int coff, Tensor gamma, Tensor beta, float eps, float momentum, Tensor(b!)? "
+    "running_mean, Tensor(c!)? running_var, Tensor(d!)? num_batches_tracked, Tensor stat_partial, int slot_px, Tensor(e!) stats) -> ()",
+    "tgsr::ca_net(Tensor sent_emb, Tensor w, Tensor b, int ncf, Tensor? eps) -> (Tensor, Tensor, Tensor)",
+    "tgsr::conv1x1(Tensor x, Tensor w) -> Tensor",
+    "tgsr::conv3x3_fused(Tensor x, Tensor wpack, int cout, Tensor? scale, Tensor? shift, bool glu, bool upsample, Tensor? residual) -> "
+    "Tensor",
+    "tgsr::conv3x3_fused_out(Tensor x, Tensor wpack, int cout, Tensor? scale, Tensor? shift, bool glu, bool upsample, Tensor? residual, "
+    "Tensor(a!) out) -> ()",
+    "tgsr::conv3x3_gemm(Tensor x, Tensor w) -> Tensor",
+    "tgsr::conv3x3_gemm_dgrad(Tensor dy, Tensor w) -> Tensor",
+    "tgsr::conv3x3_gemm_wgrad_out(Tensor dy, Tensor x, Tensor(a!) dw) -> ()",
+    "tgsr::conv3x3_wgrad(Tensor draw, Tensor x, bool upsample, bool winograd, Tensor(a!) dw) -> ()",
+    "tgsr::conv3x3_wino(Tensor x, Tensor upack, int cout, Tensor? scale, Tensor? shift, bool glu, Tensor? residual) -> Tensor",
+    "tgsr::conv3x3_wino4(Tensor x, Tensor upack, int cout, Tensor? scale, Tensor? shift, bool glu, Tensor? residual) -> Tensor",
+    "tgsr::conv3x3_wino4_out(Tensor x, Tensor upack, int cout, Tensor? scale, Tensor? shift, bool glu, Tensor? residual, Tensor(a!) "
+    "out) -> ()",
+    "tgsr::conv3x3_wino4_stats(Tensor x, Tensor upack, int cout) -> (Tensor, Tensor)",
+    "tgsr::conv3x3_wino4w(Tensor x, Tensor upack, int cout, Tensor? scale, Tensor? shift, bool glu, Tensor? residual) -> Tensor",
+    "tgsr::conv3x3_wino4w_out(Tensor x, Tensor upack, int cout, Tensor? scale, Tensor? shift, bool glu, Tensor? residual, Tensor(a!) "
+    "out) -> ()",
+    "tgsr::conv3x3_wino4w_stats(Tensor x, Tensor upack, int cout) -> (Tensor, Tensor)",
+    "tgsr::conv3x3_wino_out(Tensor x, Tensor upack, int cout, Tensor? scale, Tensor? shift, bool glu, Tensor? residual, Tensor(a!) out) "
+    "-> ()",
+    "tgsr::conv3x3_wino_stats(Tensor x, Tensor upack, int cout) -> (Tensor, Tensor)",
+    "tgsr::conv4x4s2(Tensor x, Tensor w, bool leaky) -> Tensor",
+    "tgsr::conv4x4s2_dgrad(Tensor dy, Tensor w, int H, int W) -> Tensor",
+    "tgsr::conv4x4s2_wgrad(Tensor dy, Tensor x) -> Tensor",
+    "tgsr::conv4x4s2_wgrad_out(Tensor dy, Tensor x, Tensor(a!) dw) -> ()",
+    "tgsr::conv_to3(Tensor x, Tensor w, bool tanh_axpy, Tensor? addend, float alpha) -> Tensor",
+    "tgsr::conv_to3_bwd(Tensor dy, Tensor? out, Tensor? addend, float alpha, Tensor x, Tensor w, bool tanh_axpy, bool need_dx, bool "
+    "need_dw) -> (Tensor, Tensor)",
+    "tgsr::damsm_words(Tensor img_features, Tensor words_emb, int[] cap_lens, float gamma1, float gamma2) -> (Tensor, Tensor)",
+    "tgsr::damsm_words_bwd(Tensor img_features, Tensor words_emb, int[] cap_lens, float gamma1, float gamma2, Tensor grad_sim) -> "
+    "(Tensor, Tensor)",
+    "tgsr::func_attention(Tensor query, Tensor context, float gamma1) -> (Tensor, Tensor)",
+    "tgsr::gconv(bool dgrad, Tensor A, Tensor S, int s_coff, int s_ch, Tensor(a!) out, int o_coff, int kh, int kw, int stride, int "
+    "padh, int padw, Tensor? bias, bool relu, bool accumulate, Tensor(b!)? ws, Tensor? mask) -> ()",
+    "tgsr::gconv_pack(Tensor w, Tensor? scale, bool dgrad) -> Tensor",
+    "tgsr::gconv_stats(Tensor A, Tensor S, int s_coff, int s_ch, Tensor(a!) out, int o_coff, int kh, int kw, int stride, int padh, int "
+    "padw, Tensor(b!)? ws, Tensor(c!) stat_partial) -> ()",
+    "tgsr::glu(Tensor x) -> Tensor",
+    "tgsr::glu_bwd(Tensor dy, Tensor x) -> Tensor",
+    "tgsr::gru_gate_table(Tensor emb, Tensor w_ih, Tensor b_ih, Tensor b_hh) -> (Tensor, Tensor)",
+    "tgsr::interleave2x2_(Tensor t00, Tensor t01, Tensor t10, Tensor t11, Tensor(a!) dx, bool accumulate, Tensor? mask) -> ()",
+    "tgsr::leaky_relu_bwd(Tensor dy, Tensor y) -> Tensor",
+    "tgsr::linear(Tensor x, Tensor w, Tensor? bias) -> Tensor",
+    "tgsr::lp_conv3x3(Tensor x, Tensor wpack, int cin, int cout, Tensor? scale, Tensor? shift, bool glu, bool upsample, Tensor? "
+    "residual, int res_coff, Tensor(a!) out, int out_coff) -> ()",
+    "tgsr::lp_conv_to3(Tensor x, Tensor wpack, int K, bool tanh_axpy, Tensor? addend, float alpha) -> Tensor",
+    "tgsr::lp_conv_to3_map(Tensor x, Tensor wpack, int K, bool tanh, Tensor? addend, float alpha, Tensor? amap) -> Tensor",
+    "tgsr::lp_convert(Tensor src, Tensor(a!) out) -> ()",
+    "tgsr::lp_head_combine(int[] H, int[] W, Tensor[] partial_low, Tensor[] partial_high, Tensor(a!)[] low, Tensor(b!)[] high, bool "
+    "low_tanh, float alpha) -> ()",
+    "tgsr::lp_head_combine_map(int[] H, int[] W, Tensor[] partial_low, Tensor[] partial_high, Tensor(a!)[] low, Tensor(b!)[] high, "
+    "Tensor[] amap, bool low_tanh, bool high_tanh, float alpha) -> ()",
+    "tgsr::lp_resblocks(Tensor x, Tensor[] wpacks, Tensor[] scales, Tensor[] shifts, Tensor(a!) tmp, Tensor(b!) a, Tensor(c!) b, "
+    "Tensor(d!) flags) -> ()",
+    "tgsr::lp_stem(Tensor x, Tensor w, Tensor scale, Tensor shift, Tensor(a!) out, int out_coff) -> ()",
+    "tgsr::lp_stem_att(Tensor x, Tensor w, Tensor scale, Tensor shift, Tensor(a!) out, int out_coff, Tensor att_pack, int nsets, int "
+    "index, int T, bool use_mask, bool correct_mask, int c_coff, Tensor(b!)? attn) -> ()",
+    "tgsr::lp_upconv_glu(Tensor x, Tensor wpack, int cin, int cout, Tensor? scale, Tensor? shift, Tensor(a!) out, int out_coff) -> ()",
+    "tgsr::lp_upconv_glu_att(Tensor x, Tensor wpack, int cin, int cout, Tensor? scale, Tensor? shift, Tensor(a!) out, int out_coff, "
+    "Tensor att_pack, int nsets, int index, int T, bool use_mask, bool correct_mask, int c_coff, Tensor(b!)? attn) -> ()",
+    "tgsr::lp_upconv_glu_head(Tensor x, Tensor wpack, int cin, int cout, Tensor? scale, Tensor? shift, Tensor head_wpack, int K, "
+    "Tensor(a!) partial, Tensor(b!)? out, int out_coff) -> ()",
+    "tgsr::lp_upconv_glu_head_att(Tensor x, Tensor wpack, int cin, int cout, Tensor? scale, Tensor? shift, Tensor head_wpack, int K, "
+    "Tensor(a!) partial, Tensor(b!) out, int out_coff, Tensor att_pack, int nsets, int index, int T, bool use_mask, bool correct_mask, "
+    "int c_coff, Tensor(c!)? attn) -> ()",
+    "tgsr::lp_word_attention(Tensor(a!) h_img, Tensor src, Tensor? mask, int T, bool correct_mask, int c_coff) -> Tensor",
+    "tgsr::lstm_gate_table(Tensor emb, Tensor w_ih, Tensor b_ih, Tensor b_hh) -> Tensor",
+    "tgsr::maxpool3s2(Tensor x, Tensor(a!) out, int o_coff) -> ()",
+    "tgsr::maxpool3s2_bwd(Tensor x, Tensor dy, int dy_coff, Tensor(a!) dx, bool accumulate, Tensor? mask) -> ()",
+    "tgsr::multi_copy(Tensor(a!)[] dsts, Tensor[] srcs) -> ()",
+    "tgsr::pack_conv3x3_weight(Tensor w, bool dgrad) -> Tensor",
+    "tgsr::pack_upwino4_weight(Tensor w, bool glu) -> Tensor",
+    "tgsr::pack_upwino_weight(Tensor w, bool glu) -> Tensor",
+    "tgsr::pack_wino4_weight(Tensor w, bool glu, bool dgrad) -> Tensor",
+    "tgsr::pack_wino4w_weight(Tensor w, bool glu, bool dgrad) -> Tensor",
+    "tgsr::pack_wino_weight(Tensor w, bool glu, bool dgrad) -> Tensor",
+    "tgsr::plane_mean(Tensor x) -> Tensor",
+    "tgsr::plane_mean_bwd(Tensor dy, int H, int W) -> Tensor",
+    "tgsr::relu_mask_(Tensor(a!) dy, Tensor y, int coff, int ch) -> ()",
+    "tgsr::rowdot(Tensor x, Tensor w, Tensor? bias) -> Tensor",
+    "tgsr::rowdot_bwd(Tensor dy, Tensor x, Tensor w, bool need_dx, bool need_dw) -> (Tensor, Tensor)",
+    "tgsr::sum_stack(Tensor stack, int n, Tensor(a!) out) -> ()",
+    "tgsr::sumpool2x2(Tensor x) -> Tensor",
+    "tgsr::text_tail(Tensor words, Tensor[] w_ctxs, Tensor sent_emb, Tensor ca_w, Tensor ca_b, int ncf, Tensor captions) -> (Tensor, "
+    "Tensor, Tensor, Tensor)",
+    "tgsr::text_tail_lp(Tensor words, Tensor[] w_ctxs, Tensor sent_emb, Tensor ca_w, Tensor ca_b, int ncf, Tensor captions, bool bf16) "
+    "-> (Tensor, Tensor, Tensor, Tensor, Tensor)",
+    "tgsr::to_uint8(Tensor img) -> Tensor",
+    "tgsr::upconv3x3_glu(Tensor x, Tensor wpack, int cout, Tensor scale, Tensor shift) -> Tensor",
+    "tgsr::upconv3x3_glu_out(Tensor x, Tensor wpack, int cout, Tensor scale, Tensor shift, Tensor(a!) out) -> ()",
+    "tgsr::upwino(Tensor x, Tensor upack, int cout, Tensor? scale, Tensor? shift, bool glu) -> Tensor",
+    "tgsr::upwino4_glu(Tensor x, Tensor upack, int cout, Tensor scale, Tensor shift) -> Tensor",
+    "tgsr::upwino4_glu_out(Tensor x, Tensor upack, int cout, Tensor scale, Tensor shift, Tensor(a!) out) -> ()",
+    "tgsr::upwino_glu(Tensor x, Tensor upack, int cout, Tensor scale, Tensor shift) -> Tensor",
+    "tgsr::upwino_glu_out(Tensor x, Tensor upack, int cout, Tensor scale, Tensor shift, Tensor(a!) out) -> ()",
+    "tgsr::weighted_bce(Tensor a, Tensor? b, Tensor target, Tensor weight) -> Tensor",
+    "tgsr::weighted_bce_bwd(Tensor dy, Tensor a, Tensor? b, Tensor target, Tensor weight) -> (Tensor, Tensor)",
+    "tgsr::word_attention(Tensor h, Tensor words, Tensor w_ctx, Tensor? mask, bool correct_mask, Tensor? src) -> (Tensor, Tensor)",
+    "tgsr::word_attention_bwd(Tensor h, Tensor src, Tensor? mask, bool correct_mask, int T, Tensor dc) -> (Tensor, Tensor)",
+    "tgsr::word_attention_out(Tensor h, Tensor words, Tensor w_ctx, Tensor? mask, bool correct_mask, Tensor? src, Tensor(a!) out) -> "
+    "Tensor",
+    "tgsr::word_project(Tensor words, Tensor[] w_ctxs) -> Tensor[]",
+]
+
+
+def test_form_table_names_the_c_abi_and_the_operators_stay():
+    """Every C entry point ops.FORMS names is declared in _lib.SIGNATURES, and torch.ops.tgsr has every operator it had before the
+    conv / pack operators were generated from the table, with the same schema."""
+    import tgsr_amd.custom_ops  # noqa: F401
+    import tgsr_amd.lp  # noqa: F401
+    from tgsr_amd import _lib, ops
+    for f in ops.FORMS.values():
+        for name in (f.fwd, f.fwd_plain, f.stats, f.nslots, f.pack, f.pack_dgrad, f.elems):
+            assert name is None or name in _lib.SIGNATURES, (f.name, name)
+        assert (f.stats is None) == (f.nslots is None) and f.fwd and f.pack and f.elems
+    have = {str(s) for s in torch._C._jit_get_all_schemas() if s.name.startswith("tgsr::")}
+    missing = [s for s in _TGSR_SCHEMAS if s not in have]
+    assert not missing, missing

@@ -8,6 +8,8 @@ The reference trains through torch autograd over nn.Conv2d / nn.BatchNorm2d(trai
         backward: tgsr_bn_train_bwd (GLU', BN') -> data gradient = the same conv kernels on flipped/transposed
                   weights (+ tgsr_sumpool2x2 through the up-sample) and tgsr_conv3x3_wgrad
 """
+import os
+
 import torch
 
 from . import custom_ops as C
@@ -87,43 +89,29 @@ class PackCache:
     still equals the one it was made from (a load_state_dict or any other in-place write makes it re-pack on the spot)."""
 
     def __init__(self):
-        self.entries = {}            # (data_ptr, shape, kind) -> [weight alias, kind, packed, version]
+        self.entries = {}            # (data_ptr, shape, form, dgrad) -> [weight alias, form, dgrad, packed, version]
         self.stream = None
         self.event = None
 
-    @staticmethod
-    def _pack(weight, kind, out):
-        if kind in ("wino4", "wino4_dgrad"):
-            return ops.pack_wino4_weight(weight, False, kind == "wino4_dgrad", out=out)
-        if kind in ("wino4w", "wino4w_dgrad"):
-            return ops.pack_wino4w_weight(weight, False, kind == "wino4w_dgrad", out=out)
-        if kind == "wino":
-            return ops.pack_wino_weight(weight, False, False, out=out)
-        if kind == "wino_dgrad":
-            return ops.pack_wino_weight(weight, False, True, out=out)
-        if kind == "upwino":
-            return ops.pack_upwino_weight(weight, False, out=out)
-        return ops.pack_conv3x3_weight(weight, kind == "direct_dgrad", out=out)
-
-    def get(self, weight, kind):
+    def get(self, weight, form, dgrad=False):
         if self.event is not None:                       # first use after a repack: this stream waits for it once
             torch.cuda.current_stream(weight.device).wait_event(self.event)
             self.event = None
-        key = (weight.data_ptr(), tuple(weight.shape), kind)
+        key = (weight.data_ptr(), tuple(weight.shape), form, dgrad)
         e = self.entries.get(key)
-        if e is not None and e[3] == weight._version:
-            return e[2]
-        out = self._pack(weight, kind, e[2] if e is not None else None)
-        self.entries[key] = [weight.detach(), kind, out, weight._version]
+        if e is not None and e[4] == weight._version:
+            return e[3]
+        out = ops.pack_weight(form, weight, False, dgrad, e[3] if e is not None else None)
+        self.entries[key] = [weight.detach(), form, dgrad, out, weight._version]
         return out
 
-    def get_captured(self, weight, kind):
+    def get_captured(self, weight, form, dgrad=False):
         """Inside a hipGraph capture of a train step (train.SRTrainer): the cached pack, without a launch - the captured
         optimizer segment rewrites every entry in place at the end of each replay (`repack_captured`), so whatever step is
-        replayed next finds the packs of the current weights at these addresses.  None when the (weight, kind) pair was never
+        replayed next finds the packs of the current weights at these addresses.  None when the (weight, form) pair was never
         packed by an eager step: the caller then packs inside the graph."""
-        e = self.entries.get((weight.data_ptr(), tuple(weight.shape), kind))
-        return None if e is None else e[2]
+        e = self.entries.get((weight.data_ptr(), tuple(weight.shape), form, dgrad))
+        return None if e is None else e[3]
 
     def repack_captured(self, side):
         """`repack(force=True)` as nodes of the graph being captured on the current stream: the pack launches fork onto `side`
@@ -132,12 +120,12 @@ class PackCache:
         side.wait_stream(cur)
         with torch.cuda.stream(side), torch.no_grad():
             for e in self.entries.values():
-                self._pack(e[0], e[1], e[2])
+                ops.pack_weight(e[1], e[0], False, e[2], e[3])
 
     def mark_fresh(self):
         """After a replay whose graph re-packed every entry: the entries match the weights' current version counters."""
         for e in self.entries.values():
-            e[3] = e[0]._version
+            e[4] = e[0]._version
 
     def settle(self, dev):
         """Make the current stream wait for a pending eager repack (before a replay that reads the packs)."""
@@ -159,77 +147,54 @@ class PackCache:
             self.stream.wait_stream(torch.cuda.current_stream(dev))
             with torch.cuda.stream(self.stream), torch.no_grad():
                 for e in self.entries.values():
-                    if force or e[3] != e[0]._version:
-                        self._pack(e[0], e[1], e[2])
-                        e[3] = e[0]._version
+                    if force or e[4] != e[0]._version:
+                        ops.pack_weight(e[1], e[0], False, e[2], e[3])
+                        e[4] = e[0]._version
             self.event = torch.cuda.Event()
             self.event.record(self.stream)
 
 
-import os as _os
-BN_STATS_IN_CONV = _os.environ.get("TGSR_BN_STATS_IN_CONV", "1") != "0"
+BN_STATS_IN_CONV = os.environ.get("TGSR_BN_STATS_IN_CONV", "1") != "0"
 _PACKS = None        # the PackCache of the trainer whose step is running (train.SRTrainer sets it), else packs are per call
 
 
-def _packed(weight, kind):
+def _packed(weight, form, dgrad=False):
     if _PACKS is not None and weight.is_cuda:
         if not torch.cuda.is_current_stream_capturing():
-            return _PACKS.get(weight, kind)
-        hit = _PACKS.get_captured(weight, kind)
+            return _PACKS.get(weight, form, dgrad)
+        hit = _PACKS.get_captured(weight, form, dgrad)
         if hit is not None:
             return hit
-    if kind in ("wino4", "wino4_dgrad"):
-        return C.pack_wino4_weight(weight, False, kind == "wino4_dgrad")
-    if kind in ("wino4w", "wino4w_dgrad"):
-        return C.pack_wino4w_weight(weight, False, kind == "wino4w_dgrad")
-    if kind in ("wino", "wino_dgrad"):
-        return C.pack_wino_weight(weight, False, kind == "wino_dgrad")
-    if kind == "upwino":
-        return C.pack_upwino_weight(weight, False)
-    return C.pack_conv3x3_weight(weight, kind == "direct_dgrad")
+    return ops.pack_weight(form, weight, False, dgrad)
 
 
 def _conv_raw(x: torch.Tensor, weight: torch.Tensor, upsample: bool = False, dgrad: bool = False,
               residual: torch.Tensor = None) -> torch.Tensor:
-    """conv3x3 without affine / activation (what BatchNorm's batch statistics are taken of, and the data gradient):
-    the Winograd kernel where it applies (no up-sampling, Cout % 64 == 0, Cin % 4 == 0), else the direct kernel.
+    """conv3x3 without affine / activation (what BatchNorm's batch statistics are taken of, and the data gradient) on the
+    kernel form ops.conv3x3_form names for training: F(4x4) / F(2x2) Winograd, forward and data gradient alike, the
+    up-sample-aware Winograd form without its gate, else the direct kernel.
     The weights change every step: they are packed per call (a few microseconds each), or - inside a trainer's step -
     served from its PackCache, which re-packs them all behind the optimizer on a stream of its own.  `dgrad`: `weight` is the forward
     layer's [Cin_of_x... = weight.shape[0]] filter and the conv applied is its transpose (pack kernels read it
     transposed and flipped: no flip / transpose / copy kernels)."""
     from . import util
     Cout = weight.shape[1] if dgrad else weight.shape[0]
-    if util.WINOGRAD and not upsample and util._wino4_takes(x, Cout, None, residual):
-        # the large layers: F(4x4, 3x3), forward and data gradient alike (tgsr_winograd4.hip); the register-fed form where the
-        # convolution has an even number of 4-channel stages
-        if x.shape[1] % 8 == 0:
-            return C.conv3x3_wino4w(x, _packed(weight, "wino4w_dgrad" if dgrad else "wino4w"), Cout, None, None, False, residual)
-        return C.conv3x3_wino4(x, _packed(weight, "wino4_dgrad" if dgrad else "wino4"), Cout, None, None, False, residual)
-    if util.WINOGRAD and not upsample and util._wino_pays(x, Cout, None, None):
-        return C.conv3x3_wino(x, _packed(weight, "wino_dgrad" if dgrad else "wino"), Cout, None, None, False, residual)
-    if util.WINOGRAD and upsample and ops.upwino_supported(x, Cout):
-        assert not dgrad and residual is None
-        return C.upwino(x, _packed(weight, "upwino"), Cout, None, None, False)
-    return C.conv3x3_fused(x, _packed(weight, "direct_dgrad" if dgrad else "direct"), Cout, None, None, False, upsample, residual)
+    form = ops.conv3x3_form(x, Cout, upsample, False, None, residual, util.WINOGRAD, True)
+    return C.CONV3X3[form](x, _packed(weight, form, dgrad), Cout, None, None, False, upsample, residual)
 
 
 def _cba_forward(x, weight, gamma, beta, running_mean, running_var, residual, glu, upsample, momentum, eps, nbt):
     """conv3x3 (raw) -> BatchNorm batch statistics -> normalise (+ GLU | + residual).  Returns (out, raw, stats)."""
     from . import util
     w = weight.detach()
-    if BN_STATS_IN_CONV and util.WINOGRAD and not upsample and util._wino4_takes(x, w.shape[0], None, None):
-        raw, part = (C.conv3x3_wino4w_stats(x, _packed(w, "wino4w"), w.shape[0]) if x.shape[1] % 8 == 0 else
-                     C.conv3x3_wino4_stats(x, _packed(w, "wino4"), w.shape[0]))
-        out, stats = C.bn_train_fwd_from_stats(raw, gamma.detach(), beta.detach(), float(eps), float(momentum), running_mean,
-                                               running_var, 1 if glu else 0, residual, nbt, part)
-        return out, raw, stats
-    if BN_STATS_IN_CONV and util.WINOGRAD and not upsample and util._wino_pays(x, w.shape[0], None, None):
+    form = ops.conv3x3_form(x, w.shape[0], upsample, False, None, None, util.WINOGRAD, True)
+    if BN_STATS_IN_CONV and ops.FORMS[form].stats is not None:
         # BatchNorm's statistics pass rides the convolution's epilogue: one (sum, sumsq) pair per channel and wave tile
-        raw, part = C.conv3x3_wino_stats(x, _packed(w, "wino"), w.shape[0])
+        raw, part = C.conv3x3_stats(form, x, _packed(w, form), w.shape[0])
         out, stats = C.bn_train_fwd_from_stats(raw, gamma.detach(), beta.detach(), float(eps), float(momentum), running_mean,
                                                running_var, 1 if glu else 0, residual, nbt, part)
         return out, raw, stats
-    raw = _conv_raw(x, w, upsample)
+    raw = C.CONV3X3[form](x, _packed(w, form), w.shape[0], None, None, False, upsample)
     out, stats = C.bn_train_fwd(raw, gamma.detach(), beta.detach(), float(eps), float(momentum), running_mean, running_var,
                                 1 if glu else 0, residual, nbt)
     return out, raw, stats

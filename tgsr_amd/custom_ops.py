@@ -43,118 +43,101 @@ def _co(cout, glu):
     return cout // 2 if glu else cout
 
 
-# ------------------------------------------------------------------------------------------------ fused conv3x3 (direct)
-def _conv3x3_fused(x, wpack, cout, scale, shift, glu, upsample, residual):
-    return ops.conv3x3_fused(x, wpack, cout, scale, shift, glu=glu, upsample=upsample, residual=residual)
+# ------------------------------------------------------------------------------------------------ conv3x3, every kernel form
+# One operator family per row of ops.FORMS: `op` (functional), `op`_out (into a channel-slice view), `op`_stats where the form has
+# the BatchNorm-statistics epilogue, `op_plain` (the un-gated up-sampling convolution of training) and `pack_op`.
+def _pack_fake(form, w, dgrad):
+    return w.new_empty(ops.packed_elems(form, w.shape[1], w.shape[0]) if dgrad else ops.packed_elems(form, w.shape[0], w.shape[1]))
 
 
-def _conv3x3_fused_fake(x, wpack, cout, scale, shift, glu, upsample, residual):
-    B, _, H, W = x.shape
-    m = 2 if upsample else 1
-    return x.new_empty(B, _co(cout, glu), H * m, W * m)
+def _define_form(f):
+    form, g = f.name, globals()
+    pack = "upack" if "wino" in form else "wpack"          # the schema's name for the Winograd-transformed / the re-ordered weights
+    run = ops._conv3x3
+    if f.up:           # upBlock forms: gated, the affine required, no residual
+        sig = "Tensor x, Tensor %s, int cout, Tensor scale, Tensor shift" % pack
+        fn = lambda x, p, cout, s, t: run(form, x, p, cout, s, t, True, True, None, None)                          # noqa: E731
+        fn_out = lambda x, p, cout, s, t, out: (run(form, x, p, cout, s, t, True, True, None, out), None)[1]      # noqa: E731
+        fake = lambda x, p, cout, s, t: x.new_empty(x.shape[0], cout // 2, 2 * x.shape[2], 2 * x.shape[3])        # noqa: E731
+    elif f.tail == "epi,up":
+        sig = "Tensor x, Tensor %s, int cout, Tensor? scale, Tensor? shift, bool glu, bool upsample, Tensor? residual" % pack
+        fn = lambda x, p, cout, s, t, glu, up, res: run(form, x, p, cout, s, t, glu, up, res, None)               # noqa: E731
+        fn_out = lambda x, p, cout, s, t, glu, up, res, out: (run(form, x, p, cout, s, t, glu, up, res, out), None)[1]   # noqa: E731
+        fake = lambda x, p, cout, s, t, glu, up, res: x.new_empty(x.shape[0], _co(cout, glu), x.shape[2] * (2 if up else 1),   # noqa: E731
+                                                                  x.shape[3] * (2 if up else 1))
+    else:
+        sig = "Tensor x, Tensor %s, int cout, Tensor? scale, Tensor? shift, bool glu, Tensor? residual" % pack
+        fn = lambda x, p, cout, s, t, glu, res: run(form, x, p, cout, s, t, glu, False, res, None)                # noqa: E731
+        fn_out = lambda x, p, cout, s, t, glu, res, out: (run(form, x, p, cout, s, t, glu, False, res, out), None)[1]    # noqa: E731
+        fake = lambda x, p, cout, s, t, glu, res: x.new_empty(x.shape[0], _co(cout, glu), x.shape[2], x.shape[3])  # noqa: E731
+    g[f.op] = _define("%s(%s) -> Tensor" % (f.op, sig), fn, fake)
+    g[f.op + "_out"] = _define("%s_out(%s, Tensor(a!) out) -> ()" % (f.op, sig), fn_out, lambda *a: None)
+    if f.op_plain is not None:
+        g[f.op_plain] = _define("%s(Tensor x, Tensor %s, int cout, Tensor? scale, Tensor? shift, bool glu) -> Tensor" % (f.op_plain, pack),
+                                lambda x, p, cout, s, t, glu: run(form, x, p, cout, s, t, glu, True, None, None),
+                                lambda x, p, cout, s, t, glu: x.new_empty(x.shape[0], _co(cout, glu), 2 * x.shape[2], 2 * x.shape[3]))
+    if f.stats is not None:
+        g[f.op + "_stats"] = _define(
+            "%s_stats(Tensor x, Tensor %s, int cout) -> (Tensor, Tensor)" % (f.op, pack),
+            lambda x, p, cout: run(form, x, p, cout, None, None, False, False, None, None, True),
+            lambda x, p, cout: (x.new_empty(x.shape[0], cout, x.shape[2], x.shape[3]),
+                                x.new_empty(cout, ops.stats_nslots(form, x.shape[0], x.shape[2], x.shape[3], cout), 2)))
+    # the pack operator's schema names the flags the form's pack has: a data-gradient pack (`dgrad`), the gate grouping (`glu`)
+    if f.pack_op is None:
+        return
+    if f.pack_arg == "k":
+        g[f.pack_op] = _define("%s(Tensor w, bool dgrad) -> Tensor" % f.pack_op, lambda w, d: ops.pack_weight(form, w, False, d),
+                               lambda w, d: _pack_fake(form, w, d))
+    elif f.pack_dgrad is not None:
+        g[f.pack_op] = _define("%s(Tensor w, bool glu, bool dgrad) -> Tensor" % f.pack_op, lambda w, gl, d: ops.pack_weight(form, w, gl, d),
+                               lambda w, gl, d: _pack_fake(form, w, d))
+    else:
+        g[f.pack_op] = _define("%s(Tensor w, bool glu) -> Tensor" % f.pack_op, lambda w, gl: ops.pack_weight(form, w, gl),
+                               lambda w, gl: _pack_fake(form, w, False))
 
 
-def _conv3x3_fused_out(x, wpack, cout, scale, shift, glu, upsample, residual, out):
-    ops.conv3x3_fused(x, wpack, cout, scale, shift, glu=glu, upsample=upsample, residual=residual, out=out)
+for _f in ops.FORMS.values():
+    _define_form(_f)
 
 
-conv3x3_fused = _define("conv3x3_fused(Tensor x, Tensor wpack, int cout, Tensor? scale, Tensor? shift, bool glu, "
-                        "bool upsample, Tensor? residual) -> Tensor", _conv3x3_fused, _conv3x3_fused_fake)
-conv3x3_fused_out = _define("conv3x3_fused_out(Tensor x, Tensor wpack, int cout, Tensor? scale, Tensor? shift, bool glu, "
-                            "bool upsample, Tensor? residual, Tensor(a!) out) -> ()", _conv3x3_fused_out,
-                            lambda *a: None)
+def _caller(f):
+    """`f`'s operators behind ONE signature, for the callers that hold ops.conv3x3_form's answer: into `out` (a channel-slice view)
+    where one is given.  Built once per form; the operators are looked up in this module by name at each call."""
+    g, op, op_out, op_plain = globals(), f.op, f.op + "_out", f.op_plain
+    if f.up:
+        def call(x, pack, cout, scale, shift, glu=False, upsample=True, residual=None, out=None):
+            assert residual is None
+            if not glu:
+                return g[op_plain](x, pack, cout, scale, shift, False)
+            if out is None:
+                return g[op](x, pack, cout, scale, shift)
+            g[op_out](x, pack, cout, scale, shift, out)
+            return out
+    elif f.tail == "epi,up":
+        def call(x, pack, cout, scale, shift, glu=False, upsample=False, residual=None, out=None):
+            if out is None:
+                return g[op](x, pack, cout, scale, shift, glu, upsample, residual)
+            g[op_out](x, pack, cout, scale, shift, glu, upsample, residual, out)
+            return out
+    else:
+        def call(x, pack, cout, scale, shift, glu=False, upsample=False, residual=None, out=None):
+            if out is None:
+                return g[op](x, pack, cout, scale, shift, glu, residual)
+            g[op_out](x, pack, cout, scale, shift, glu, residual, out)
+            return out
+    return call
 
 
-# ------------------------------------------------------------------------------------------------ Winograd conv3x3
-def _conv3x3_wino(x, upack, cout, scale, shift, glu, residual):
-    return ops.conv3x3_wino(x, upack, cout, scale, shift, glu=glu, residual=residual)
+# form -> f(x, pack, cout, scale, shift, glu, upsample, residual, out): the layer on that kernel form
+CONV3X3 = {f.name: _caller(f) for f in ops.FORMS.values()}
 
 
-def _conv3x3_wino_out(x, upack, cout, scale, shift, glu, residual, out):
-    ops.conv3x3_wino(x, upack, cout, scale, shift, glu=glu, residual=residual, out=out)
+_STATS_OP = {f.name: f.op + "_stats" for f in ops.FORMS.values() if f.stats is not None}
 
 
-def _wino_stats_fake(x, upack, cout):
-    n = ops.wino_stats_nslots(x.shape[0], x.shape[2], x.shape[3], cout)
-    return x.new_empty(x.shape[0], cout, x.shape[2], x.shape[3]), x.new_empty(cout, n, 2)
-
-
-conv3x3_wino_stats = _define("conv3x3_wino_stats(Tensor x, Tensor upack, int cout) -> (Tensor, Tensor)",
-                             lambda x, upack, cout: ops.conv3x3_wino_stats(x, upack, cout), _wino_stats_fake)
-conv3x3_wino = _define("conv3x3_wino(Tensor x, Tensor upack, int cout, Tensor? scale, Tensor? shift, bool glu, "
-                       "Tensor? residual) -> Tensor", _conv3x3_wino,
-                       lambda x, upack, cout, scale, shift, glu, residual:
-                       x.new_empty(x.shape[0], _co(cout, glu), x.shape[2], x.shape[3]))
-conv3x3_wino_out = _define("conv3x3_wino_out(Tensor x, Tensor upack, int cout, Tensor? scale, Tensor? shift, bool glu, "
-                           "Tensor? residual, Tensor(a!) out) -> ()", _conv3x3_wino_out, lambda *a: None)
-
-
-def _wino4_stats_fake(x, upack, cout):
-    n = ops.wino4_stats_nslots(x.shape[0], x.shape[2], x.shape[3], cout)
-    return x.new_empty(x.shape[0], cout, x.shape[2], x.shape[3]), x.new_empty(cout, n, 2)
-
-
-conv3x3_wino4_stats = _define("conv3x3_wino4_stats(Tensor x, Tensor upack, int cout) -> (Tensor, Tensor)",
-                              lambda x, upack, cout: ops.conv3x3_wino4_stats(x, upack, cout), _wino4_stats_fake)
-conv3x3_wino4 = _define("conv3x3_wino4(Tensor x, Tensor upack, int cout, Tensor? scale, Tensor? shift, bool glu, "
-                        "Tensor? residual) -> Tensor",
-                        lambda x, upack, cout, scale, shift, glu, residual:
-                        ops.conv3x3_wino4(x, upack, cout, scale, shift, glu=glu, residual=residual),
-                        lambda x, upack, cout, scale, shift, glu, residual:
-                        x.new_empty(x.shape[0], _co(cout, glu), x.shape[2], x.shape[3]))
-conv3x3_wino4_out = _define("conv3x3_wino4_out(Tensor x, Tensor upack, int cout, Tensor? scale, Tensor? shift, bool glu, "
-                            "Tensor? residual, Tensor(a!) out) -> ()",
-                            lambda x, upack, cout, scale, shift, glu, residual, out:
-                            (ops.conv3x3_wino4(x, upack, cout, scale, shift, glu=glu, residual=residual, out=out), None)[1],
-                            lambda *a: None)
-
-
-pack_wino4w_weight = _define("pack_wino4w_weight(Tensor w, bool glu, bool dgrad) -> Tensor",
-                             lambda w, g, d: ops.pack_wino4w_weight(w, glu=g, dgrad=d),
-                             lambda w, g, d: w.new_empty(((w.shape[0 if d else 1] + 3) // 4) * 144 * w.shape[1 if d else 0]))
-
-
-def _wino4w_stats_fake(x, upack, cout):
-    n = ops.wino4_stats_nslots(x.shape[0], x.shape[2], x.shape[3], cout, wide=True)
-    return x.new_empty(x.shape[0], cout, x.shape[2], x.shape[3]), x.new_empty(cout, n, 2)
-
-
-conv3x3_wino4w_stats = _define("conv3x3_wino4w_stats(Tensor x, Tensor upack, int cout) -> (Tensor, Tensor)",
-                               lambda x, upack, cout: ops.conv3x3_wino4_stats(x, upack, cout, wide=True), _wino4w_stats_fake)
-conv3x3_wino4w = _define("conv3x3_wino4w(Tensor x, Tensor upack, int cout, Tensor? scale, Tensor? shift, bool glu, "
-                         "Tensor? residual) -> Tensor",
-                         lambda x, upack, cout, scale, shift, glu, residual:
-                         ops.conv3x3_wino4(x, upack, cout, scale, shift, glu=glu, residual=residual, wide=True),
-                         lambda x, upack, cout, scale, shift, glu, residual:
-                         x.new_empty(x.shape[0], _co(cout, glu), x.shape[2], x.shape[3]))
-conv3x3_wino4w_out = _define("conv3x3_wino4w_out(Tensor x, Tensor upack, int cout, Tensor? scale, Tensor? shift, bool glu, "
-                             "Tensor? residual, Tensor(a!) out) -> ()",
-                             lambda x, upack, cout, scale, shift, glu, residual, out:
-                             (ops.conv3x3_wino4(x, upack, cout, scale, shift, glu=glu, residual=residual, out=out, wide=True), None)[1],
-                             lambda *a: None)
-
-
-# ------------------------------------------------------------------------------------------------ upBlock forms
-def _up_fake(x, pack, cout, scale, shift):
-    return x.new_empty(x.shape[0], cout // 2, 2 * x.shape[2], 2 * x.shape[3])
-
-
-upwino4_glu = _define("upwino4_glu(Tensor x, Tensor upack, int cout, Tensor scale, Tensor shift) -> Tensor",
-                      lambda x, p, cout, s, t: ops.upwino4_glu(x, p, cout, s, t), _up_fake)
-upwino4_glu_out = _define("upwino4_glu_out(Tensor x, Tensor upack, int cout, Tensor scale, Tensor shift, Tensor(a!) out) -> ()",
-                          lambda x, p, cout, s, t, out: (ops.upwino4_glu(x, p, cout, s, t, out=out), None)[1], lambda *a: None)
-pack_upwino4_weight = _define("pack_upwino4_weight(Tensor w, bool glu) -> Tensor", lambda w, g: ops.pack_upwino4_weight(w, glu=g),
-                              lambda w, g: w.new_empty(((w.shape[1] + 3) // 4) * 112 * w.shape[0]))
-upwino_glu = _define("upwino_glu(Tensor x, Tensor upack, int cout, Tensor scale, Tensor shift) -> Tensor",
-                     lambda x, p, cout, s, t: ops.upwino_glu(x, p, cout, s, t), _up_fake)
-upwino_glu_out = _define("upwino_glu_out(Tensor x, Tensor upack, int cout, Tensor scale, Tensor shift, Tensor(a!) out) -> ()",
-                         lambda x, p, cout, s, t, out: (ops.upwino_glu(x, p, cout, s, t, out=out), None)[1], lambda *a: None)
-upconv3x3_glu = _define("upconv3x3_glu(Tensor x, Tensor wpack, int cout, Tensor scale, Tensor shift) -> Tensor",
-                        lambda x, p, cout, s, t: ops.upconv3x3_glu(x, p, cout, s, t), _up_fake)
-upconv3x3_glu_out = _define("upconv3x3_glu_out(Tensor x, Tensor wpack, int cout, Tensor scale, Tensor shift, "
-                            "Tensor(a!) out) -> ()",
-                            lambda x, p, cout, s, t, out: (ops.upconv3x3_glu(x, p, cout, s, t, out=out), None)[1],
-                            lambda *a: None)
+def conv3x3_stats(form, x, pack, cout):
+    """`form`'s raw convolution with BatchNorm's partial sums in its epilogue: (raw, stat_partial)."""
+    return globals()[_STATS_OP[form]](x, pack, cout)
 
 
 # ------------------------------------------------------------------------------------------------ word attention
@@ -301,19 +284,6 @@ conv3x3_gemm_wgrad_out = _define("conv3x3_gemm_wgrad_out(Tensor dy, Tensor x, Te
                                  lambda dy, x, dw: (ops.conv3x3_gemm_wgrad(dy, x, out=dw), None)[1], lambda *a: None)
 conv4x4s2_wgrad_out = _define("conv4x4s2_wgrad_out(Tensor dy, Tensor x, Tensor(a!) dw) -> ()",
                               lambda dy, x, dw: (ops.conv4x4s2_wgrad(dy, x, out=dw), None)[1], lambda *a: None)
-pack_conv3x3_weight = _define("pack_conv3x3_weight(Tensor w, bool dgrad) -> Tensor", lambda w, d: ops.pack_conv3x3_weight(w, dgrad=d),
-                              lambda w, d: w.new_empty(((w.shape[0 if d else 1] + 3) // 4) * 36 * w.shape[1 if d else 0]))
-pack_wino_weight = _define("pack_wino_weight(Tensor w, bool glu, bool dgrad) -> Tensor",
-                           lambda w, g, d: ops.pack_wino_weight(w, glu=g, dgrad=d),
-                           lambda w, g, d: w.new_empty(((w.shape[0 if d else 1] + 3) // 4) * 64 * w.shape[1 if d else 0]))
-pack_wino4_weight = _define("pack_wino4_weight(Tensor w, bool glu, bool dgrad) -> Tensor",
-                            lambda w, g, d: ops.pack_wino4_weight(w, glu=g, dgrad=d),
-                            lambda w, g, d: w.new_empty(((w.shape[0 if d else 1] + 3) // 4) * 144 * w.shape[1 if d else 0]))
-pack_upwino_weight = _define("pack_upwino_weight(Tensor w, bool glu) -> Tensor", lambda w, g: ops.pack_upwino_weight(w, glu=g),
-                             lambda w, g: w.new_empty(((w.shape[1] + 3) // 4) * (w.shape[0] // 64) * 2304))
-upwino = _define("upwino(Tensor x, Tensor upack, int cout, Tensor? scale, Tensor? shift, bool glu) -> Tensor",
-                 lambda x, p, cout, s, t, glu: ops.upwino_glu(x, p, cout, s, t, glu=glu),
-                 lambda x, p, cout, s, t, glu: x.new_empty(x.shape[0], cout // 2 if glu else cout, 2 * x.shape[2], 2 * x.shape[3]))
 
 
 # ------------------------------------------------------------------------------------------------ word attention backward

@@ -2,6 +2,7 @@
 torch's current HIP stream.  PyTorch is plumbing here (device memory + streams); the arithmetic is in
 libtgsr_hip.so.  No function in this file computes on the CPU or through eager torch ops.
 """
+import collections
 import ctypes
 import functools
 import os
@@ -83,43 +84,160 @@ def _nchw_bstride(t: torch.Tensor, name: str) -> Tuple[torch.Tensor, int]:
     return t, C * H * W
 
 
+# ----------------------------------------------------------------------------------------- the conv3x3 kernel forms
+# Everything the host side knows about a kernel form the fp32 generator's 3x3 convolutions run on is one row here; the
+# launcher (_conv3x3), the packer (pack_weight), the router (conv3x3_form) and the operator definitions of custom_ops.py read it.
+#   what        the public wrapper below that launches it (named in error messages);  op: its torch.ops.tgsr operator (`op`_out
+#               writes into a view;  op_plain: the un-gated operator of training;  pack_op: the pack operator)
+#   fwd         C entry point;  fwd_plain: the entry without the gate where that is another function;  tail: what the entry takes
+#               after (out, batch stride): "epi,up" / "epi" (those two also take a residual in front of out), "glu" or ""
+#   stats, nslots   the raw convolution whose epilogue leaves BatchNorm's partial sums, and its slot count (training)
+#   pack, pack_dgrad, elems   the pack of a [Cout,Cin,3,3] weight, of its data-gradient conv, and the packed size;  pack_arg: what
+#               they take after (Cout, Cin): "k" the kernel size (all three), "glu" the gate flag (pack only), "" nothing
+#   up          the nearest x2 up-sampling is part of the kernel;  gate_only: it has the GLU epilogue only
+#   kernel      the name it reports to `profile`
+#   shape(cin, cout, H, W)   the shapes the kernel takes (H x W of the input)
+#   align       out / residual must start on this many bytes with batch strides that keep every image there (x: always 16 where
+#               a form has a requirement at all; 0: the kernel takes any address)
+Form = collections.namedtuple("Form", "name what op op_plain pack_op fwd fwd_plain tail stats nslots pack pack_dgrad elems pack_arg "
+                                      "up gate_only kernel shape align")
+
+
+def _wino4_shape(cin, cout, H, W):
+    return cout % 64 == 0 and cin % 4 == 0 and W % 64 == 0 and H % 8 == 0            # whole workgroup tiles
+
+
+def _wino4_form(cin: int) -> str:
+    """Which of the two F(4x4) forms a layer that goes there takes: the register-fed one where the layer has an even number of
+    4-channel stages, else the LDS-fed one."""
+    return "wino4w" if cin % 8 == 0 else "wino4"
+
+
+FORMS = {f.name: f for f in (
+    Form("direct", "conv3x3_fused", "conv3x3_fused", None, "pack_conv3x3_weight", "tgsr_conv3x3_fwd", None, "epi,up", None, None,
+         "tgsr_pack_conv_weight", "tgsr_pack_conv_weight_dgrad", "tgsr_packed_weight_elems", "k",
+         False, False, "conv3x3_mfma_kernel", lambda cin, cout, H, W: True, 0),
+    Form("wino", "conv3x3_wino", "conv3x3_wino", None, "pack_wino_weight", "tgsr_wino_conv3x3_fwd", None, "epi",
+         "tgsr_wino_conv3x3_stats_fwd", "tgsr_wino_stats_nslots",
+         "tgsr_pack_wino_weight", "tgsr_pack_wino_weight_dgrad", "tgsr_packed_wino_weight_elems", "glu",
+         False, False, "wino_conv3x3_kernel", lambda cin, cout, H, W: cout % 32 == 0 and cin % 4 == 0 and W % 4 == 0, 8),
+    # F(4x4, 3x3), LDS-fed
+    Form("wino4", "conv3x3_wino4", "conv3x3_wino4", None, "pack_wino4_weight", "tgsr_wino4_conv3x3_fwd", None, "epi",
+         "tgsr_wino4_conv3x3_stats_fwd", "tgsr_wino4_stats_nslots",
+         "tgsr_pack_wino4_weight", "tgsr_pack_wino4_weight_dgrad", "tgsr_packed_wino4_weight_elems", "glu",
+         False, False, "wino4_conv3x3_kernel", _wino4_shape, 16),
+    # F(4x4, 3x3), register-fed: 128-row groups where Cout % 128 == 0, else 64-row groups in 4-wave workgroups; its pack has the size
+    # of wino4's in another order
+    Form("wino4w", "conv3x3_wino4", "conv3x3_wino4w", None, "pack_wino4w_weight", "tgsr_wino4_wide_conv3x3_fwd", None, "epi",
+         "tgsr_wino4_wide_conv3x3_stats_fwd", "tgsr_wino4_wide_stats_nslots",
+         "tgsr_pack_wino4_wide_weight", "tgsr_pack_wino4_wide_weight_dgrad", "tgsr_packed_wino4_weight_elems", "glu",
+         False, False, "wino4w_conv3x3_kernel", lambda cin, cout, H, W: _wino4_shape(cin, cout, H, W) and _wino4_form(cin) == "wino4w", 16),
+    # the upBlock forms: sub-pixel (four 2x2 convs on the pre-upsample tensor), Winograd F(2x2) and F(4x4) on the up-sampled grid
+    Form("upconv", "upconv3x3_glu", "upconv3x3_glu", None, None, "tgsr_upconv3x3_glu_fwd", None, "", None, None,
+         "tgsr_pack_upconv_weight", None, "tgsr_packed_upconv_weight_elems", "",
+         True, True, "upconv_glu_mfma_kernel", lambda cin, cout, H, W: cout % 64 == 0, 0),
+    Form("upwino", "upwino_glu", "upwino_glu", "upwino", "pack_upwino_weight", "tgsr_upwino_glu_fwd", "tgsr_upwino_fwd", "", None, None,
+         "tgsr_pack_upwino_weight", None, "tgsr_packed_upwino_weight_elems", "glu",
+         True, False, "upwino_glu_kernel", lambda cin, cout, H, W: cout % 64 == 0 and cin % 4 == 0 and W % 4 == 0, 8),
+    Form("upwino4", "upwino4_glu", "upwino4_glu", None, "pack_upwino4_weight", "tgsr_upwino4_fwd", None, "glu", None, None,
+         "tgsr_pack_upwino4_weight", None, "tgsr_packed_upwino4_weight_elems", "glu",
+         True, False, "upwino4_kernel",                        # an even number of 4-channel stages, whole 4 x 64 OUTPUT tiles
+         lambda cin, cout, H, W: cout % 64 == 0 and cin % 8 == 0 and (2 * W) % 64 == 0 and (2 * H) % 4 == 0, 16),
+)}
+
+
 # ----------------------------------------------------------------------------------------- weight prep
 @functools.lru_cache(maxsize=None)
-def _pack_elems(kind: str, cout: int, cin: int) -> int:
-    L = _lib.lib()
-    return int({"conv": lambda: L.tgsr_packed_weight_elems(cout, cin, 3), "wino": lambda: L.tgsr_packed_wino_weight_elems(cout, cin),
-                "wino4": lambda: L.tgsr_packed_wino4_weight_elems(cout, cin),
-                "upconv": lambda: L.tgsr_packed_upconv_weight_elems(cout, cin),
-                "upwino": lambda: L.tgsr_packed_upwino_weight_elems(cout, cin),
-                "upwino4": lambda: L.tgsr_packed_upwino4_weight_elems(cout, cin)}[kind]())
+def packed_elems(form: str, cout: int, cin: int) -> int:
+    """Floats in form `form`'s pack of a [cout, cin, 3, 3] weight (the library's own count)."""
+    f = FORMS[form]
+    fn = getattr(_lib.lib(), f.elems)
+    return int(fn(cout, cin, 3) if f.pack_arg == "k" else fn(cout, cin))
 
 
-def _check_pack(what: str, kind: str, pack: torch.Tensor, cout: int, cin: int):
-    """The kernels walk the packed filter by (Cout, Cin of the INPUT): a pack made for another channel count would be
-    read past its end.  torch raises a shape error for the same mistake (weight [Cout, Cin', 3, 3] on a Cin-channel
-    input); so does this."""
-    if pack.numel() != _pack_elems(kind, cout, cin):
-        raise TgsrError("%s: the packed weight holds %d values, not the %d of a [%d, %d, 3, 3] filter - the input has %d "
-                        "channels, the weight was packed for another count" % (what, pack.numel(), _pack_elems(kind, cout, cin),
-                                                                              cout, cin, cin))
+def _bad_pack(what: str, form: str, pack: torch.Tensor, cout: int, cin: int):
+    """The kernels walk the packed filter by (Cout, Cin of the INPUT): a pack made for another channel count (its size is not
+    packed_elems) would be read past its end.  torch raises a shape error for the same mistake (weight [Cout, Cin', 3, 3] on a
+    Cin-channel input); so does this."""
+    raise TgsrError("%s: the packed weight holds %d values, not the %d of a [%d, %d, 3, 3] filter - the input has %d "
+                    "channels, the weight was packed for another count" % (what, pack.numel(), packed_elems(form, cout, cin),
+                                                                          cout, cin, cin))
 
 
-def pack_conv3x3_weight(w: torch.Tensor, dgrad: bool = False, out: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """[Cout,Cin,3,3] -> the [ceil(Cin/4)][9][4][Cout] stream order of tgsr_conv3x3_fwd.  `dgrad`: w is the forward
-    conv's weight and the pack is of its data-gradient conv (in/out swapped, taps flipped) - no flip/transpose copies."""
+def _pack_out(out, n, dev):
+    """A pack's destination: fresh, or the caller's persistent buffer (autograd.PackCache re-packs in place)."""
+    if out is None:
+        return torch.empty(n, dtype=torch.float32, device=dev)
+    if out.numel() != n or out.dtype != torch.float32 or out.device != dev or not out.is_contiguous():
+        raise TgsrError("pack: out %s %s does not hold %d floats" % (tuple(out.shape), out.dtype, n))
+    return out
+
+
+def pack_weight(form: str, w: torch.Tensor, glu: bool = False, dgrad: bool = False, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The pack of `w` [Cout,Cin,3,3] for kernel form `form` (a key of FORMS).  `glu` must match the epilogue the pack is used
+    with (the Winograd packs group value channels with their gate channels).  `dgrad`: w is the forward conv's weight and the
+    pack is of its data-gradient conv (in/out swapped, taps flipped: the pack kernels read it so - no flip/transpose copies)."""
+    f = FORMS[form]
     _need_hip(w)
     w = _f32(w.detach(), "weight").contiguous()
     Cout, Cin, K, K2 = w.shape
     assert K == 3 and K2 == 3
+    name = f.pack
     if dgrad:
-        Cout, Cin = Cin, Cout
-    L = _lib.lib()
-    out = _pack_out(out, L.tgsr_packed_weight_elems(Cout, Cin, 3), w.device)
-    if dgrad:
-        check(L.tgsr_pack_conv_weight_dgrad(_p(w), _p(out), Cout, Cin, 3, _stream()), "tgsr_pack_conv_weight_dgrad")
+        assert not glu
+        if f.pack_dgrad is None:
+            raise TgsrError("pack_weight: the %s form has no data-gradient pack" % form)
+        Cout, Cin, name = Cin, Cout, f.pack_dgrad
+    fn = getattr(_lib.lib(), name)
+    out = _pack_out(out, packed_elems(form, Cout, Cin), w.device)
+    if f.pack_arg == "k":
+        rc = fn(_p(w), _p(out), Cout, Cin, 3, _stream())
+    elif f.pack_arg == "glu" and not dgrad:
+        rc = fn(_p(w), _p(out), Cout, Cin, 1 if glu else 0, _stream())
     else:
-        check(L.tgsr_pack_conv_weight(_p(w), _p(out), Cout, Cin, 3, _stream()), "tgsr_pack_conv_weight")
+        rc = fn(_p(w), _p(out), Cout, Cin, _stream())
+    check(rc, name)
     return out
+
+
+def pack_conv3x3_weight(w: torch.Tensor, dgrad: bool = False, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """[Cout,Cin,3,3] -> the [ceil(Cin/4)][9][4][Cout] stream order of tgsr_conv3x3_fwd.  `dgrad`: see pack_weight."""
+    return pack_weight("direct", w, False, dgrad, out)
+
+
+def pack_wino_weight(w: torch.Tensor, glu: bool = False, dgrad: bool = False, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """[Cout,Cin,3,3] -> Winograd F(2x2,3x3) transformed weights [ceil(Cin/8)][Cout/64][16 pos][8][64].  `glu`, `dgrad`: see
+    pack_weight."""
+    return pack_weight("wino", w, glu, dgrad, out)
+
+
+def pack_wino4_weight(w: torch.Tensor, glu: bool = False, dgrad: bool = False, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """[Cout,Cin,3,3] -> Winograd F(4x4,3x3) transformed weights [Cin/4][Cout/64][9 quads][4 ci][64 rows][4] (U = G g G^T in
+    double, rounded once).  `glu`, `dgrad`: see pack_weight."""
+    return pack_weight("wino4", w, glu, dgrad, out)
+
+
+def pack_wino4w_weight(w: torch.Tensor, glu: bool = False, dgrad: bool = False, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The pack of the register-fed F(4x4,3x3) kernel: per-wave fragment order [Cin/4][groups][8 | 4 blocks][9 quads][64 lanes][4]
+    (128-row groups where Cout % 128 == 0, else 64-row groups) - not interchangeable with pack_wino4_weight's.  `glu`, `dgrad`: see pack_weight."""
+    return pack_weight("wino4w", w, glu, dgrad, out)
+
+
+def pack_upconv_weight(w: torch.Tensor) -> torch.Tensor:
+    """[Cout,Cin,3,3] -> [ceil(Cin/4)][4 phases][4 taps][4][Cout] with the sub-pixel tap sums (tgsr_upconv3x3_glu_fwd)."""
+    return pack_weight("upconv", w)
+
+
+def pack_upwino_weight(w: torch.Tensor, glu: bool = True, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """[Cout,Cin,3,3] -> the 9 tap-sum positions of the up-sample-aware Winograd form (tgsr_upwino_glu_fwd; glu=False:
+    the layout of tgsr_upwino_fwd)."""
+    return pack_weight("upwino", w, glu, False, out)
+
+
+def pack_upwino4_weight(w: torch.Tensor, glu: bool = True, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """[Cout,Cin,3,3] -> the 25 live positions of the up-sample-aware F(4x4,3x3) form (tgsr_upwino4_fwd), the -1/3 factors of
+    the fifth transformed row / column folded in; computed in double, rounded once."""
+    return pack_weight("upwino4", w, glu, False, out)
 
 
 def bn_fold(weight, bias, running_mean, running_var, eps: float = BN_EPS):
@@ -134,108 +252,7 @@ def bn_fold(weight, bias, running_mean, running_var, eps: float = BN_EPS):
     return scale, shift
 
 
-# ----------------------------------------------------------------------------------------- convolutions
-def conv3x3_fused(x: torch.Tensor, wpack: torch.Tensor, cout: int, scale: Optional[torch.Tensor],
-                  shift: Optional[torch.Tensor], glu: bool = False, upsample: bool = False,
-                  residual: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """conv3x3 [+nearest x2 in front] + per-channel affine + (GLU | residual add) in one launch.
-    `out` may be a channel-slice view of a wider buffer (dense C,H,W block, any batch stride)."""
-    _need_hip(x, wpack, scale, shift, residual, out)
-    x, xbs = _nchw_bstride(_f32(x, "x"), "x")
-    B, Cin, H, W = x.shape
-    _check_pack("conv3x3_fused", "conv", wpack, cout, Cin)
-    Ho, Wo = (2 * H, 2 * W) if upsample else (H, W)
-    co = cout // 2 if glu else cout
-    if out is None:
-        out = torch.empty(B, co, Ho, Wo, dtype=torch.float32, device=x.device)
-    if tuple(out.shape) != (B, co, Ho, Wo) or out.stride(3) != 1 or out.stride(2) != Wo or out.stride(1) != Ho * Wo:
-        raise TgsrError("conv3x3_fused: bad `out` shape/strides %s %s" % (tuple(out.shape), out.stride()))
-    obs = out.stride(0) if B > 1 else co * Ho * Wo
-    rbs = 0
-    if residual is not None:
-        if glu:
-            raise TgsrError("conv3x3_fused: residual with GLU is not a reference pattern")
-        residual, rbs = _nchw_bstride(_f32(residual, "residual"), "residual")
-        if tuple(residual.shape) != (B, co, Ho, Wo):
-            raise TgsrError("conv3x3_fused: residual shape %s" % (tuple(residual.shape),))
-    e0 = _ev() if profile is not None else None
-    rc = _lib.lib().tgsr_conv3x3_fwd(_p(x), xbs, B, Cin, H, W, _p(wpack), cout, _p(scale), _p(shift), _p(residual), rbs,
-                                     _p(out), obs, _lib.EPI_AFFINE_GLU if glu else _lib.EPI_AFFINE,
-                                     1 if upsample else 0, _stream())
-    check(rc, "tgsr_conv3x3_fwd")
-    if profile is not None:
-        nbytes = 4 * (B * Cin * H * W + B * co * Ho * Wo * (2 if residual is not None else 1) + cout * Cin * 9)
-        profile.append(("conv3x3_mfma_kernel", 2.0 * B * Ho * Wo * cout * Cin * 9, nbytes, e0, _ev()))
-    return out
-
-
-def _pack_out(out, n, dev):
-    """A pack's destination: fresh, or the caller's persistent buffer (autograd.PackCache re-packs in place)."""
-    if out is None:
-        return torch.empty(n, dtype=torch.float32, device=dev)
-    if out.numel() != n or out.dtype != torch.float32 or out.device != dev or not out.is_contiguous():
-        raise TgsrError("pack: out %s %s does not hold %d floats" % (tuple(out.shape), out.dtype, n))
-    return out
-
-
-def pack_wino_weight(w: torch.Tensor, glu: bool = False, dgrad: bool = False, out: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """[Cout,Cin,3,3] -> Winograd F(2x2,3x3) transformed weights [ceil(Cin/8)][Cout/64][16 pos][8][64]; `glu` must
-    match the epilogue the pack is used with (it groups value channels with their gate channels).  `dgrad`: w is the
-    forward conv's weight, the pack is of its data-gradient conv (see pack_conv3x3_weight)."""
-    _need_hip(w)
-    w = _f32(w.detach(), "weight").contiguous()
-    Cout, Cin = w.shape[0], w.shape[1]
-    if dgrad:
-        Cout, Cin = Cin, Cout
-    L = _lib.lib()
-    out = _pack_out(out, L.tgsr_packed_wino_weight_elems(Cout, Cin), w.device)
-    if dgrad:
-        assert not glu
-        check(L.tgsr_pack_wino_weight_dgrad(_p(w), _p(out), Cout, Cin, _stream()), "tgsr_pack_wino_weight_dgrad")
-    else:
-        check(L.tgsr_pack_wino_weight(_p(w), _p(out), Cout, Cin, 1 if glu else 0, _stream()), "tgsr_pack_wino_weight")
-    return out
-
-
-def wino_supported(x: torch.Tensor, cout: int, out: Optional[torch.Tensor] = None,
-                   residual: Optional[torch.Tensor] = None) -> bool:
-    """Shapes the Winograd kernel takes: Cout % 32 == 0, Cin % 4 == 0, width % 4 == 0, x planes 16-byte aligned,
-    out / residual 8-byte aligned with even batch strides."""
-    if not (x.dim() == 4 and cout % 32 == 0 and x.shape[1] % 4 == 0 and x.shape[3] % 4 == 0 and
-            x.data_ptr() % 16 == 0 and (x.shape[0] == 1 or x.stride(0) % 4 == 0)):
-        return False
-    for t in (out, residual):
-        if t is not None and (t.data_ptr() % 8 != 0 or (t.shape[0] > 1 and t.stride(0) % 2 != 0)):
-            return False
-    return True
-
-
-def conv3x3_wino(x: torch.Tensor, upack: torch.Tensor, cout: int, scale, shift, glu: bool = False,
-                 residual: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """conv3x3 + affine + (GLU | residual) by Winograd F(2x2,3x3) (same contract as conv3x3_fused, no upsample)."""
-    _need_hip(x, upack, scale, shift, residual, out)
-    x, xbs = _nchw_bstride(_f32(x, "x"), "x")
-    B, Cin, H, W = x.shape
-    _check_pack("conv3x3_wino", "wino", upack, cout, Cin)
-    co = cout // 2 if glu else cout
-    if out is None:
-        out = torch.empty(B, co, H, W, dtype=torch.float32, device=x.device)
-    if tuple(out.shape) != (B, co, H, W) or out.stride(3) != 1 or out.stride(2) != W or out.stride(1) != H * W:
-        raise TgsrError("conv3x3_wino: bad `out` shape/strides %s %s" % (tuple(out.shape), out.stride()))
-    obs = out.stride(0) if B > 1 else co * H * W
-    rbs = 0
-    if residual is not None:
-        residual, rbs = _nchw_bstride(_f32(residual, "residual"), "residual")
-    e0 = _ev() if profile is not None else None
-    rc = _lib.lib().tgsr_wino_conv3x3_fwd(_p(x), xbs, B, Cin, H, W, _p(upack), cout, _p(scale), _p(shift), _p(residual),
-                                          rbs, _p(out), obs, _lib.EPI_AFFINE_GLU if glu else _lib.EPI_AFFINE, _stream())
-    check(rc, "tgsr_wino_conv3x3_fwd")
-    if profile is not None:
-        nbytes = 4 * (B * Cin * H * W + B * co * H * W * (2 if residual is not None else 1) + cout * Cin * 9)
-        profile.append(("wino_conv3x3_kernel", 2.0 * B * H * W * cout * Cin * 9, nbytes, e0, _ev()))
-    return out
-
-
+# ----------------------------------------------------------------------------------------- routing
 WINO4_MIN_PIXELS = 64 * 64        # per image; profiles/HISTORY.md 3.1e: the error study that keeps F(4x4) off the 32 x 32 layers
 WINO4_MIN_PIXELS_64 = 128 * 128   # pixels per image from which layers with 64-channel groups only may use F(4x4) too
 # The up-sample-aware F(4x4) form must keep +-1 among its interpolation points (its 25-of-36 structure depends on them,
@@ -278,14 +295,14 @@ def wino4_wanted(cin: int, cout: int, H: int, W: int, B: int = 16) -> bool:
     Numerics (profiles/HISTORY.md 3.1e / 3.1g; tests/test_hip_parity.py::test_fp32_parity_margin_*): layers of >= 128 x 128
     pixels; at 64 x 64 .. 128 x 128 only the convolutions with 128-channel groups; nothing below 64 x 64 (the early, small layers
     are the ones whose error the rest of the network amplifies).
-    Work: >= 256 workgroups of the form the layer takes - register-fed (Cin % 8 == 0): 4 x 64 pixels x 128 rows, or x 64 rows
+    Work: >= 256 workgroups of the form the layer takes (`_wino4_form`) - register-fed: 4 x 64 pixels x 128 rows, or x 64 rows
     where Cout % 128 != 0; else the LDS-fed form, 8 x 64 x 64 (measured at batch 4 .. 32: each routed layer faster than on
     F(2x2), each unrouted one slower; the batch-2 golden case stays on F(2x2) except for the last upBlocks).
     `ROUTING` holds the switches (environment, read at import)."""
     R = ROUTING
     if not R.wino4:
         return False
-    if not (cout % 64 == 0 and cin % 4 == 0 and W % 64 == 0 and H % 8 == 0 and H * W >= WINO4_MIN_PIXELS):
+    if not (_wino4_shape(cin, cout, H, W) and H * W >= WINO4_MIN_PIXELS):
         return False
     if cin < R.min_cin or H * W < R.min_pixels:          # diagnostics
         return False
@@ -293,213 +310,11 @@ def wino4_wanted(cin: int, cout: int, H: int, W: int, B: int = 16) -> bool:
         return False
     if R.pin_batch:
         B = R.pin_batch
-    if cin % 8 == 0:
+    if _wino4_form(cin) == "wino4w":
         nwg = B * (H // 4) * (W // 64) * (cout // (128 if cout % 128 == 0 else 64))
     else:
         nwg = B * (H // 8) * (W // 64) * (cout // 64)
     return nwg >= R.min_workgroups
-
-
-def pack_wino4_weight(w: torch.Tensor, glu: bool = False, dgrad: bool = False, out: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """[Cout,Cin,3,3] -> Winograd F(4x4,3x3) transformed weights [Cin/4][Cout/64][9 quads][4 ci][64 rows][4] (U = G g G^T in
-    double, rounded once); `glu` must match the epilogue the pack is used with.  `dgrad`: w is the forward conv's weight, the
-    pack is of its data-gradient conv (see pack_conv3x3_weight)."""
-    _need_hip(w)
-    w = _f32(w.detach(), "weight").contiguous()
-    Cout, Cin = w.shape[0], w.shape[1]
-    if dgrad:
-        Cout, Cin = Cin, Cout
-    L = _lib.lib()
-    out = _pack_out(out, L.tgsr_packed_wino4_weight_elems(Cout, Cin), w.device)
-    if dgrad:
-        assert not glu
-        check(L.tgsr_pack_wino4_weight_dgrad(_p(w), _p(out), Cout, Cin, _stream()), "tgsr_pack_wino4_weight_dgrad")
-    else:
-        check(L.tgsr_pack_wino4_weight(_p(w), _p(out), Cout, Cin, 1 if glu else 0, _stream()), "tgsr_pack_wino4_weight")
-    return out
-
-
-def pack_wino4w_weight(w: torch.Tensor, glu: bool = False, dgrad: bool = False, out: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """The pack of the register-fed F(4x4,3x3) kernel: per-wave fragment order [Cin/4][groups][8 | 4 blocks][9 quads][64 lanes][4]
-    (128-row groups where Cout % 128 == 0, else 64-row groups) - not interchangeable with pack_wino4_weight's.  `dgrad`: w is the
-    forward conv's weight, the pack is of its data-gradient conv."""
-    _need_hip(w)
-    w = _f32(w.detach(), "weight").contiguous()
-    Cout, Cin = w.shape[0], w.shape[1]
-    if dgrad:
-        Cout, Cin = Cin, Cout
-    L = _lib.lib()
-    out = _pack_out(out, L.tgsr_packed_wino4_weight_elems(Cout, Cin), w.device)
-    if dgrad:
-        assert not glu
-        check(L.tgsr_pack_wino4_wide_weight_dgrad(_p(w), _p(out), Cout, Cin, _stream()), "tgsr_pack_wino4_wide_weight_dgrad")
-    else:
-        check(L.tgsr_pack_wino4_wide_weight(_p(w), _p(out), Cout, Cin, 1 if glu else 0, _stream()), "tgsr_pack_wino4_wide_weight")
-    return out
-
-
-def conv3x3_wino4(x: torch.Tensor, upack: torch.Tensor, cout: int, scale, shift, glu: bool = False,
-                  residual: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None, wide: bool = False) -> torch.Tensor:
-    """conv3x3 + affine + (GLU | residual) by Winograd F(4x4,3x3) (same contract as conv3x3_wino; 16-byte aligned tensors).
-    `wide`: the register-fed form (Cin % 8 == 0), upack from pack_wino4w_weight."""
-    _need_hip(x, upack, scale, shift, residual, out)
-    x, xbs = _nchw_bstride(_f32(x, "x"), "x")
-    B, Cin, H, W = x.shape
-    _check_pack("conv3x3_wino4", "wino4", upack, cout, Cin)
-    co = cout // 2 if glu else cout
-    if out is None:
-        out = torch.empty(B, co, H, W, dtype=torch.float32, device=x.device)
-    if tuple(out.shape) != (B, co, H, W) or out.stride(3) != 1 or out.stride(2) != W or out.stride(1) != H * W:
-        raise TgsrError("conv3x3_wino4: bad `out` shape/strides %s %s" % (tuple(out.shape), out.stride()))
-    obs = out.stride(0) if B > 1 else co * H * W
-    rbs = 0
-    if residual is not None:
-        residual, rbs = _nchw_bstride(_f32(residual, "residual"), "residual")
-        if tuple(residual.shape) != (B, co, H, W):
-            raise TgsrError("conv3x3_wino4: residual shape %s" % (tuple(residual.shape),))
-    e0 = _ev() if profile is not None else None
-    fn = _lib.lib().tgsr_wino4_wide_conv3x3_fwd if wide else _lib.lib().tgsr_wino4_conv3x3_fwd
-    rc = fn(_p(x), xbs, B, Cin, H, W, _p(upack), cout, _p(scale), _p(shift), _p(residual), rbs, _p(out), obs,
-            _lib.EPI_AFFINE_GLU if glu else _lib.EPI_AFFINE, _stream())
-    check(rc, "tgsr_wino4_wide_conv3x3_fwd" if wide else "tgsr_wino4_conv3x3_fwd")
-    if profile is not None:
-        nbytes = 4 * (B * Cin * H * W + B * co * H * W * (2 if residual is not None else 1) + cout * Cin * 9)
-        profile.append(("wino4w_conv3x3_kernel" if wide else "wino4_conv3x3_kernel", 2.0 * B * H * W * cout * Cin * 9, nbytes, e0, _ev()))
-    return out
-
-
-def wino4_stats_nslots(B: int, H: int, W: int, cout: int, wide: bool = False) -> int:
-    """Partial-sum pairs per channel conv3x3_wino4_stats writes for this shape (0: unsupported)."""
-    L = _lib.lib()
-    return int((L.tgsr_wino4_wide_stats_nslots if wide else L.tgsr_wino4_stats_nslots)(int(B), int(H), int(W), int(cout)))
-
-
-def conv3x3_wino4_stats(x: torch.Tensor, upack: torch.Tensor, cout: int, wide: bool = False):
-    """conv3x3_wino_stats on the F(4x4, 3x3) kernels: (out [B,cout,H,W], stat_partial [cout, nslots, 2]).  `wide`: the
-    register-fed form (upack from pack_wino4w_weight)."""
-    _need_hip(x, upack)
-    x, xbs = _nchw_bstride(_f32(x, "x"), "x")
-    B, Cin, H, W = x.shape
-    _check_pack("conv3x3_wino4_stats", "wino4", upack, cout, Cin)
-    L = _lib.lib()
-    nslots = (L.tgsr_wino4_wide_stats_nslots if wide else L.tgsr_wino4_stats_nslots)(B, H, W, cout)
-    if nslots < 1:
-        raise TgsrError("conv3x3_wino4_stats: unsupported shape %s -> %d channels" % (tuple(x.shape), cout))
-    out = torch.empty(B, cout, H, W, dtype=torch.float32, device=x.device)
-    part = torch.empty(cout, nslots, 2, dtype=torch.float32, device=x.device)
-    e0 = _ev() if profile is not None else None
-    fn = L.tgsr_wino4_wide_conv3x3_stats_fwd if wide else L.tgsr_wino4_conv3x3_stats_fwd
-    check(fn(_p(x), xbs, B, Cin, H, W, _p(upack), cout, _p(out), cout * H * W, _p(part), _stream()),
-          "tgsr_wino4_wide_conv3x3_stats_fwd" if wide else "tgsr_wino4_conv3x3_stats_fwd")
-    if profile is not None:
-        profile.append(("wino4w_conv3x3_kernel" if wide else "wino4_conv3x3_kernel", 2.0 * B * H * W * cout * Cin * 9,
-                        4 * (B * Cin * H * W + B * cout * H * W + cout * Cin * 9), e0, _ev()))
-    return out, part
-
-
-def wino_stats_nslots(B: int, H: int, W: int, cout: int) -> int:
-    """Partial-sum pairs per channel conv3x3_wino_stats writes for this shape (0: unsupported)."""
-    return int(_lib.lib().tgsr_wino_stats_nslots(int(B), int(H), int(W), int(cout)))
-
-
-def conv3x3_wino_stats(x: torch.Tensor, upack: torch.Tensor, cout: int):
-    """The raw Winograd convolution (no affine, no residual) whose epilogue also leaves BatchNorm's batch statistics as
-    partial sums: returns (out [B,cout,H,W], stat_partial [cout, nslots, 2]) for bn_train_fwd(..., stat_partial=...)."""
-    _need_hip(x, upack)
-    x, xbs = _nchw_bstride(_f32(x, "x"), "x")
-    B, Cin, H, W = x.shape
-    _check_pack("conv3x3_wino_stats", "wino", upack, cout, Cin)
-    L = _lib.lib()
-    nslots = L.tgsr_wino_stats_nslots(B, H, W, cout)
-    if nslots < 1:
-        raise TgsrError("conv3x3_wino_stats: unsupported shape %s -> %d channels" % (tuple(x.shape), cout))
-    out = torch.empty(B, cout, H, W, dtype=torch.float32, device=x.device)
-    part = torch.empty(cout, nslots, 2, dtype=torch.float32, device=x.device)
-    e0 = _ev() if profile is not None else None
-    check(L.tgsr_wino_conv3x3_stats_fwd(_p(x), xbs, B, Cin, H, W, _p(upack), cout, _p(out), cout * H * W, _p(part), _stream()),
-          "tgsr_wino_conv3x3_stats_fwd")
-    if profile is not None:
-        profile.append(("wino_conv3x3_kernel", 2.0 * B * H * W * cout * Cin * 9,
-                        4 * (B * Cin * H * W + B * cout * H * W + cout * Cin * 9), e0, _ev()))
-    return out, part
-
-
-def pack_upconv_weight(w: torch.Tensor) -> torch.Tensor:
-    """[Cout,Cin,3,3] -> [ceil(Cin/4)][4 phases][4 taps][4][Cout] with the sub-pixel tap sums (tgsr_upconv3x3_glu_fwd)."""
-    _need_hip(w)
-    w = _f32(w.detach(), "weight").contiguous()
-    Cout, Cin = w.shape[0], w.shape[1]
-    L = _lib.lib()
-    out = torch.empty(L.tgsr_packed_upconv_weight_elems(Cout, Cin), dtype=torch.float32, device=w.device)
-    check(L.tgsr_pack_upconv_weight(_p(w), _p(out), Cout, Cin, _stream()), "tgsr_pack_upconv_weight")
-    return out
-
-
-def upconv3x3_glu(x: torch.Tensor, wpack_up: torch.Tensor, cout: int, scale, shift,
-                  out: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """upBlock in one launch by sub-pixel decomposition (4 x 2x2 convs on the pre-upsample tensor)."""
-    _need_hip(x, wpack_up, scale, shift, out)
-    x, xbs = _nchw_bstride(_f32(x, "x"), "x")
-    B, Cin, H, W = x.shape
-    _check_pack("upconv3x3_glu", "upconv", wpack_up, cout, Cin)
-    co, Ho, Wo = cout // 2, 2 * H, 2 * W
-    if out is None:
-        out = torch.empty(B, co, Ho, Wo, dtype=torch.float32, device=x.device)
-    if tuple(out.shape) != (B, co, Ho, Wo) or out.stride(3) != 1 or out.stride(2) != Wo or out.stride(1) != Ho * Wo:
-        raise TgsrError("upconv3x3_glu: bad `out` shape/strides %s %s" % (tuple(out.shape), out.stride()))
-    obs = out.stride(0) if B > 1 else co * Ho * Wo
-    e0 = _ev() if profile is not None else None
-    rc = _lib.lib().tgsr_upconv3x3_glu_fwd(_p(x), xbs, B, Cin, H, W, _p(wpack_up), cout, _p(scale), _p(shift), _p(out),
-                                           obs, _stream())
-    check(rc, "tgsr_upconv3x3_glu_fwd")
-    if profile is not None:
-        nbytes = 4 * (B * Cin * H * W + B * co * Ho * Wo + cout * Cin * 9)
-        profile.append(("upconv_glu_mfma_kernel", 2.0 * B * Ho * Wo * cout * Cin * 9, nbytes, e0, _ev()))
-    return out
-
-
-def pack_upwino_weight(w: torch.Tensor, glu: bool = True, out: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """[Cout,Cin,3,3] -> the 9 tap-sum positions of the up-sample-aware Winograd form (tgsr_upwino_glu_fwd; glu=False:
-    the layout of tgsr_upwino_fwd)."""
-    _need_hip(w)
-    w = _f32(w.detach(), "weight").contiguous()
-    Cout, Cin = w.shape[0], w.shape[1]
-    L = _lib.lib()
-    out = _pack_out(out, L.tgsr_packed_upwino_weight_elems(Cout, Cin), w.device)
-    check(L.tgsr_pack_upwino_weight(_p(w), _p(out), Cout, Cin, 1 if glu else 0, _stream()), "tgsr_pack_upwino_weight")
-    return out
-
-
-def upwino_supported(x: torch.Tensor, cout: int, out: Optional[torch.Tensor] = None) -> bool:
-    """Shapes tgsr_upwino_glu_fwd takes: Cout % 64 == 0, Cin % 4 == 0, W % 4 == 0, aligned planes."""
-    if not (x.dim() == 4 and cout % 64 == 0 and x.shape[1] % 4 == 0 and x.shape[3] % 4 == 0 and
-            x.data_ptr() % 16 == 0 and (x.shape[0] == 1 or x.stride(0) % 4 == 0)):
-        return False
-    return out is None or (out.data_ptr() % 8 == 0 and (out.shape[0] == 1 or out.stride(0) % 2 == 0))
-
-
-def upwino_glu(x: torch.Tensor, upack: torch.Tensor, cout: int, scale, shift,
-               out: Optional[torch.Tensor] = None, glu: bool = True) -> torch.Tensor:
-    """upBlock in one launch by Winograd on the up-sampled grid (9 products per 2x2 outputs); contract of upconv3x3_glu.
-    glu=False: Upsample -> conv3x3 -> affine without the gate (out [B,cout,2H,2W]; scale/shift may be None)."""
-    _need_hip(x, upack, scale, shift, out)
-    x, xbs = _nchw_bstride(_f32(x, "x"), "x")
-    B, Cin, H, W = x.shape
-    _check_pack("upwino_glu", "upwino", upack, cout, Cin)
-    co, Ho, Wo = (cout // 2 if glu else cout), 2 * H, 2 * W
-    if out is None:
-        out = torch.empty(B, co, Ho, Wo, dtype=torch.float32, device=x.device)
-    if tuple(out.shape) != (B, co, Ho, Wo) or out.stride(3) != 1 or out.stride(2) != Wo or out.stride(1) != Ho * Wo:
-        raise TgsrError("upwino_glu: bad `out` shape/strides %s %s" % (tuple(out.shape), out.stride()))
-    obs = out.stride(0) if B > 1 else co * Ho * Wo
-    e0 = _ev() if profile is not None else None
-    fn = _lib.lib().tgsr_upwino_glu_fwd if glu else _lib.lib().tgsr_upwino_fwd
-    rc = fn(_p(x), xbs, B, Cin, H, W, _p(upack), cout, _p(scale), _p(shift), _p(out), obs, _stream())
-    check(rc, "tgsr_upwino_glu_fwd" if glu else "tgsr_upwino_fwd")
-    if profile is not None:
-        nbytes = 4 * (B * Cin * H * W + B * co * Ho * Wo + cout * Cin * 9)
-        profile.append(("upwino_glu_kernel", 2.0 * B * Ho * Wo * cout * Cin * 9, nbytes, e0, _ev()))
-    return out
 
 
 def upwino4_wanted(cin: int, cout: int, H: int, W: int, B: int = 16) -> bool:
@@ -513,47 +328,191 @@ def upwino4_wanted(cin: int, cout: int, H: int, W: int, B: int = 16) -> bool:
     Ho, Wo = 2 * H, 2 * W
     if cin < R.upwino4_min_cin:                            # diagnostics: which upBlocks cost what (DESIGN 3.1f)
         return False
-    if not (cout % 64 == 0 and cin % 8 == 0 and Wo % 64 == 0 and Ho % 4 == 0 and Ho * Wo >= UPWINO4_MIN_OUT_PIXELS):
+    if not (FORMS["upwino4"].shape(cin, cout, H, W) and Ho * Wo >= UPWINO4_MIN_OUT_PIXELS):
         return False
     if R.pin_batch:
         B = R.pin_batch
     return B * (Ho // 4) * (Wo // 64) * (cout // 64) >= R.min_workgroups
 
 
-def pack_upwino4_weight(w: torch.Tensor, glu: bool = True, out: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """[Cout,Cin,3,3] -> the 25 live positions of the up-sample-aware F(4x4,3x3) form (tgsr_upwino4_fwd), the -1/3 factors of
-    the fifth transformed row / column folded in; computed in double, rounded once."""
-    _need_hip(w)
-    w = _f32(w.detach(), "weight").contiguous()
-    Cout, Cin = w.shape[0], w.shape[1]
+def _aligned(t, nbytes: int) -> bool:
+    """`t` (None: nothing to ask) starts on an `nbytes` boundary and its batch stride keeps every image on one."""
+    return t is None or (t.data_ptr() % nbytes == 0 and (t.shape[0] == 1 or t.stride(0) % (nbytes // 4) == 0))
+
+
+def _dense(t) -> bool:
+    return t is None or (t.stride(3) == 1 and t.stride(2) == t.shape[3] and t.stride(1) == t.shape[2] * t.shape[3])
+
+
+def conv3x3_form(x, cout: int, upsample: bool = False, glu: bool = False, out=None, residual=None, winograd: bool = True,
+                 training: bool = False) -> str:
+    """Which kernel form (a key of FORMS) a conv3x3 layer takes - THE routing decision; the eval-mode blocks of util.py and the
+    training blocks of autograd.py all ask here.  Host arithmetic on shapes, strides and addresses (x / out / residual need
+    `shape`, `stride()`, `data_ptr()` only); the library is not touched.
+      winograd   util.WINOGRAD (TGSR_WINOGRAD=0: the direct kernel, and the sub-pixel form for upBlocks)
+      training   the caller is autograd.py: BatchNorm's batch statistics sit between the convolution and the gate, so `glu` is
+                 False there and the gated one-launch upBlock forms (upconv, upwino4) are not available.
+    In order of preference.  Without up-sampling: F(4x4) where wino4_wanted routes the layer and every tensor is a dense NCHW block
+    on 16 bytes; F(2x2) where the kernel takes the shape and pays - always with 64-channel groups, with 32-channel groups (Cout %
+    64 != 0: 8-row workgroup tiles) only when the image gives >= 256 workgroups (measured at B=16: 32->32 @128^2 40 vs 71 us, @64^2
+    16 vs 20 us, @32^2 16 vs 13 us); else the direct kernel.  With it: an eval-mode upBlock (`glu`) with whole 64-channel groups is
+    ONE launch - Winograd on the up-sampled grid with the up-sampling folded into the input transform (upwino: 9 of 16 positions
+    survive, 2.25 multiplies per output), its F(4x4) form (25 of 36: 1.56) where upwino4_wanted routes the layer, and the
+    sub-pixel form (upconv: 4 multiplies) for what Winograd does not take; training has the un-gated upwino entry; everything
+    else up-samples inside the direct kernel."""
+    if x.dim() != 4:
+        return "direct"       # whose wrapper refuses it
+    B, cin, H, W = x.shape
+    if upsample:
+        f = FORMS["upwino"]
+        wino = winograd and f.shape(cin, cout, H, W) and _aligned(x, 16) and _aligned(out, f.align)
+        if training:
+            return "upwino" if wino else "direct"
+        if not (glu and FORMS["upconv"].shape(cin, cout, H, W)):
+            return "direct"
+        if not wino:
+            return "upconv"
+        return "upwino4" if upwino4_wanted(cin, cout, H, W, B) and _aligned(out, FORMS["upwino4"].align) else "upwino"
+    if not winograd:
+        return "direct"
+    if (wino4_wanted(cin, cout, H, W, B) and _aligned(x, 16) and _dense(x) and _aligned(out, 16) and _dense(out) and
+            _aligned(residual, 16) and _dense(residual)):
+        return _wino4_form(cin)
+    if training:
+        residual = None       # what autograd.py adds in a data-gradient conv's epilogue is a gradient it has just allocated: not asked
+    f = FORMS["wino"]
+    if (f.shape(cin, cout, H, W) and _aligned(x, 16) and _aligned(out, f.align) and _aligned(residual, f.align) and
+            (cout % 64 == 0 or B * ((W + 31) // 32) * ((H + 7) // 8) >= 256)):
+        return "wino"
+    return "direct"
+
+
+# ----------------------------------------------------------------------------------------- convolutions
+def _what(f, stats: bool) -> str:
+    """The public wrapper a launch came through, for an error message."""
+    return f.what + "_stats" if stats else f.what
+
+
+def _conv3x3(form: str, x, pack, cout: int, scale, shift, glu: bool, upsample: bool, residual, out, stats: bool = False):
+    """Validate, allocate (or check `out`), launch and bracket for `profile`: every conv3x3 form goes through here.  `stats`:
+    the form's raw convolution with BatchNorm's partial sums in the epilogue; returns (out, stat_partial [cout, nslots, 2])."""
+    f = FORMS[form]
+    if f.gate_only and not glu:
+        raise TgsrError("%s: the %s form has the GLU epilogue only" % (_what(f, stats), form))
+    _need_hip(x, pack, scale, shift, residual, out)
+    x, xbs = _nchw_bstride(_f32(x, "x"), "x")
+    B, Cin, H, W = x.shape
+    if pack.numel() != packed_elems(form, cout, Cin):
+        _bad_pack(_what(f, stats), form, pack, cout, Cin)
+    Ho, Wo = (2 * H, 2 * W) if upsample else (H, W)
+    co = cout // 2 if glu else cout
     L = _lib.lib()
-    out = _pack_out(out, L.tgsr_packed_upwino4_weight_elems(Cout, Cin), w.device)
-    check(L.tgsr_pack_upwino4_weight(_p(w), _p(out), Cout, Cin, 1 if glu else 0, _stream()), "tgsr_pack_upwino4_weight")
-    return out
+    part = None
+    if stats:
+        nslots = getattr(L, f.nslots)(B, H, W, cout)
+        if nslots < 1:
+            raise TgsrError("%s: unsupported shape %s -> %d channels" % (_what(f, stats), tuple(x.shape), cout))
+        part = torch.empty(cout, nslots, 2, dtype=torch.float32, device=x.device)
+    if out is None:
+        out = torch.empty(B, co, Ho, Wo, dtype=torch.float32, device=x.device)
+    if tuple(out.shape) != (B, co, Ho, Wo) or out.stride(3) != 1 or out.stride(2) != Wo or out.stride(1) != Ho * Wo:
+        raise TgsrError("%s: bad `out` shape/strides %s %s" % (_what(f, stats), tuple(out.shape), out.stride()))
+    obs = out.stride(0) if B > 1 else co * Ho * Wo
+    rbs = 0
+    if residual is not None:
+        if (glu and form == "direct") or not f.tail.startswith("epi"):
+            raise TgsrError("%s: residual with GLU is not a reference pattern" % _what(f, stats))
+        residual, rbs = _nchw_bstride(_f32(residual, "residual"), "residual")
+        if tuple(residual.shape) != (B, co, Ho, Wo):
+            raise TgsrError("%s: residual shape %s" % (_what(f, stats), tuple(residual.shape)))
+    e0 = _ev() if profile is not None else None
+    name = f.stats if stats else (f.fwd if glu or f.fwd_plain is None else f.fwd_plain)
+    fn = getattr(L, name)
+    if stats:
+        rc = fn(_p(x), xbs, B, Cin, H, W, _p(pack), cout, _p(out), obs, _p(part), _stream())
+    elif f.tail == "epi":
+        rc = fn(_p(x), xbs, B, Cin, H, W, _p(pack), cout, _p(scale), _p(shift), _p(residual), rbs, _p(out), obs,
+                _lib.EPI_AFFINE_GLU if glu else _lib.EPI_AFFINE, _stream())
+    elif f.tail == "epi,up":
+        rc = fn(_p(x), xbs, B, Cin, H, W, _p(pack), cout, _p(scale), _p(shift), _p(residual), rbs, _p(out), obs,
+                _lib.EPI_AFFINE_GLU if glu else _lib.EPI_AFFINE, 1 if upsample else 0, _stream())
+    elif f.tail == "glu":
+        rc = fn(_p(x), xbs, B, Cin, H, W, _p(pack), cout, _p(scale), _p(shift), _p(out), obs, 1 if glu else 0, _stream())
+    else:
+        rc = fn(_p(x), xbs, B, Cin, H, W, _p(pack), cout, _p(scale), _p(shift), _p(out), obs, _stream())
+    check(rc, name)
+    if profile is not None:
+        nbytes = 4 * (B * Cin * H * W + B * co * Ho * Wo * (2 if residual is not None else 1) + cout * Cin * 9)
+        profile.append((f.kernel, 2.0 * B * Ho * Wo * cout * Cin * 9, nbytes, e0, _ev()))
+    return (out, part) if stats else out
+
+
+def conv3x3_fused(x: torch.Tensor, wpack: torch.Tensor, cout: int, scale: Optional[torch.Tensor],
+                  shift: Optional[torch.Tensor], glu: bool = False, upsample: bool = False,
+                  residual: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """conv3x3 [+nearest x2 in front] + per-channel affine + (GLU | residual add) in one launch.
+    `out` may be a channel-slice view of a wider buffer (dense C,H,W block, any batch stride)."""
+    return _conv3x3("direct", x, wpack, cout, scale, shift, glu, upsample, residual, out)
+
+
+def conv3x3_wino(x: torch.Tensor, upack: torch.Tensor, cout: int, scale, shift, glu: bool = False,
+                 residual: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """conv3x3 + affine + (GLU | residual) by Winograd F(2x2,3x3) (same contract as conv3x3_fused, no upsample)."""
+    return _conv3x3("wino", x, upack, cout, scale, shift, glu, False, residual, out)
+
+
+def conv3x3_wino4(x: torch.Tensor, upack: torch.Tensor, cout: int, scale, shift, glu: bool = False,
+                  residual: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None, wide: bool = False) -> torch.Tensor:
+    """conv3x3 + affine + (GLU | residual) by Winograd F(4x4,3x3) (same contract as conv3x3_wino; 16-byte aligned tensors).
+    `wide`: the register-fed form (Cin a multiple of 8), upack from pack_wino4w_weight."""
+    return _conv3x3("wino4w" if wide else "wino4", x, upack, cout, scale, shift, glu, False, residual, out)
+
+
+def stats_nslots(form: str, B: int, H: int, W: int, cout: int) -> int:
+    """Partial-sum pairs per channel the `stats` entry of `form` writes for this shape (0: unsupported)."""
+    return int(getattr(_lib.lib(), FORMS[form].nslots)(int(B), int(H), int(W), int(cout)))
+
+
+def wino_stats_nslots(B: int, H: int, W: int, cout: int) -> int:
+    """stats_nslots of conv3x3_wino_stats."""
+    return stats_nslots("wino", B, H, W, cout)
+
+
+def wino4_stats_nslots(B: int, H: int, W: int, cout: int, wide: bool = False) -> int:
+    """stats_nslots of conv3x3_wino4_stats."""
+    return stats_nslots("wino4w" if wide else "wino4", B, H, W, cout)
+
+
+def conv3x3_wino_stats(x: torch.Tensor, upack: torch.Tensor, cout: int):
+    """The raw Winograd convolution (no affine, no residual) whose epilogue also leaves BatchNorm's batch statistics as
+    partial sums: returns (out [B,cout,H,W], stat_partial [cout, nslots, 2]) for bn_train_fwd(..., stat_partial=...)."""
+    return _conv3x3("wino", x, upack, cout, None, None, False, False, None, None, stats=True)
+
+
+def conv3x3_wino4_stats(x: torch.Tensor, upack: torch.Tensor, cout: int, wide: bool = False):
+    """conv3x3_wino_stats on the F(4x4, 3x3) kernels: (out [B,cout,H,W], stat_partial [cout, nslots, 2]).  `wide`: the
+    register-fed form (upack from pack_wino4w_weight)."""
+    return _conv3x3("wino4w" if wide else "wino4", x, upack, cout, None, None, False, False, None, None, stats=True)
+
+
+def upconv3x3_glu(x: torch.Tensor, wpack_up: torch.Tensor, cout: int, scale, shift,
+                  out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """upBlock in one launch by sub-pixel decomposition (4 x 2x2 convs on the pre-upsample tensor)."""
+    return _conv3x3("upconv", x, wpack_up, cout, scale, shift, True, True, None, out)
+
+
+def upwino_glu(x: torch.Tensor, upack: torch.Tensor, cout: int, scale, shift,
+               out: Optional[torch.Tensor] = None, glu: bool = True) -> torch.Tensor:
+    """upBlock in one launch by Winograd on the up-sampled grid (9 products per 2x2 outputs); contract of upconv3x3_glu.
+    glu=False: Upsample -> conv3x3 -> affine without the gate (out [B,cout,2H,2W]; scale/shift may be None)."""
+    return _conv3x3("upwino", x, upack, cout, scale, shift, glu, True, None, out)
 
 
 def upwino4_glu(x: torch.Tensor, upack: torch.Tensor, cout: int, scale, shift,
                 out: Optional[torch.Tensor] = None, glu: bool = True) -> torch.Tensor:
     """upBlock in one launch by F(4x4,3x3) on the up-sampled grid (25 products per 4x4 outputs); contract of upwino_glu with
     16-byte aligned tensors."""
-    _need_hip(x, upack, scale, shift, out)
-    x, xbs = _nchw_bstride(_f32(x, "x"), "x")
-    B, Cin, H, W = x.shape
-    _check_pack("upwino4_glu", "upwino4", upack, cout, Cin)
-    co, Ho, Wo = (cout // 2 if glu else cout), 2 * H, 2 * W
-    if out is None:
-        out = torch.empty(B, co, Ho, Wo, dtype=torch.float32, device=x.device)
-    if tuple(out.shape) != (B, co, Ho, Wo) or out.stride(3) != 1 or out.stride(2) != Wo or out.stride(1) != Ho * Wo:
-        raise TgsrError("upwino4_glu: bad `out` shape/strides %s %s" % (tuple(out.shape), out.stride()))
-    obs = out.stride(0) if B > 1 else co * Ho * Wo
-    e0 = _ev() if profile is not None else None
-    rc = _lib.lib().tgsr_upwino4_fwd(_p(x), xbs, B, Cin, H, W, _p(upack), cout, _p(scale), _p(shift), _p(out), obs,
-                                     1 if glu else 0, _stream())
-    check(rc, "tgsr_upwino4_fwd")
-    if profile is not None:
-        nbytes = 4 * (B * Cin * H * W + B * co * Ho * Wo + cout * Cin * 9)
-        profile.append(("upwino4_kernel", 2.0 * B * Ho * Wo * cout * Cin * 9, nbytes, e0, _ev()))
-    return out
+    return _conv3x3("upwino4", x, upack, cout, scale, shift, glu, True, None, out)
 
 
 def conv_to3(x: torch.Tensor, w: torch.Tensor, tanh_axpy: bool = False, addend: Optional[torch.Tensor] = None,

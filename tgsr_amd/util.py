@@ -24,105 +24,50 @@ def _ver(*ts):
     return tuple((t.data_ptr(), t._version, t.device) for t in ts if t is not None)
 
 
-# Inference convolutions without upsampling go through the Winograd F(2x2,3x3) kernel where it applies
-# (ops.wino_supported: Cout % 64 == 0, Cin % 4 == 0, W % 4 == 0), the large layers (>= 64 x 64 pixels and a full round of
-# workgroups: ops.wino4_wanted) through F(4x4,3x3) (TGSR_WINO4=0: F(2x2) there too); TGSR_WINOGRAD=0 keeps the direct kernel.
+# Which kernel form an eval-mode convolution takes is ops.conv3x3_form's decision: Winograd F(2x2,3x3) / F(4x4,3x3) where they
+# apply (TGSR_WINO4=0: F(2x2) there too); TGSR_WINOGRAD=0 keeps the direct kernel.
 WINOGRAD = os.environ.get("TGSR_WINOGRAD", "1") != "0"
 
 
 class _FusedParams:
     """Packed conv weight + folded BN affine for one conv(+bn) pair, rebuilt when any source tensor changes
-    (load_state_dict / optimizer step / .cuda()).  The direct and the Winograd packs are built on first use."""
+    (load_state_dict / optimizer step / .cuda()).  One pack per kernel form the layer has been routed to, built on first use."""
 
     def __init__(self):
         self.key = None
-        self.wpack = self.upack = self.u4pack = self.scale = self.shift = None
+        self.packs = {}              # (form, glu) -> pack
+        self.scale = self.shift = None
 
-    def _refresh(self, conv: nn.Conv2d, bn):
+    def get(self, form: str, conv: nn.Conv2d, bn, glu: bool):
+        """(pack of `form`, scale, shift)"""
         src = [conv.weight] + ([bn.weight, bn.bias, bn.running_mean, bn.running_var] if bn is not None else [])
         key = _ver(*src)
         if key != self.key:
-            self.wpack = self.upack = self.u4pack = None
+            self.packs.clear()
             if bn is not None:
                 self.scale, self.shift = ops.bn_fold(bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.eps)
             else:
                 self.scale = self.shift = None
             self.key = key
-
-    def get(self, conv: nn.Conv2d, bn):
-        self._refresh(conv, bn)
-        if self.wpack is None:
-            self.wpack = ops.pack_conv3x3_weight(conv.weight)
-        return self.wpack, self.scale, self.shift
-
-    def get_wino(self, conv: nn.Conv2d, bn, glu: bool):
-        self._refresh(conv, bn)
-        if self.upack is None:
-            self.upack = ops.pack_wino_weight(conv.weight, glu=glu)
-        return self.upack, self.scale, self.shift
-
-
-    def get_wino4(self, conv: nn.Conv2d, bn, glu: bool):
-        """(pack, scale, shift, wide): the register-fed form of the F(4x4) kernel (tgsr_wino4_wide_conv3x3_fwd: 128-row groups
-        where Cout % 128 == 0, else 64-row groups in 4-wave workgroups) where the layer has an even number of 4-channel stages."""
-        self._refresh(conv, bn)
-        wide = conv.in_channels % 8 == 0
-        if self.u4pack is None:
-            self.u4pack = (C.pack_wino4w_weight(conv.weight.detach(), glu, False) if wide else
-                           C.pack_wino4_weight(conv.weight.detach(), glu, False))
-        return self.u4pack, self.scale, self.shift, wide
-
-
-def _wino4_takes(x, cout, out, residual):
-    """The F(4x4, 3x3) kernel: the layers ops.wino4_wanted names (>= 64 x 64 pixels, whole 8 x 64 tiles, 64-channel groups, a
-    full round of workgroups) when every tensor is 16-byte aligned with batch strides % 4 == 0."""
-    if x.dim() != 4 or not ops.wino4_wanted(x.shape[1], cout, x.shape[2], x.shape[3], x.shape[0]):
-        return False
-    for t in (x, out, residual):
-        if t is not None and (t.data_ptr() % 16 != 0 or (t.shape[0] > 1 and t.stride(0) % 4 != 0) or t.stride(3) != 1 or
-                              t.stride(2) != t.shape[3] or t.stride(1) != t.shape[2] * t.shape[3]):
-            return False
-    return True
-
-
-def _wino_pays(x, cout, out, residual):
-    """Winograd where the kernel takes the shape and is the faster one: always for 64-channel groups; 32-channel
-    groups (Cout % 64 != 0: 8-row workgroup tiles) only when the image gives >= 256 workgroups (measured at B=16:
-    32->32 @128^2 40 vs 71 us, @64^2 16 vs 20 us, @32^2 16 vs 13 us)."""
-    if not ops.wino_supported(x, cout, out=out, residual=residual):
-        return False
-    if cout % 64 == 0:
-        return True
-    B, _, H, W = x.shape
-    return B * ((W + 31) // 32) * ((H + 7) // 8) >= 256
+        pack = self.packs.get((form, glu))
+        if pack is None:
+            pack = self.packs[(form, glu)] = ops.pack_weight(form, conv.weight, glu)
+        return pack, self.scale, self.shift
 
 
 def _conv_bn(x, fp: _FusedParams, conv, bn, glu=False, upsample=False, residual=None, out=None, training=False):
     """One fused block.  eval: conv + folded-BN affine + GLU/residual in one launch (optionally into `out`, a
-    channel-slice view).  training: batch-statistics BN through tgsr_amd.autograd (differentiable)."""
+    channel-slice view), on the kernel form ops.conv3x3_form names.  training: batch-statistics BN through tgsr_amd.autograd
+    (differentiable)."""
     if training:
         from .autograd import conv_bn_act_train
         y = conv_bn_act_train(x, conv, bn, glu=glu, upsample=upsample, residual=residual)
         if out is not None:
             raise RuntimeError("training path does not write into channel-slice views")
         return y
-    if WINOGRAD and not upsample and _wino4_takes(x, conv.out_channels, out, residual):
-        upack, scale, shift, wide = fp.get_wino4(conv, bn, glu)
-        if out is None:
-            return (C.conv3x3_wino4w if wide else C.conv3x3_wino4)(x, upack, conv.out_channels, scale, shift, glu, residual)
-        (C.conv3x3_wino4w_out if wide else C.conv3x3_wino4_out)(x, upack, conv.out_channels, scale, shift, glu, residual, out)
-        return out
-    if WINOGRAD and not upsample and _wino_pays(x, conv.out_channels, out, residual):
-        upack, scale, shift = fp.get_wino(conv, bn, glu)
-        if out is None:
-            return C.conv3x3_wino(x, upack, conv.out_channels, scale, shift, glu, residual)
-        C.conv3x3_wino_out(x, upack, conv.out_channels, scale, shift, glu, residual, out)
-        return out
-    wpack, scale, shift = fp.get(conv, bn)
-    if out is None:
-        return C.conv3x3_fused(x, wpack, conv.out_channels, scale, shift, glu, upsample, residual)
-    C.conv3x3_fused_out(x, wpack, conv.out_channels, scale, shift, glu, upsample, residual, out)
-    return out
+    form = ops.conv3x3_form(x, conv.out_channels, upsample, glu, out, residual, WINOGRAD)
+    pack, scale, shift = fp.get(form, conv, bn, glu)
+    return C.CONV3X3[form](x, pack, conv.out_channels, scale, shift, glu, upsample, residual, out)
 
 
 def invalidate_caches(module: nn.Module):
@@ -134,8 +79,6 @@ def invalidate_caches(module: nn.Module):
             fp = getattr(m, name, None)
             if isinstance(fp, _FusedParams):
                 fp.key = None
-        if hasattr(m, "_up_key"):
-            m._up_key = None
         if hasattr(m, "_table_key"):
             m._key = m._table_key = None
         if hasattr(m, "_a_host"):
@@ -179,34 +122,9 @@ class _UpBlock(nn.Sequential):
         super().__init__(nn.Upsample(scale_factor=2, mode='nearest'), conv3x3(in_planes, out_planes * 2),
                          nn.BatchNorm2d(out_planes * 2), GLU())
         self._fp = _FusedParams()
-        self._up_key = self._up_pack = self._up_aff = None
 
     def forward(self, x, out=None):
-        conv, bn = self[1], self[2]
-        if not self.training and conv.out_channels % 64 == 0:
-            # inference: Winograd on the up-sampled grid with the up-sampling folded into the input transform (9 of the
-            # 16 positions survive: 2.25 multiplies per output); shapes it does not take use the sub-pixel form (four
-            # 2x2 convs on the pre-upsample tensor, 4 multiplies per output)
-            wino = WINOGRAD and ops.upwino_supported(x, conv.out_channels, out=out)
-            # ... and the F(4x4) form of it (25 of 36 positions: 1.56 multiplies per output) where ops.upwino4_wanted routes
-            # the layer (output >= 256 x 256 pixels: the generator's last upBlock, whole tiles, a full round of workgroups) and the
-            # tensors are 16-byte aligned
-            w4 = (wino and ops.upwino4_wanted(x.shape[1], conv.out_channels, x.shape[2], x.shape[3], x.shape[0]) and
-                  x.data_ptr() % 16 == 0 and (out is None or (out.data_ptr() % 16 == 0 and (out.shape[0] == 1 or out.stride(0) % 4 == 0))))
-            src = [conv.weight, bn.weight, bn.bias, bn.running_mean, bn.running_var]
-            key = (_ver(*src), wino, w4)
-            if key != self._up_key:
-                self._up_pack = (C.pack_upwino4_weight(conv.weight.detach(), True) if w4 else
-                                 (ops.pack_upwino_weight if wino else ops.pack_upconv_weight)(conv.weight))
-                self._up_aff = ops.bn_fold(bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.eps)
-                self._up_key = key
-            fn, fn_out = ((C.upwino4_glu, C.upwino4_glu_out) if w4 else
-                          ((C.upwino_glu, C.upwino_glu_out) if wino else (C.upconv3x3_glu, C.upconv3x3_glu_out)))
-            if out is None:
-                return fn(x, self._up_pack, conv.out_channels, self._up_aff[0], self._up_aff[1])
-            fn_out(x, self._up_pack, conv.out_channels, self._up_aff[0], self._up_aff[1], out)
-            return out
-        return _conv_bn(x, self._fp, conv, bn, glu=True, upsample=True, out=out, training=self.training)
+        return _conv_bn(x, self._fp, self[1], self[2], glu=True, upsample=True, out=out, training=self.training)
 
 
 def upBlock(in_planes, out_planes):
