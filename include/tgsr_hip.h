@@ -668,6 +668,23 @@ int tgsr_gaussian_blur_u8(const uint8_t* in, int N, int H, int W, int radius, ui
 int tgsr_u8_normalize(const uint8_t* in, float* out, int64_t n, void* stream);
 
 /*
+ * Image quality of SR output against ground truth, on uint8 images as the reference's caller saves them.
+ *   tgsr_sr_metrics  sr, hr: dense NCHW [B][3][H][W], each independently float32 (sr_f32 / hr_f32 != 0: quantised in the kernel
+ *       by tgsr_to_uint8's rule) or uint8.  shave >= 0 pixels are removed from every border first; the crop must be at least
+ *       11 x 11.  out: float64 [B][3] = (SSE over RGB, SSE over Y, sum of the SSIM values of the crop's (Hc - 10)(Wc - 10) windows).
+ *       Y is the reference's rgb2y (trainer_objective.py:168-174) byte for byte; the SSEs are exact integers, so that
+ *       rmse = sqrt(sse / n), psnr = 20 log10(255 / rmse) on the host equal the reference's psnr() (:177-181) bit for bit.
+ *       SSIM on Y: Wang et al. 2004 as in ssim.m - 11 x 11 Gaussian window of sigma 1.5, 'valid' filtering, K1 = 0.01, K2 = 0.03,
+ *       L = 255, fp64.  ws: tgsr_sr_metrics_ws_elems(...) float64 (per-tile partial sums, added in tile order).
+ *       Two launches on `stream`, no atomics, no host synchronisation: capturable, and the same bits on every run.
+ *   tgsr_rgb_to_y_u8  rgb uint8 [B][3][H][W] -> y uint8 [B][H][W], the same Y.
+ */
+int64_t tgsr_sr_metrics_ws_elems(int B, int H, int W, int shave);
+int tgsr_sr_metrics(const void* sr, int sr_f32, const void* hr, int hr_f32, int B, int H, int W, int shave, double* ws,
+                    double* out, void* stream);
+int tgsr_rgb_to_y_u8(const uint8_t* rgb, int B, int H, int W, uint8_t* y, void* stream);
+
+/*
  * Weight gradient of tgsr_conv3x3_fwd: dw[Cout][Cin][3][3] = sum over (b, y, x) of grad_out * shifted input
  * (upsample=1: the input is read through the folded nearest-x2, H/W are the PRE-upsample sizes).
  * grad_out [B][Cout][Ho][Wo] dense; x [B][Cin][H][W] with batch stride; Cout % 32 == 0.

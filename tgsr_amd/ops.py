@@ -1699,6 +1699,54 @@ def to_uint8(img: torch.Tensor) -> torch.Tensor:
     return out
 
 
+# ----------------------------------------------------------------------------------------- image quality
+METRICS_WINDOW = 11      # the SSIM window; a shaved crop may not be smaller
+
+
+def _metrics_image(t: torch.Tensor, name: str, dtypes) -> torch.Tensor:
+    if t.dtype not in dtypes:
+        raise TgsrError("%s must be %s, got %s" % (name, " or ".join(str(d) for d in dtypes), t.dtype))
+    if t.dim() != 4 or t.shape[1] != 3:
+        raise TgsrError("%s must be [B, 3, H, W], got %s" % (name, tuple(t.shape)))
+    if t.shape[0] < 1:
+        raise TgsrError("%s: empty batch" % name)
+    if not t.is_contiguous():
+        raise TgsrError("%s must be contiguous NCHW (strides %s)" % (name, tuple(t.stride())))
+    return t.detach()
+
+
+def sr_metrics(sr: torch.Tensor, hr: torch.Tensor, shave: int = 0) -> torch.Tensor:
+    """float64 [B, 3] = (SSE over RGB, SSE over Y, sum of the SSIM-on-Y window values) of `sr` against `hr` (tgsr_sr_metrics), on
+    uint8 images: each input is uint8 NCHW or float32 NCHW (quantised in the kernel like `to_uint8`); `shave` pixels leave every
+    border first.  The SSEs are exact integers; the crop has (H - 2 shave - 10)(W - 2 shave - 10) windows."""
+    _need_hip(sr, hr)
+    sr = _metrics_image(sr, "sr", (torch.float32, torch.uint8))
+    hr = _metrics_image(hr, "hr", (torch.float32, torch.uint8))
+    if sr.shape != hr.shape:
+        raise TgsrError("sr_metrics: sr %s and hr %s differ in shape" % (tuple(sr.shape), tuple(hr.shape)))
+    shave = int(shave)
+    B, _, H, W = sr.shape
+    if shave < 0 or H - 2 * shave < METRICS_WINDOW or W - 2 * shave < METRICS_WINDOW:
+        raise ValueError("sr_metrics: %d x %d images shaved by %d leave a crop under %d x %d"
+                         % (H, W, shave, METRICS_WINDOW, METRICS_WINDOW))
+    L = _lib.lib()
+    ws = torch.empty(L.tgsr_sr_metrics_ws_elems(B, H, W, shave), dtype=torch.float64, device=sr.device)
+    out = torch.empty(B, 3, dtype=torch.float64, device=sr.device)
+    check(L.tgsr_sr_metrics(_p(sr), int(sr.dtype == torch.float32), _p(hr), int(hr.dtype == torch.float32), B, H, W, shave,
+                            _p(ws), _p(out), _stream()), "tgsr_sr_metrics")
+    return out
+
+
+def rgb_to_y(rgb: torch.Tensor) -> torch.Tensor:
+    """The reference's rgb2y (trainer_objective.py:168-174) on uint8 [B, 3, H, W] -> uint8 [B, H, W], byte for byte."""
+    _need_hip(rgb)
+    rgb = _metrics_image(rgb, "rgb", (torch.uint8,))
+    B, _, H, W = rgb.shape
+    out = torch.empty(B, H, W, dtype=torch.uint8, device=rgb.device)
+    check(_lib.lib().tgsr_rgb_to_y_u8(_p(rgb), B, H, W, _p(out), _stream()), "tgsr_rgb_to_y_u8")
+    return out
+
+
 # ----------------------------------------------------------------------------------------- discriminator convolutions
 def _dconv(kind: int):
     L = _lib.lib()

@@ -784,6 +784,150 @@ class SRTrainer:
         self._auto_end(False)
         return errG.detach()
 
+    # ------------------------------------------------------------------ validation, snapshots, resume
+    @contextlib.contextmanager
+    def _eval_weights(self, ema):
+        """Scope in which both generators are in eval mode and - `ema` - hold the EMA weights `avg_param_G`, copied IN PLACE
+        into the parameters (their addresses, which the flat optimizer and the captured graphs are bound to, do not change).
+        On exit everything is as it was: the parameters bit for bit, the training modes, the random generators' states, and the
+        weight packs of the PackCache (derived from the restored values: still valid, so they are not marked stale)."""
+        cuda = self.device.type == "cuda"
+        nets = (self.netGL, self.netGH)
+        modes = [m.training for m in nets]
+        rng_cpu = torch.get_rng_state()
+        rng_dev = torch.cuda.get_rng_state(self.device) if cuda else None
+        fresh = None
+        if self._packs is not None:
+            self._packs.settle(self.device)                  # a pending re-pack reads the parameters: it comes first
+            fresh = [e for e in self._packs.entries.values() if e[4] == e[0]._version]
+        backup = None
+        try:
+            with torch.no_grad():
+                if ema:
+                    backup = [p.detach().clone() for p in self.params]
+                    torch._foreach_copy_([p.data for p in self.params], self.avg_param_G)
+                    self._bump_g()                           # the eval modules' folded / packed weights key on the version counters
+            for m in nets:
+                m.eval()
+            yield
+        finally:
+            with torch.no_grad():
+                if backup is not None:
+                    torch._foreach_copy_([p.data for p in self.params], backup)
+                    self._bump_g()
+            for m, mode in zip(nets, modes):
+                m.train(mode)
+            if fresh is not None:
+                for e in fresh:
+                    e[4] = e[0]._version
+            torch.set_rng_state(rng_cpu)
+            if rng_dev is not None:
+                torch.cuda.set_rng_state(rng_dev, self.device)
+
+    @torch.no_grad()
+    def evaluate(self, batches, ema=True, shave=0, max_batches=None):
+        """Score a validation set: `batches` yields (captions, cap_lens, LR, LRb, hr_pyramid); the generators run in eval mode
+        (SRPipeline.from_modules over this trainer's modules, no copies) with the EMA weights (`ema`, the ones `snapshot` saves by
+        default) or the current ones, and every output scale is scored against hr_pyramid[k] on the device (tgsr_amd.metrics:
+        PSNR / RMSE on RGB and Y, SSIM on Y, `shave` border pixels removed) - no synchronisation per batch, one at the end.
+        Returns {"fine": [per scale], "fake": [per scale]}, per scale {"psnr": [N], "rmse", "psnr_y", "rmse_y", "ssim_y", "n": N,
+        "mean": {...}} over the N images seen.  Afterwards the trainer is exactly as it was (`_eval_weights`).
+        Data parallel: every rank passes ITS batches; the rows are gathered in rank order and every rank returns the same dict."""
+        from . import metrics
+        from .parallel import dp_world
+        from .trainer import SRPipeline
+        if getattr(self, "_eval_pipe", None) is None:
+            self._eval_pipe = SRPipeline.from_modules(self.text_encoder, self.netGL, self.netGH, device=self.device)
+        book = metrics.ScoreBook(shave)
+        nscales = 0
+        with torch.cuda.device(self.device), self._eval_weights(ema):
+            for k, (captions, cap_lens, LR, LRb, hr_pyramid) in enumerate(batches):
+                if max_batches is not None and k >= max_batches:
+                    break
+                out = self._eval_pipe(captions, cap_lens, LR, LRb)
+                nscales = len(hr_pyramid)
+                for name in ("fine", "fake"):
+                    if len(out[name]) != nscales:
+                        raise ValueError("evaluate: %d %s images against %d ground-truth scales" % (len(out[name]), name, nscales))
+                    for i, hr in enumerate(hr_pyramid):
+                        book.add((name, i), out[name][i].contiguous(), hr.contiguous())
+        if dp_world() > 1:
+            import torch.distributed as dist
+            mine = ({s: book.rows(s) for s in book.scales()}, dict(book._size))
+            every = [None] * dist.get_world_size()
+            dist.all_gather_object(every, mine)
+            book = metrics.ScoreBook.merge([metrics.ScoreBook.from_rows(r, sizes, shave) for r, sizes in every])
+            nscales = max([i for _n, i in book.scales()], default=-1) + 1
+        res = book.result()
+        if not res:
+            raise ValueError("evaluate: no validation batch")
+        return {name: [res[(name, i)] for i in range(nscales)] for name in ("fine", "fake")}
+
+    def snapshot_due(self, epoch, max_epoch=None):
+        """The snapshot rule of the reference's training loops (pretrain_DAMSM.py:286-287), for the generators."""
+        max_epoch = cfg.TRAIN.MAX_EPOCH if max_epoch is None else max_epoch
+        return epoch % cfg.TRAIN.SNAPSHOT_INTERVAL == 0 or epoch == max_epoch
+
+    @staticmethod
+    def snapshot_paths(model_dir, epoch):
+        """(`netG_epoch_%d.pth`, the same with 'netG' -> 'netGH'): the pair trainer_objective.py:90-93 loads."""
+        name = "netG_epoch_%d.pth" % epoch
+        return os.path.join(model_dir, name), os.path.join(model_dir, name.replace("netG", "netGH"))
+
+    def _state_dicts(self, ema):
+        """(G_SR_NET_low's, NetG_highweight's) state_dicts, detached copies; `ema`: the parameters' entries are the EMA weights."""
+        sds, k = [], 0
+        for m in (self.netGL, self.netGH):
+            sd = {name: v.detach().clone() for name, v in m.state_dict().items()}
+            for name, _p in m.named_parameters():
+                if ema and name in sd:
+                    sd[name] = self.avg_param_G[k].detach().clone()
+                k += 1
+            sds.append(sd)
+        return sds
+
+    def snapshot(self, model_dir, epoch, ema=True):
+        """`netG_epoch_%d.pth` (G_SR_NET_low) and `netGH_epoch_%d.pth` (NetG_highweight): state_dicts only, the keys of the shipped
+        checkpoints - what the reference's caller (trainer_objective.py:90-93) and SRPipeline.load_state_dicts load strictly.
+        `ema` (default): the EMA weights `avg_param_G` with the current running statistics, else the current weights.  No
+        optimizer state (the reference saves none).  Under data parallelism call it on rank 0."""
+        os.makedirs(model_dir, exist_ok=True)
+        pl, ph = self.snapshot_paths(model_dir, epoch)
+        sd_l, sd_h = self._state_dicts(ema)
+        torch.save(sd_l, pl)
+        torch.save(sd_h, ph)
+        return pl, ph
+
+    @staticmethod
+    def resume_epoch(net_g):
+        """The epoch to continue from, out of a snapshot's file name: the digits behind the last '_', + 1; '' -> 0."""
+        if net_g == '':
+            return 0
+        return int(net_g[net_g.rfind('_') + 1:net_g.rfind('.')]) + 1
+
+    def resume(self, net_g=None):
+        """Load `cfg.TRAIN.NET_G` (a netG snapshot) and NetG_highweight from the same name with 'netG' -> 'netGH'
+        (trainer_objective.py:90-93), IN PLACE - parameter addresses, and with them the flat optimizer's views and the captured
+        graphs, stay valid; the EMA copy restarts from the loaded weights, the version counters move and every cached weight
+        pack is re-derived.  Optimizer moments are left as they are (none are saved).  Returns the epoch to continue from."""
+        net_g = cfg.TRAIN.NET_G if net_g is None else net_g
+        start = self.resume_epoch(net_g)
+        if net_g == '':
+            return 0
+        d, base = os.path.split(net_g)
+        sd_l = torch.load(net_g, map_location=self.device)
+        sd_h = torch.load(os.path.join(d, base.replace('netG', 'netGH')), map_location=self.device)
+        if self._packs is not None:
+            self._packs.settle(self.device)
+        self.netGL.load_state_dict(sd_l, strict=True)
+        self.netGH.load_state_dict(sd_h, strict=True)
+        with torch.no_grad():
+            torch._foreach_copy_(self.avg_param_G, [p.data for p in self.params])
+        self._bump_g()
+        if self._packs is not None:
+            self._packs.repack(force=True)
+        return start
+
 
 class DAMSMTrainer:
     """pretrain_DAMSM.py:48-125, 262-284: joint training of RNN_ENCODER and the CNN_ENCODER heads on

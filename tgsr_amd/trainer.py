@@ -138,6 +138,48 @@ class SRPipeline:
             from .lp_pipeline import LpExecutor
             self._lp = LpExecutor(self.netGL, self.netGH, dtype)
 
+    @classmethod
+    def from_modules(cls, text_encoder, netGL, netGH, device=None, overlap=True, dtype="fp32", branch_num=None):
+        """A pipeline over EXISTING modules (a trainer's, say): nothing is copied, moved or switched - the caller puts the
+        modules on `device` (default: where netGL's parameters live) and in the mode the forward is to run in (eval for
+        inference).  `overlap` and `dtype` as in the constructor; branch_num: None = 4 for the x8 generators of model.py, else
+        cfg.TREE.BRANCH_NUM (the x16 ones of models16.py, trainer_objective.py:74-87)."""
+        from . import model as _m8
+        self = cls.__new__(cls)
+        self.dtype = dtype
+        self._lp = None
+        if branch_num is None:
+            x8 = isinstance(netGL, _m8.G_SR_NET_low)
+            branch_num = 4 if x8 else (cfg.TREE.BRANCH_NUM if int(cfg.TREE.BRANCH_NUM) != 4 else 3)
+        self.branch_num = int(branch_num)
+        lp_dtype = dtype not in ("fp32", "f32", None)
+        if self.branch_num != 4 and lp_dtype and getattr(netGH, "weightmap", False):
+            from .lp_pipeline import X16_WEIGHTMAP_REFUSAL
+            raise ValueError(X16_WEIGHTMAP_REFUSAL)
+        self.text_encoder, self.netGL, self.netGH = text_encoder, netGL, netGH
+        self.device = torch.device(device) if device is not None else next(netGL.parameters()).device
+        self.overlap = overlap
+        self._side = None
+        if lp_dtype:
+            from .lp_pipeline import LpExecutor
+            self._lp = LpExecutor(self.netGL, self.netGH, dtype)
+        return self
+
+    def score(self, out, hr_pyramid, shave=0):
+        """Image quality of a forward's outputs against ground truth: {"fine": [scores of scale k], "fake": [...]}, scores =
+        tgsr_amd.metrics.image_scores(out[...][k], hr_pyramid[k]) - float64 arrays psnr, rmse, psnr_y, rmse_y, ssim_y of length B,
+        on the uint8 images the reference's caller would save.  hr_pyramid: float32 in [-1, 1] (the loader's) or uint8, one
+        tensor per output scale (3 for the x8 generators, 4 for the x16 ones)."""
+        from . import metrics
+        res = {}
+        with torch.cuda.device(self.device):
+            for name in ("fine", "fake"):
+                imgs = out[name]
+                if len(imgs) != len(hr_pyramid):
+                    raise ValueError("score: %d %s images against %d ground-truth scales" % (len(imgs), name, len(hr_pyramid)))
+                res[name] = [metrics.image_scores(im.contiguous(), hr.contiguous(), shave) for im, hr in zip(imgs, hr_pyramid)]
+        return res
+
     def load_state_dicts(self, sd_E=None, sd_GL=None, sd_GH=None):
         """strict for E and GL; the x8 GH tolerates only a missing `a` (never saved by the reference, model.py:246-248);
         the x16 GH registers `a` as a parameter (models16.py:126) and loads it.  The weight-map forms load their maps
