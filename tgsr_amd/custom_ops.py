@@ -17,7 +17,7 @@ from typing import Optional
 
 import torch
 
-from . import ops
+from . import lp, ops
 
 _lib = torch.library.Library("tgsr", "DEF")
 _T = torch.Tensor
@@ -578,97 +578,79 @@ rgb_to_y = _define("rgb_to_y(Tensor rgb) -> Tensor", lambda rgb: ops.rgb_to_y(rg
 
 # ================================================================================================ reduced-precision path
 # (lp images are mutable arguments: every kernel writes a channel slice of a caller-owned zero-bordered image)
-def _lp():
-    from . import lp
-    return lp
-
-
 lp_conv3x3 = _define("lp_conv3x3(Tensor x, Tensor wpack, int cin, int cout, Tensor? scale, Tensor? shift, bool glu, bool upsample, "
                      "Tensor? residual, int res_coff, Tensor(a!) out, int out_coff) -> ()",
                      lambda x, wp, cin, cout, s, t, glu, up, res, rco, out, oco:
-                     (_lp().conv3x3(x, wp, cin, cout, s, t, glu=glu, upsample=up, residual=res, res_coff=rco, out=out, out_coff=oco),
+                     (lp.conv3x3(x, wp, cin, cout, s, t, glu=glu, upsample=up, residual=res, res_coff=rco, out=out, out_coff=oco),
                       None)[1], lambda *a: None)
 lp_resblocks = _define("lp_resblocks(Tensor x, Tensor[] wpacks, Tensor[] scales, Tensor[] shifts, Tensor(a!) tmp, Tensor(b!) a, "
                        "Tensor(c!) b, Tensor(d!) flags) -> ()",
-                       lambda x, wp, sc, sh, tmp, a, b, flags: (_lp().resblocks(x, list(wp), list(sc), list(sh), tmp, a, b, flags), None)[1],
+                       lambda x, wp, sc, sh, tmp, a, b, flags: (lp.resblocks(x, list(wp), list(sc), list(sh), tmp, a, b, flags), None)[1],
                        lambda *a: None)
-lp_upconv_glu = _define("lp_upconv_glu(Tensor x, Tensor wpack, int cin, int cout, Tensor? scale, Tensor? shift, Tensor(a!) out, "
-                        "int out_coff) -> ()",
-                        lambda x, wp, cin, cout, s, t, out, oco: (_lp().upconv_glu(x, wp, cin, cout, s, t, out=out, out_coff=oco), None)[1],
-                        lambda *a: None)
-lp_upconv_glu_head = _define("lp_upconv_glu_head(Tensor x, Tensor wpack, int cin, int cout, Tensor? scale, Tensor? shift, "
-                             "Tensor head_wpack, int K, Tensor(a!) partial, Tensor(b!)? out, int out_coff) -> ()",
-                             lambda x, wp, cin, cout, s, t, hw, K, part, out, oco:
-                             (_lp().upconv_glu_head(x, wp, cin, cout, s, t, hw, K, partial=part, out=out, out_coff=oco,
-                                                    write_out=out is not None), None)[1], lambda *a: None)
-lp_stem = _define("lp_stem(Tensor x, Tensor w, Tensor scale, Tensor shift, Tensor(a!) out, int out_coff) -> ()",
-                  lambda x, w, s, t, out, oco: (_lp().stem(x, w, s, t, out=out, out_coff=oco), None)[1], lambda *a: None)
-
-
-
-def _att(pack, nsets, index, T, use_mask, correct_mask, c_coff, attn):
-    return _lp().AttFuse(pack, nsets, index, T, use_mask, correct_mask, c_coff, attn)
-
-
-# the producers of h that also attend to the words for the pixels they have just computed (GlobalAttention.py:87-130 at
+# the producers of h may also attend to the words for the pixels they have just computed (GlobalAttention.py:87-130 at
 # util.py:768-771 / 814-817): att_pack = text_tail_lp's fifth output, index = which projection the stage attends through
-_ATT_SCHEMA = "Tensor att_pack, int nsets, int index, int T, bool use_mask, bool correct_mask, int c_coff"
-lp_stem_att = _define("lp_stem_att(Tensor x, Tensor w, Tensor scale, Tensor shift, Tensor(a!) out, int out_coff, " + _ATT_SCHEMA +
-                      ", Tensor(b!)? attn) -> ()",
-                      lambda x, w, s, t, out, oco, pack, ns, ix, T, um, cm, cco, attn:
-                      (_lp().stem(x, w, s, t, out=out, out_coff=oco, att=_att(pack, ns, ix, T, um, cm, cco, attn)), None)[1],
-                      lambda *a: None)
-lp_upconv_glu_att = _define("lp_upconv_glu_att(Tensor x, Tensor wpack, int cin, int cout, Tensor? scale, Tensor? shift, "
-                            "Tensor(a!) out, int out_coff, " + _ATT_SCHEMA + ", Tensor(b!)? attn) -> ()",
-                            lambda x, wp, cin, cout, s, t, out, oco, pack, ns, ix, T, um, cm, cco, attn:
-                            (_lp().upconv_glu(x, wp, cin, cout, s, t, out=out, out_coff=oco,
-                                              att=_att(pack, ns, ix, T, um, cm, cco, attn)), None)[1], lambda *a: None)
-lp_upconv_glu_head_att = _define("lp_upconv_glu_head_att(Tensor x, Tensor wpack, int cin, int cout, Tensor? scale, Tensor? shift, "
-                                 "Tensor head_wpack, int K, Tensor(a!) partial, Tensor(b!) out, int out_coff, " + _ATT_SCHEMA +
-                                 ", Tensor(c!)? attn) -> ()",
-                                 lambda x, wp, cin, cout, s, t, hw, K, part, out, oco, pack, ns, ix, T, um, cm, cco, attn:
-                                 (_lp().upconv_glu_head(x, wp, cin, cout, s, t, hw, K, partial=part, out=out, out_coff=oco,
-                                                        att=_att(pack, ns, ix, T, um, cm, cco, attn)), None)[1],
-                                 lambda *a: None)
-lp_convert = _define("lp_convert(Tensor src, Tensor(a!) out) -> ()", lambda src, out: (_lp().convert(src, out), None)[1],
+_ATT_SCHEMA = ", Tensor att_pack, int nsets, int index, int T, bool use_mask, bool correct_mask, int c_coff, Tensor(%s!)? attn"
+
+
+def _define_lp_upconv(name, head, att):
+    """The upBlock by sub-pixel decomposition [+ the partial sums of its image head] [+ the next stage's word attention] (the
+    last eight arguments: lp.AttFuse's)."""
+    schema = name + "(Tensor x, Tensor wpack, int cin, int cout, Tensor? scale, Tensor? shift, "
+    if head:      # without the attention `out` may be absent: the feature image is then not written
+        schema += "Tensor head_wpack, int K, Tensor(a!) partial, Tensor(b!)%s out, int out_coff" % ("" if att else "?")
+    else:
+        schema += "Tensor(a!) out, int out_coff"
+
+    def fn(x, wp, cin, cout, s, t, *rest):
+        a = lp.AttFuse(*rest[-8:]) if att else None
+        if head:
+            hw, K, part, out, oco = rest[:5]
+            lp.upconv_glu_head(x, wp, cin, cout, s, t, hw, K, partial=part, out=out, out_coff=oco, write_out=out is not None, att=a)
+        else:
+            lp.upconv_glu(x, wp, cin, cout, s, t, out=rest[0], out_coff=rest[1], att=a)
+    return _define(schema + (_ATT_SCHEMA % ("c" if head else "b") if att else "") + ") -> ()", fn, lambda *a: None)
+
+
+def _define_lp_stem(name, att):
+    def fn(x, w, s, t, out, oco, *a):
+        lp.stem(x, w, s, t, out=out, out_coff=oco, att=lp.AttFuse(*a) if att else None)
+    return _define(name + "(Tensor x, Tensor w, Tensor scale, Tensor shift, Tensor(a!) out, int out_coff" +
+                   (_ATT_SCHEMA % "b" if att else "") + ") -> ()", fn, lambda *a: None)
+
+
+lp_upconv_glu = _define_lp_upconv("lp_upconv_glu", False, False)
+lp_upconv_glu_head = _define_lp_upconv("lp_upconv_glu_head", True, False)
+lp_upconv_glu_att = _define_lp_upconv("lp_upconv_glu_att", False, True)
+lp_upconv_glu_head_att = _define_lp_upconv("lp_upconv_glu_head_att", True, True)
+lp_stem = _define_lp_stem("lp_stem", False)
+lp_stem_att = _define_lp_stem("lp_stem_att", True)
+lp_convert = _define("lp_convert(Tensor src, Tensor(a!) out) -> ()", lambda src, out: (lp.convert(src, out), None)[1],
                      lambda *a: None)
+_to3_fake = lambda x, *a: x.new_empty(x.shape[0], 3, x.shape[1] - 2, x.shape[2] - 2, dtype=torch.float32)      # noqa: E731
 lp_conv_to3 = _define("lp_conv_to3(Tensor x, Tensor wpack, int K, bool tanh_axpy, Tensor? addend, float alpha) -> Tensor",
-                      lambda x, wp, K, act, add, alpha: _lp().conv_to3(x, wp, K, tanh_axpy=act, addend=add, alpha=alpha),
-                      lambda x, wp, K, act, add, alpha: x.new_empty(x.shape[0], 3, x.shape[1] - 2, x.shape[2] - 2, dtype=torch.float32))
+                      lambda x, wp, K, act, add, alpha: lp.conv_to3(x, wp, K, tanh_axpy=act, addend=add, alpha=alpha), _to3_fake)
+# NetG_highweight's other forms (weightmap x useAct, model.py:212-298): the weight map a_k in place of alpha, tanh or the identity
+lp_conv_to3_map = _define("lp_conv_to3_map(Tensor x, Tensor wpack, int K, bool tanh, Tensor? addend, float alpha, Tensor? amap) "
+                          "-> Tensor",
+                          lambda x, wp, K, th, add, alpha, amap: lp.conv_to3_map(x, wp, K, tanh=th, addend=add, alpha=alpha, amap=amap),
+                          _to3_fake)
 lp_word_attention = _define("lp_word_attention(Tensor(a!) h_img, Tensor src, Tensor? mask, int T, bool correct_mask, int c_coff) -> Tensor",
-                            lambda h, src, mask, T, cm, cco: _lp().word_attention(h, src, mask, T, correct_mask=cm, c_coff=cco),
+                            lambda h, src, mask, T, cm, cco: lp.word_attention(h, src, mask, T, correct_mask=cm, c_coff=cco),
                             lambda h, src, mask, T, cm, cco: h.new_empty(h.shape[0], T, h.shape[1] - 2, h.shape[2] - 2, dtype=torch.float32))
 
 
-def _lp_head_combine(sizes_h, sizes_w, partial_low, partial_high, low, high, low_tanh, alpha):
+def _lp_head_combine(sizes_h, sizes_w, partial_low, partial_high, low, high, low_tanh, alpha, amap=(), high_tanh=True):
     n = len(sizes_h)
     none = lambda t: None if (t is None or t.numel() == 0) else t          # noqa: E731  (an empty tensor stands for "absent")
-    _lp().head_combine(low[0].shape[0], list(zip(sizes_h, sizes_w)), [none(t) for t in partial_low[:n]],
-                       [none(t) for t in partial_high[:n]], list(low[:n]), [none(t) for t in high[:n]], low_tanh, alpha)
+    lp.head_combine(low[0].shape[0], list(zip(sizes_h, sizes_w)), [none(t) for t in partial_low[:n]],
+                    [none(t) for t in partial_high[:n]], list(low[:n]), [none(t) for t in high[:n]], low_tanh, alpha,
+                    amap=[none(t) for t in amap[:n]] if len(amap) else None, high_tanh=high_tanh)
 
 
 lp_head_combine = _define("lp_head_combine(int[] H, int[] W, Tensor[] partial_low, Tensor[] partial_high, Tensor(a!)[] low, "
                           "Tensor(b!)[] high, bool low_tanh, float alpha) -> ()", _lp_head_combine, lambda *a: None)
-
-
-# NetG_highweight's other forms (weightmap x useAct, model.py:212-298): the weight map a_k in place of alpha, tanh or the identity
-lp_conv_to3_map = _define("lp_conv_to3_map(Tensor x, Tensor wpack, int K, bool tanh, Tensor? addend, float alpha, Tensor? amap) "
-                          "-> Tensor",
-                          lambda x, wp, K, th, add, alpha, amap: _lp().conv_to3_map(x, wp, K, tanh=th, addend=add, alpha=alpha,
-                                                                                    amap=amap),
-                          lambda x, wp, K, th, add, alpha, amap:
-                          x.new_empty(x.shape[0], 3, x.shape[1] - 2, x.shape[2] - 2, dtype=torch.float32))
-
-
-def _lp_head_combine_map(sizes_h, sizes_w, partial_low, partial_high, low, high, amap, low_tanh, high_tanh, alpha):
-    n = len(sizes_h)
-    none = lambda t: None if (t is None or t.numel() == 0) else t          # noqa: E731  (an empty tensor stands for "absent")
-    maps = [none(t) for t in amap[:n]] if len(amap) else None
-    _lp().head_combine(low[0].shape[0], list(zip(sizes_h, sizes_w)), [none(t) for t in partial_low[:n]],
-                       [none(t) for t in partial_high[:n]], list(low[:n]), [none(t) for t in high[:n]], low_tanh, alpha,
-                       amap=maps, high_tanh=high_tanh)
-
-
+# + the per-scale weight maps and / or tanh-free high heads of NetG_highweight's other forms
 lp_head_combine_map = _define("lp_head_combine_map(int[] H, int[] W, Tensor[] partial_low, Tensor[] partial_high, "
                               "Tensor(a!)[] low, Tensor(b!)[] high, Tensor[] amap, bool low_tanh, bool high_tanh, float alpha) -> ()",
-                              _lp_head_combine_map, lambda *a: None)
+                              lambda H, W, pl, ph, lo, hi, amap, low_tanh, high_tanh, alpha:
+                              _lp_head_combine(H, W, pl, ph, lo, hi, low_tanh, alpha, amap, high_tanh), lambda *a: None)

@@ -5,12 +5,14 @@ BASELINE.json configs[4] ("bf16 ... MFMA bf16 attention + fused conv, hipGraph-c
 border rule: include/tgsr_hip.h, tgsr_lp_common.h).  As in `tgsr_amd.ops`, nothing here computes on the CPU or through
 eager torch arithmetic: torch allocates (zeroed) buffers and supplies the stream.
 """
+import collections
 import ctypes
+import functools
 from typing import Optional
 
 import torch
 
-from . import _lib
+from . import _lib, ops
 from ._lib import TgsrError, check
 from .ops import _need_hip, _p, _stream
 
@@ -35,6 +37,16 @@ def _img(t: torch.Tensor, name: str):
         raise TgsrError("%s must be a contiguous lp image [B,H+2,W+2,C] of bf16/f16, got %s %s" %
                         (name, tuple(t.shape), t.dtype))
     return t.shape[0], t.shape[1] - 2, t.shape[2] - 2, t.shape[3]
+
+
+def _run(entry: str, args, record=None):
+    """One call of the C ABI on torch's current stream.  While a profile is taken (ops.profile is a list) the call sits between
+    two events and `record()` = (name, flops, bytes) is appended with them.  Returns the first event (None: no profile)."""
+    e0 = ops._ev() if ops.profile is not None else None
+    check(getattr(_lib.lib(), entry)(*args, _stream()), entry)
+    if ops.profile is not None and record is not None:
+        ops.profile.append(record() + (e0, ops._ev()))
+    return e0
 
 
 def from_nchw(x: torch.Tensor, dtype=None, cpitch: Optional[int] = None, coff: int = 0,
@@ -115,15 +127,11 @@ def conv3x3(x: torch.Tensor, wpack: torch.Tensor, cin: int, cout: int, scale, sh
         rb, rh, rw, rcp = _img(residual, "residual")
         if (rb, rh, rw) != (B, H, W) or residual.dtype != x.dtype:
             raise TgsrError("lp.conv3x3: residual %s" % (tuple(residual.shape),))
-    from . import ops
-    e0 = ops._ev() if ops.profile is not None else None
-    rc = _lib.lib().tgsr_lp_conv3x3_fwd(DT[x.dtype], _p(x), xcp, B, cin, H, W, _p(wpack), cout, _p(scale), _p(shift),
-                                        _p(residual), rcp, res_coff, _p(out), ocp, out_coff,
-                                        _lib.EPI_AFFINE_GLU if glu else _lib.EPI_AFFINE, 1 if upsample else 0, _stream())
-    check(rc, "tgsr_lp_conv3x3_fwd")
-    if ops.profile is not None:
-        nbytes = 2 * (B * cin * Hi * Wi + B * co * H * W * (2 if residual is not None else 1) + cout * cin * 9)
-        ops.profile.append(("lp_conv3x3_kernel", 2.0 * B * H * W * cout * cin * 9, nbytes, e0, ops._ev()))
+    _run("tgsr_lp_conv3x3_fwd", (DT[x.dtype], _p(x), xcp, B, cin, H, W, _p(wpack), cout, _p(scale), _p(shift), _p(residual), rcp,
+                                 res_coff, _p(out), ocp, out_coff, _lib.EPI_AFFINE_GLU if glu else _lib.EPI_AFFINE,
+                                 1 if upsample else 0),
+         lambda: ("lp_conv3x3_kernel", 2.0 * B * H * W * cout * cin * 9,
+                  2 * (B * cin * Hi * Wi + B * co * H * W * (2 if residual is not None else 1) + cout * cin * 9)))
     return out
 
 
@@ -144,7 +152,6 @@ def resblocks(x: torch.Tensor, wpacks, scales, shifts, tmp: torch.Tensor, a: tor
               flags: torch.Tensor) -> torch.Tensor:
     """Two ResBlocks (four dependent conv3x3 on 64 channels: GLU, + residual, GLU, + residual) in one launch
     (tgsr_lp_resblocks_fwd): x -> tmp -> a -> tmp -> b, bit-identical to four `conv3x3` launches.  Returns b."""
-    import ctypes
     _need_hip(x, tmp, a, b, flags, *wpacks, *scales, *shifts)
     B, H, W, xcp = _img(x, "x")
     dims = [_img(t, n) for t, n in ((tmp, "tmp"), (a, "a"), (b, "b"))]
@@ -159,14 +166,10 @@ def resblocks(x: torch.Tensor, wpacks, scales, shifts, tmp: torch.Tensor, a: tor
     wp = (ctypes.c_void_p * 4)(*[w.data_ptr() for w in wpacks])
     sc = (ctypes.c_void_p * 4)(*[None if s_ is None else s_.data_ptr() for s_ in scales])
     sh = (ctypes.c_void_p * 4)(*[None if s_ is None else s_.data_ptr() for s_ in shifts])
-    from . import ops
-    e0 = ops._ev() if ops.profile is not None else None
-    rc = L.tgsr_lp_resblocks_fwd(DT[x.dtype], _p(x), xcp, B, H, W, wp, sc, sh, _p(tmp), dims[0][3], _p(a), dims[1][3], _p(b),
-                                 dims[2][3], _p(flags), _stream())
-    check(rc, "tgsr_lp_resblocks_fwd")
-    if ops.profile is not None:
-        px = B * H * W
-        ops.profile.append(("lp_conv3x3_kernel", 2.0 * px * 9 * 64 * (128 + 64 + 128 + 64), 2 * (px * 64 * 10 + 9 * 64 * 384), e0, ops._ev()))
+    px = B * H * W
+    _run("tgsr_lp_resblocks_fwd", (DT[x.dtype], _p(x), xcp, B, H, W, wp, sc, sh, _p(tmp), dims[0][3], _p(a), dims[1][3], _p(b),
+                                   dims[2][3], _p(flags)),
+         lambda: ("lp_conv3x3_kernel", 2.0 * px * 9 * 64 * (128 + 64 + 128 + 64), 2 * (px * 64 * 10 + 9 * 64 * 384)))
     return b
 
 
@@ -195,7 +198,6 @@ class AttFuse:
 
 def _att_profile(att, B, H, W, e0):
     """The fused attention is accounted under its own name (zero-duration marker: its time is inside the producer's)."""
-    from . import ops
     if ops.profile is not None and att is not None:
         nbytes = B * H * W * (2 * 32 + (4 * att.T if att.attn is not None else 0))       # h comes from LDS: c_code + attn only
         ops.profile.append(("lp_attention_fused", 4.0 * B * H * W * 32 * att.T, nbytes, e0, e0))
@@ -220,14 +222,11 @@ def stem(x: torch.Tensor, w: torch.Tensor, scale: torch.Tensor, shift: torch.Ten
         raise TgsrError("lp.stem: out %s" % (tuple(out.shape),))
     if att is not None:
         att.check(B, H, W, out.dtype)
-        from . import ops
-        e0 = ops._ev() if ops.profile is not None else None
-        check(_lib.lib().tgsr_lp_stem_att_fwd(DT[out.dtype], _p(x), B, H, W, _p(w), C, _p(scale), _p(shift), _p(out), ocp,
-                                              out_coff, *att.args(), _stream()), "tgsr_lp_stem_att_fwd")
-        _att_profile(att, B, H, W, e0)
-        return out
-    check(_lib.lib().tgsr_lp_stem_fwd(DT[out.dtype], _p(x), B, H, W, _p(w), C, _p(scale), _p(shift), _p(out), ocp,
-                                      out_coff, _stream()), "tgsr_lp_stem_fwd")
+    args = (DT[out.dtype], _p(x), B, H, W, _p(w), C, _p(scale), _p(shift), _p(out), ocp, out_coff)
+    if att is None:
+        check(_lib.lib().tgsr_lp_stem_fwd(*args, _stream()), "tgsr_lp_stem_fwd")
+    else:
+        _att_profile(att, B, H, W, _run("tgsr_lp_stem_att_fwd", args + att.args()))
     return out
 
 
@@ -244,29 +243,6 @@ def pack_to3_weight(w: torch.Tensor, dtype) -> torch.Tensor:
     return out
 
 
-def conv_to3(x: torch.Tensor, wpack: torch.Tensor, K: int, tanh_axpy: bool = False,
-             addend: Optional[torch.Tensor] = None, alpha: float = 0.0, out: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """KxK conv of channels [0,32) of an lp image to a 3-channel fp32 NCHW image [+ tanh + alpha * addend]."""
-    _need_hip(x, wpack, addend, out)
-    B, H, W, xcp = _img(x, "x")
-    if addend is not None:
-        addend = addend.contiguous()
-        if addend.dtype != torch.float32 or tuple(addend.shape) != (B, 3, H, W):
-            raise TgsrError("lp.conv_to3: addend %s" % (tuple(addend.shape),))
-    if out is None:
-        out = torch.empty(B, 3, H, W, dtype=torch.float32, device=x.device)
-    from . import ops
-    e0 = ops._ev() if ops.profile is not None else None
-    rc = _lib.lib().tgsr_lp_conv_to3_fwd(DT[x.dtype], _p(x), xcp, B, 32, H, W, _p(wpack), K,
-                                         _lib.ACT_TANH_AXPY if tanh_axpy else _lib.ACT_NONE, _p(addend), float(alpha),
-                                         _p(out), _stream())
-    check(rc, "tgsr_lp_conv_to3_fwd")
-    if ops.profile is not None:
-        nbytes = B * H * W * (2 * 32 + 4 * 3 * (2 if addend is not None else 1))
-        ops.profile.append(("lp_to3_kernel", 2.0 * B * H * W * 3 * 32 * K * K, nbytes, e0, ops._ev()))
-    return out
-
-
 def _map(amap: Optional[torch.Tensor], H: int, W: int, what: str):
     """A weight map [H, W] fp32 contiguous (NetG_highweight(weightmap=True)'s a_k), or None."""
     if amap is None:
@@ -276,29 +252,36 @@ def _map(amap: Optional[torch.Tensor], H: int, W: int, what: str):
     return amap
 
 
+def _to3(what, with_map, x, wpack, K, act, addend, alpha, amap, out):
+    """The stand-alone image head behind conv_to3 (tgsr_lp_conv_to3_fwd) and conv_to3_map (tgsr_lp_conv_to3_map_fwd: the
+    same arguments + the weight map)."""
+    _need_hip(x, wpack, addend, amap, out)
+    B, H, W, xcp = _img(x, "x")
+    amap = _map(amap, H, W, what)
+    if addend is not None:
+        addend = addend.contiguous()
+        if addend.dtype != torch.float32 or tuple(addend.shape) != (B, 3, H, W):
+            raise TgsrError("%s: addend %s" % (what, tuple(addend.shape)))
+    if out is None:
+        out = torch.empty(B, 3, H, W, dtype=torch.float32, device=x.device)
+    args = (DT[x.dtype], _p(x), xcp, B, 32, H, W, _p(wpack), K, act, _p(addend), float(alpha))
+    _run("tgsr_lp_conv_to3_map_fwd" if with_map else "tgsr_lp_conv_to3_fwd", args + ((_p(amap), _p(out)) if with_map else (_p(out),)),
+         lambda: ("lp_to3_kernel", 2.0 * B * H * W * 3 * 32 * K * K,
+                  B * H * W * (2 * 32 + 4 * 3 * (2 if addend is not None else 1)) + (4 * H * W if amap is not None else 0)))
+    return out
+
+
+def conv_to3(x: torch.Tensor, wpack: torch.Tensor, K: int, tanh_axpy: bool = False,
+             addend: Optional[torch.Tensor] = None, alpha: float = 0.0, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """KxK conv of channels [0,32) of an lp image to a 3-channel fp32 NCHW image [+ tanh + alpha * addend]."""
+    return _to3("lp.conv_to3", False, x, wpack, K, _lib.ACT_TANH_AXPY if tanh_axpy else _lib.ACT_NONE, addend, alpha, None, out)
+
+
 def conv_to3_map(x: torch.Tensor, wpack: torch.Tensor, K: int, tanh: bool = True, addend: Optional[torch.Tensor] = None,
                  alpha: float = 0.0, amap: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """tgsr_lp_conv_to3_map_fwd: act(KxK conv of channels [0,32) of an lp image) + a * addend -> fp32 NCHW, act = tanh or
     the identity (NetG_highweight(useAct=False)), a = amap[y][x] (weightmap=True; [H, W] fp32) or alpha."""
-    _need_hip(x, wpack, addend, amap, out)
-    B, H, W, xcp = _img(x, "x")
-    amap = _map(amap, H, W, "lp.conv_to3_map")
-    if addend is not None:
-        addend = addend.contiguous()
-        if addend.dtype != torch.float32 or tuple(addend.shape) != (B, 3, H, W):
-            raise TgsrError("lp.conv_to3_map: addend %s" % (tuple(addend.shape),))
-    if out is None:
-        out = torch.empty(B, 3, H, W, dtype=torch.float32, device=x.device)
-    from . import ops
-    e0 = ops._ev() if ops.profile is not None else None
-    rc = _lib.lib().tgsr_lp_conv_to3_map_fwd(DT[x.dtype], _p(x), xcp, B, 32, H, W, _p(wpack), K,
-                                             _lib.ACT_TANH_AXPY if tanh else _lib.ACT_IDENT_AXPY, _p(addend), float(alpha),
-                                             _p(amap), _p(out), _stream())
-    check(rc, "tgsr_lp_conv_to3_map_fwd")
-    if ops.profile is not None:
-        nbytes = B * H * W * (2 * 32 + 4 * 3 * (2 if addend is not None else 1)) + (4 * H * W if amap is not None else 0)
-        ops.profile.append(("lp_to3_kernel", 2.0 * B * H * W * 3 * 32 * K * K, nbytes, e0, ops._ev()))
-    return out
+    return _to3("lp.conv_to3_map", True, x, wpack, K, _lib.ACT_TANH_AXPY if tanh else _lib.ACT_IDENT_AXPY, addend, alpha, amap, out)
 
 
 def word_attention(h_img: torch.Tensor, src: torch.Tensor, mask: Optional[torch.Tensor], T: int,
@@ -311,7 +294,6 @@ def word_attention(h_img: torch.Tensor, src: torch.Tensor, mask: Optional[torch.
     B, H, W, cp = _img(h_img, "h_img")
     if tuple(src.shape) != (B, 32, 32) or src.dtype != torch.float32 or not src.is_contiguous():
         raise TgsrError("lp.word_attention: src %s" % (tuple(src.shape),))
-    from . import ops
     m8 = None
     if mask is not None:
         if tuple(mask.shape) != (B, T):
@@ -319,13 +301,9 @@ def word_attention(h_img: torch.Tensor, src: torch.Tensor, mask: Optional[torch.
         m8 = ops._mask_u8(mask)
     if attn is None and need_attn:
         attn = torch.empty(B, T, H, W, dtype=torch.float32, device=h_img.device)
-    e0 = ops._ev() if ops.profile is not None else None
-    rc = _lib.lib().tgsr_lp_word_attention_fwd(DT[h_img.dtype], _p(h_img), cp, _p(src), _p(m8), 1 if correct_mask else 0,
-                                               B, 32, T, H, W, _p(h_img), cp, c_coff, _p(attn), _stream())
-    check(rc, "tgsr_lp_word_attention_fwd")
-    if ops.profile is not None:
-        nbytes = B * H * W * (2 * 2 * 32 + (4 * T if attn is not None else 0))
-        ops.profile.append(("lp_word_attention_kernel", 4.0 * B * H * W * 32 * T, nbytes, e0, ops._ev()))
+    _run("tgsr_lp_word_attention_fwd", (DT[h_img.dtype], _p(h_img), cp, _p(src), _p(m8), 1 if correct_mask else 0, B, 32, T, H, W,
+                                        _p(h_img), cp, c_coff, _p(attn)),
+         lambda: ("lp_word_attention_kernel", 4.0 * B * H * W * 32 * T, B * H * W * (2 * 2 * 32 + (4 * T if attn is not None else 0))))
     return attn
 
 
@@ -343,8 +321,93 @@ def pack_upconv_weight(w: torch.Tensor, dtype) -> torch.Tensor:
     return out
 
 
+def upconv_packable(cin: int, cout: int) -> bool:
+    """Filters pack_upconv_weight and the sub-pixel upBlock kernel take."""
+    return cout == 64 and cin in (32, 64)
+
+
 def upconv_supported(cin: int, cout: int, Hi: int, Wi: int) -> bool:
-    return cout == 64 and cin in (32, 64) and Wi % 32 == 0 and Hi % 4 == 0
+    """Shapes the sub-pixel upBlock kernel takes, with or without a head (tgsr_lp_upconv_glu_head_fwd + tgsr_lp_head_combine
+    need an output image that is a multiple of the 8 x 64 workgroup tile: always true for Hi % 4 == 0, Wi % 32 == 0)."""
+    return upconv_packable(cin, cout) and Wi % 32 == 0 and Hi % 4 == 0
+
+
+# How one upBlock is launched: sub = the sub-pixel kernel (else the direct 9-tap form, conv3x3(upsample=True)); head = its image
+# head's partial sums in the same launch (else a stand-alone conv_to3 after it); write = the 32-channel feature image goes to
+# memory; att = the NEXT stage's word attention in the same launch.
+UpPlan = collections.namedtuple("UpPlan", "sub head write att")
+
+
+@functools.lru_cache(maxsize=None)         # a pure function of a handful of shapes, asked for six times per step
+def upblock_plan(cin: int, cout: int, Hi: int, Wi: int, K: int = 0, image_read: bool = True, att_pack: bool = False,
+                 fuse_heads: bool = True, subpixel: bool = True) -> UpPlan:
+    """THE launch decision of an upBlock on a [Hi, Wi] image (no tensors: shapes and switches in, UpPlan out).  K: its image
+    head (0: none, 3, 5); image_read: something reads the feature image after the head (not so at the last stage); att_pack:
+    the step brought the attention pack for a next stage; fuse_heads / subpixel: the TGSR_LP_FUSE_HEADS / TGSR_LP_SUBPIXEL
+    switches.  Head and attention ride only the sub-pixel kernel; the attention (on the 64-input-channel upBlocks of
+    G_SR_NET_low) attends on the image it writes; a stand-alone head reads the image, so then it is written in any case."""
+    sub = bool(subpixel) and upconv_supported(cin, cout, Hi, Wi)
+    head = sub and bool(fuse_heads) and K != 0
+    return UpPlan(sub, head, bool(image_read) or not head, sub and bool(att_pack) and bool(image_read) and cin == 64)
+
+
+def stem_att_supported(W: int) -> bool:
+    """tgsr_lp_stem_att_fwd attends on whole 32-pixel row segments of the stem's output."""
+    return W % 32 == 0
+
+
+def resblocks_chain_supported(cins, H: int, W: int, max_pixels: int) -> bool:
+    """A stage's ResBlocks as one `resblocks` launch: two blocks (four convolutions) of 64 input channels each, on an image
+    the kernel takes and of at most max_pixels (above, a layer is long enough to hide the kernel boundary)."""
+    return len(cins) == 4 and all(c == 64 for c in cins) and H * W <= max_pixels and resblocks_supported(64, H, W)
+
+
+def head_partial_elems(B: int, H: int, W: int, K: int) -> int:
+    return int(_lib.lib().tgsr_lp_head_partial_elems(B, H, W, K))
+
+
+def _upconv(what, x, wpack, cin, cout, scale, shift, out, out_coff, out_cpitch, att, head_wpack=None, K=0, partial=None,
+            write_out=True):
+    """The sub-pixel upBlock launch behind upconv_glu and upconv_glu_head: one validation, one choice among the C ABI's three
+    entry points (plain, + head, + attention with or without a head), one profile record."""
+    _need_hip(x, wpack, scale, shift, head_wpack, partial, out, *(() if att is None else (att.pack, att.attn)))
+    B, Hi, Wi, xcp = _img(x, "x")
+    L = _lib.lib()
+    co, n, ocp, with_head = cout // 2, 0, 0, head_wpack is not None
+    if with_head:
+        n = L.tgsr_lp_head_partial_elems(B, 2 * Hi, 2 * Wi, K)
+        if partial is None:
+            partial = torch.empty(n, dtype=torch.float32, device=x.device)
+        if partial.numel() != n or partial.dtype != torch.float32 or head_wpack.dtype != x.dtype:
+            raise TgsrError("%s: partial buffer / dtypes do not match" % what)
+    if write_out:
+        if out is None:
+            out = new_image(B, 2 * Hi, 2 * Wi, out_cpitch or (out_coff + co), x.dtype, x.device)
+        ob, oh, ow, ocp = _img(out, "out")
+        if (ob, oh, ow) != (B, 2 * Hi, 2 * Wi) or out.dtype != x.dtype:
+            raise TgsrError("%s: out %s / dtypes do not match" % (what, tuple(out.shape)))
+    else:
+        out = None
+    if (wpack.dtype != x.dtype or cin > xcp or wpack.numel() != L.tgsr_lp_packed_upconv_elems(cout, cin)
+            or (with_head and head_wpack.numel() != K * 512)):
+        raise TgsrError("%s: a [%d, %d, 3, 3] filter does not fit the input (%d channels) / the packs (%d%s values)"
+                        % (what, cout, cin, xcp, wpack.numel(), " / %d" % head_wpack.numel() if with_head else ""))
+    args = (DT[x.dtype], _p(x), xcp, B, cin, Hi, Wi, _p(wpack), cout, _p(scale), _p(shift), _p(out), ocp, out_coff)
+    head = (_p(head_wpack), K if with_head else 0, _p(partial))
+    if att is not None:
+        if not write_out or (with_head and K != 3):
+            raise TgsrError("%s: a fused attention needs the feature image written and the 3x3 head" % what)
+        att.check(B, 2 * Hi, 2 * Wi, x.dtype)
+        entry, args = "tgsr_lp_upconv_glu_att_fwd", args + head + att.args()
+    elif with_head:
+        entry, args = "tgsr_lp_upconv_glu_head_fwd", args + head
+    else:
+        entry = "tgsr_lp_upconv_glu_fwd"
+    e0 = _run(entry, args, lambda: (
+        "lp_upconv_glu_kernel", 2.0 * B * 4 * Hi * Wi * (cout * cin * 9 + (3 * co * K * K if with_head else 0)),
+        2 * (B * cin * Hi * Wi + (B * co * 4 * Hi * Wi if write_out else 0) + cout * cin * 16) + 4 * n))
+    _att_profile(att, B, 2 * Hi, 2 * Wi, e0)
+    return out, partial
 
 
 def upconv_glu(x: torch.Tensor, wpack: torch.Tensor, cin: int, cout: int, scale, shift,
@@ -352,43 +415,7 @@ def upconv_glu(x: torch.Tensor, wpack: torch.Tensor, cin: int, cout: int, scale,
                att: Optional[AttFuse] = None) -> torch.Tensor:
     """upBlock (Upsample x2 -> conv3x3 -> affine -> GLU) on lp images by sub-pixel decomposition, one launch;
     att: + the NEXT stage's word attention on the output tile (tgsr_lp_upconv_glu_att_fwd)."""
-    _need_hip(x, wpack, scale, shift, out, *(() if att is None else (att.pack, att.attn)))
-    B, Hi, Wi, xcp = _img(x, "x")
-    co = cout // 2
-    if out is None:
-        out = new_image(B, 2 * Hi, 2 * Wi, out_cpitch or (out_coff + co), x.dtype, x.device)
-    ob, oh, ow, ocp = _img(out, "out")
-    if (ob, oh, ow) != (B, 2 * Hi, 2 * Wi) or out.dtype != x.dtype or wpack.dtype != x.dtype:
-        raise TgsrError("lp.upconv_glu: out %s / dtypes do not match" % (tuple(out.shape),))
-    if cin > xcp or wpack.numel() != _lib.lib().tgsr_lp_packed_upconv_elems(cout, cin):
-        raise TgsrError("lp.upconv_glu: a [%d, %d, 3, 3] filter does not fit the input (%d channels) / the pack (%d values)"
-                        % (cout, cin, xcp, wpack.numel()))
-    from . import ops
-    e0 = ops._ev() if ops.profile is not None else None
-    if att is not None:
-        att.check(B, 2 * Hi, 2 * Wi, x.dtype)
-        rc = _lib.lib().tgsr_lp_upconv_glu_att_fwd(DT[x.dtype], _p(x), xcp, B, cin, Hi, Wi, _p(wpack), cout, _p(scale),
-                                                   _p(shift), _p(out), ocp, out_coff, None, 0, None, *att.args(), _stream())
-        check(rc, "tgsr_lp_upconv_glu_att_fwd")
-    else:
-        rc = _lib.lib().tgsr_lp_upconv_glu_fwd(DT[x.dtype], _p(x), xcp, B, cin, Hi, Wi, _p(wpack), cout, _p(scale), _p(shift),
-                                               _p(out), ocp, out_coff, _stream())
-        check(rc, "tgsr_lp_upconv_glu_fwd")
-    if ops.profile is not None:
-        nbytes = 2 * (B * cin * Hi * Wi + B * co * 4 * Hi * Wi + cout * cin * 16)
-        ops.profile.append(("lp_upconv_glu_kernel", 2.0 * B * 4 * Hi * Wi * cout * cin * 9, nbytes, e0, ops._ev()))
-        _att_profile(att, B, 2 * Hi, 2 * Wi, e0)
-    return out
-
-
-def head_partial_elems(B: int, H: int, W: int, K: int) -> int:
-    return int(_lib.lib().tgsr_lp_head_partial_elems(B, H, W, K))
-
-
-def head_fusable(cin: int, cout: int, Hi: int, Wi: int) -> bool:
-    """Shapes tgsr_lp_upconv_glu_head_fwd + tgsr_lp_head_combine take: the sub-pixel upBlock kernel's, and an output
-    image whose size is a multiple of the 8 x 64 workgroup tile (always true for Hi % 4 == 0, Wi % 32 == 0)."""
-    return upconv_supported(cin, cout, Hi, Wi)
+    return _upconv("lp.upconv_glu", x, wpack, cin, cout, scale, shift, out, out_coff, out_cpitch, att)[0]
 
 
 def upconv_glu_head(x: torch.Tensor, wpack: torch.Tensor, cin: int, cout: int, scale, shift, head_wpack: torch.Tensor,
@@ -397,46 +424,10 @@ def upconv_glu_head(x: torch.Tensor, wpack: torch.Tensor, cin: int, cout: int, s
     """upBlock + the image head reading it, one launch: returns (out lp image or None, partial head sums fp32).  With
     write_out=False the 32-channel feature image is not written at all (its only consumer is the head).
     att (K == 3, the image is written): + the NEXT stage's word attention on the output tile, same launch."""
-    _need_hip(x, wpack, scale, shift, head_wpack, partial, out, *(() if att is None else (att.pack, att.attn)))
-    B, Hi, Wi, xcp = _img(x, "x")
-    L = _lib.lib()
-    n = L.tgsr_lp_head_partial_elems(B, 2 * Hi, 2 * Wi, K)
-    if partial is None:
-        partial = torch.empty(n, dtype=torch.float32, device=x.device)
-    if partial.numel() != n or partial.dtype != torch.float32 or head_wpack.dtype != x.dtype or wpack.dtype != x.dtype:
-        raise TgsrError("lp.upconv_glu_head: partial buffer / dtypes do not match")
-    ocp = 0
-    if write_out:
-        if out is None:
-            out = new_image(B, 2 * Hi, 2 * Wi, out_coff + cout // 2, x.dtype, x.device)
-        ob, oh, ow, ocp = _img(out, "out")
-        if (ob, oh, ow) != (B, 2 * Hi, 2 * Wi) or out.dtype != x.dtype:
-            raise TgsrError("lp.upconv_glu_head: out %s" % (tuple(out.shape),))
-    else:
-        out = None
-    if cin > xcp or wpack.numel() != L.tgsr_lp_packed_upconv_elems(cout, cin) or head_wpack.numel() != K * 512:
-        raise TgsrError("lp.upconv_glu_head: filter packs do not fit (%d input channels, %d / %d values)"
-                        % (xcp, wpack.numel(), head_wpack.numel()))
-    from . import ops
-    e0 = ops._ev() if ops.profile is not None else None
-    if att is not None:
-        if not write_out or K != 3:
-            raise TgsrError("lp.upconv_glu_head: a fused attention needs the feature image written and the 3x3 head")
-        att.check(B, 2 * Hi, 2 * Wi, x.dtype)
-        rc = L.tgsr_lp_upconv_glu_att_fwd(DT[x.dtype], _p(x), xcp, B, cin, Hi, Wi, _p(wpack), cout, _p(scale), _p(shift),
-                                          _p(out), ocp, out_coff, _p(head_wpack), K, _p(partial), *att.args(), _stream())
-        check(rc, "tgsr_lp_upconv_glu_att_fwd")
-    else:
-        rc = L.tgsr_lp_upconv_glu_head_fwd(DT[x.dtype], _p(x), xcp, B, cin, Hi, Wi, _p(wpack), cout, _p(scale), _p(shift),
-                                           _p(out), ocp, out_coff, _p(head_wpack), K, _p(partial), _stream())
-        check(rc, "tgsr_lp_upconv_glu_head_fwd")
-    if ops.profile is not None:
-        co = cout // 2
-        nbytes = 2 * (B * cin * Hi * Wi + (B * co * 4 * Hi * Wi if write_out else 0) + cout * cin * 16) + 4 * n
-        flops = 2.0 * B * 4 * Hi * Wi * (cout * cin * 9 + 3 * co * K * K)
-        ops.profile.append(("lp_upconv_glu_kernel", flops, nbytes, e0, ops._ev()))
-        _att_profile(att, B, 2 * Hi, 2 * Wi, e0)
-    return out, partial
+    if head_wpack is None:
+        raise TgsrError("lp.upconv_glu_head: no head filter (lp.upconv_glu is the upBlock alone)")
+    return _upconv("lp.upconv_glu_head", x, wpack, cin, cout, scale, shift, out, out_coff, None, att, head_wpack, K, partial,
+                   write_out)
 
 
 def head_combine(B: int, sizes, partial_low, partial_high, low, high, low_tanh: bool, alpha: float, amap=None,
@@ -465,18 +456,12 @@ def head_combine(B: int, sizes, partial_low, partial_high, low, high, low_tanh: 
     arr_i = ctypes.c_int * n
     arr_p = ctypes.c_void_p * n
     ptr = lambda lst: arr_p(*[None if t is None else t.data_ptr() for t in lst])      # noqa: E731
-    from . import ops
-    e0 = ops._ev() if ops.profile is not None else None
+    args = (n, B, arr_i(*[s[0] for s in sizes]), arr_i(*[s[1] for s in sizes]), ptr(partial_low), ptr(partial_high), ptr(low), ptr(high))
     if maps is None and high_tanh:
-        rc = L.tgsr_lp_head_combine(n, B, arr_i(*[s[0] for s in sizes]), arr_i(*[s[1] for s in sizes]), ptr(partial_low),
-                                    ptr(partial_high), ptr(low), ptr(high), 1 if low_tanh else 0, float(alpha), _stream())
-        check(rc, "tgsr_lp_head_combine")
+        entry, args = "tgsr_lp_head_combine", args + (1 if low_tanh else 0, float(alpha))
     else:
-        rc = L.tgsr_lp_head_combine_map(n, B, arr_i(*[s[0] for s in sizes]), arr_i(*[s[1] for s in sizes]), ptr(partial_low),
-                                        ptr(partial_high), ptr(low), ptr(high), None if maps is None else ptr(maps),
-                                        1 if low_tanh else 0, 1 if high_tanh else 0, float(alpha), _stream())
-        check(rc, "tgsr_lp_head_combine_map")
-    if ops.profile is not None:
-        nbytes = 4 * sum(t.numel() for t in ts + [m for m in (maps or ()) if m is not None])
-        ops.profile.append(("lp_head_combine_kernel", 0.0, nbytes, e0, ops._ev()))
+        entry, args = "tgsr_lp_head_combine_map", args + (None if maps is None else ptr(maps), 1 if low_tanh else 0,
+                                                          1 if high_tanh else 0, float(alpha))
+    _run(entry, args, lambda: ("lp_head_combine_kernel", 0.0,
+                               4 * sum(t.numel() for t in ts + [m for m in (maps or ()) if m is not None])))
     return low, high

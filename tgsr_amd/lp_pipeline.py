@@ -69,39 +69,30 @@ class _Conv:
 
 
 class _UpConv:
-    """upBlock: sub-pixel pack where the kernel takes the shape, else the direct form."""
+    """upBlock: the packs of both kernel forms, the folded affine, and the launch a `lp.upblock_plan` asks for."""
 
     def __init__(self, conv, bn, dtype):
         self.cin, self.cout = conv.in_channels, conv.out_channels
-        self.sub = SUBPIXEL and self.cout == 64 and self.cin in (32, 64)
-        self.wsub = lp.pack_upconv_weight(conv.weight, dtype) if self.sub else None
+        # TGSR_LP_SUBPIXEL as this upBlock sees it: the sub-pixel pack exists (packed once per weight version)
+        self.wsub = lp.pack_upconv_weight(conv.weight, dtype) if SUBPIXEL and lp.upconv_packable(self.cin, self.cout) else None
         self.wpack = lp.pack_conv3x3_weight(conv.weight, dtype)
         self.scale, self.shift = ops.bn_fold(bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.eps)
 
-    def __call__(self, x, out, att=None):
-        if att is not None:
-            C.lp_upconv_glu_att(x, self.wsub, self.cin, self.cout, self.scale, self.shift, out, 0, *att)
-        elif self.sub and lp.upconv_supported(self.cin, self.cout, x.shape[1] - 2, x.shape[2] - 2):
-            C.lp_upconv_glu(x, self.wsub, self.cin, self.cout, self.scale, self.shift, out, 0)
+    def plan(self, Hi, Wi, K, image_read, att_pack=False):
+        return lp.upblock_plan(self.cin, self.cout, Hi, Wi, K, image_read, att_pack, FUSE_HEADS, self.wsub is not None)
+
+    def __call__(self, plan, x, out, head_wpack=None, K=0, partial=None, att=None):
+        """One launch: the upBlock [+ the partial sums of its head] [+ the next stage's attention, att = its arguments]."""
+        a = (x, self.wsub, self.cin, self.cout, self.scale, self.shift)
+        if plan.head:
+            op = C.lp_upconv_glu_head_att if plan.att else C.lp_upconv_glu_head
+            op(*a, head_wpack, K, partial, out if plan.write else None, 0, *(att if plan.att else ()))
+        elif plan.att:
+            C.lp_upconv_glu_att(*a, out, 0, *att)
+        elif plan.sub:
+            C.lp_upconv_glu(*a, out, 0)
         else:
             C.lp_conv3x3(x, self.wpack, self.cin, self.cout, self.scale, self.shift, True, True, None, 0, out, 0)
-        return out
-
-    def att_fusable(self, x):
-        """The next stage's attention can ride this upBlock's epilogue: the sub-pixel kernel at 64 input channels."""
-        return self.sub and self.cin == 64 and lp.upconv_supported(self.cin, self.cout, x.shape[1] - 2, x.shape[2] - 2)
-
-    def fusable(self, x):
-        return FUSE_HEADS and self.sub and lp.head_fusable(self.cin, self.cout, x.shape[1] - 2, x.shape[2] - 2)
-
-    def with_head(self, x, head_wpack, K, partial, out, att=None):
-        """upBlock + its image head's partial sums in one launch; out None: the feature image is not written."""
-        if att is not None:
-            C.lp_upconv_glu_head_att(x, self.wsub, self.cin, self.cout, self.scale, self.shift, head_wpack, K, partial, out, 0,
-                                     *att)
-        else:
-            C.lp_upconv_glu_head(x, self.wsub, self.cin, self.cout, self.scale, self.shift, head_wpack, K, partial, out, 0)
-        return out, partial
 
 
 class _Stem:
@@ -237,7 +228,7 @@ class LpExecutor:
             atts.append(torch.empty(B, T, H, W, dtype=torch.float32, device=LR.device))
             return (pack, len(atts_m), set_of[k], T, mask is not None, bool(self.gl_stage[k]["att"].correct_mask), 32, atts[-1])
 
-        fused_next = pack is not None and W0 % 32 == 0                         # stage 0: inside the stem
+        fused_next = pack is not None and lp.stem_att_supported(W0)            # stage 0: inside the stem
         self.gl_stem(LR, out=wide, att=att_args(0) if fused_next else None)    # im2f -> channels [0, 32) (+ c_code -> [32, 64))
         for k, st in enumerate(self.gl_stage):
             bb = bufs["gl"][k]
@@ -245,8 +236,7 @@ class LpExecutor:
                 atts.append(C.lp_word_attention(bb["wide"], srcs[k], mask, T, st["att"].correct_mask, 32))
             x = bb["wide"]
             Hk, Wk = x.shape[1] - 2, x.shape[2] - 2
-            if (CHAIN and len(st["res"]) == 2 and Hk * Wk <= CHAIN_MAX_PIXELS and lp.resblocks_supported(st["res"][0][0].cin, Hk, Wk)
-                    and all(c.cin == 64 for pair in st["res"] for c in pair)):
+            if CHAIN and lp.resblocks_chain_supported([c.cin for pair in st["res"] for c in pair], Hk, Wk, CHAIN_MAX_PIXELS):
                 if bb.get("flags") is None:
                     bb["flags"] = lp.resblocks_flags(B, Hk, Wk, x.device)
                 cs = [c for pair in st["res"] for c in pair]
@@ -259,20 +249,16 @@ class LpExecutor:
                     c1(bb["tmp"], residual=x, out=o)
                     x = o
             nxt = bufs["gl"][k + 1]["wide"] if k < last else bufs["h3"]
-            # the NEXT stage's attention inside this upBlock (its output is that stage's h)
-            fused_next = pack is not None and k < last and st["up"].att_fusable(x)
-            if st["up"].fusable(x):
-                # upBlock + the partial sums of its 3x3 head; the last stage's feature image is read by nothing else
-                Ho, Wo = 2 * (x.shape[1] - 2), 2 * (x.shape[2] - 2)
-                if bufs["pl"][k] is None:
-                    bufs["pl"][k] = torch.empty(lp.head_partial_elems(B, Ho, Wo, 3), dtype=torch.float32, device=x.device)
-                st["up"].with_head(x, st["head"], 3, bufs["pl"][k], nxt if k < last else None,
-                                   att=att_args(k + 1) if fused_next else None)
-                fake.append(torch.empty(B, 3, Ho, Wo, dtype=torch.float32, device=x.device))
-                pend.append(bufs["pl"][k])
+            # upBlock -> channels [0, 32) of the next stage, which nothing but the 3x3 head reads at the last stage; the NEXT
+            # stage's attention inside it where the plan says so (its output is that stage's h)
+            f, plan = _upblock(st["up"], x, nxt, st["head"], 3, bufs["pl"], k, k < last,
+                               None if pack is None else lambda: att_args(k + 1))
+            fused_next = plan.att
+            if plan.head:
+                fake.append(torch.empty(f.B, 3, f.H, f.W, dtype=torch.float32, device=x.device))
+                pend.append(f.t)
             else:
-                st["up"](x, out=nxt, att=att_args(k + 1) if fused_next else None)   # upBlock -> channels [0, 32) of the next stage
-                fake.append(C.lp_conv_to3(nxt, st["head"], 3, self.gl_head_tanh, None, 0.0))
+                fake.append(C.lp_conv_to3(f, st["head"], 3, self.gl_head_tanh, None, 0.0))
                 pend.append(None)
         if defer_heads:
             return fake, atts, mu, logvar, pend
@@ -303,16 +289,8 @@ class LpExecutor:
                 c0(cur, glu=True, out=m["t"])
                 c1(m["t"], out=m["v"])
                 cur = m["v"]
-            nlast = len(self.gh_up) - 1
-            if self.gh_up[k].fusable(cur):
-                B, Ho, Wo = cur.shape[0], 2 * (cur.shape[1] - 2), 2 * (cur.shape[2] - 2)
-                if bufs["ph"][k] is None:
-                    bufs["ph"][k] = torch.empty(lp.head_partial_elems(B, Ho, Wo, 5), dtype=torch.float32, device=cur.device)
-                self.gh_up[k].with_head(cur, self.gh_head, 5, bufs["ph"][k], bufs["u"][k] if k < nlast else None)
-                feats.append(_Partial(bufs["ph"][k], B, Ho, Wo))
-            else:
-                self.gh_up[k](cur, out=bufs["u"][k])
-                feats.append(bufs["u"][k])
+            f, _ = _upblock(self.gh_up[k], cur, bufs["u"][k], self.gh_head, 5, bufs["ph"], k, k < len(self.gh_up) - 1)
+            feats.append(f)              # the 5x5 heads wait for the low-frequency images: high_heads
             cur = bufs["u"][k]
         return feats
 
@@ -364,6 +342,22 @@ class LpExecutor:
         return fine
 
 
+def _upblock(up, x, out, head_wpack, K, partials, k, image_read, att=None):
+    """One upBlock of either generator with its KxK image head, as `lp.upblock_plan` lays it out -> (f, plan): f = the head's
+    pending partial sums (a _Partial over partials[k], allocated on first use) where the head rode the upBlock, else the feature
+    image `out` for a stand-alone head to read.  att: () -> the arguments of the next stage's attention, called if it rides too."""
+    B, Hi, Wi = x.shape[0], x.shape[1] - 2, x.shape[2] - 2
+    plan = up.plan(Hi, Wi, K, image_read, att is not None)
+    if not plan.head:
+        up(plan, x, out, att=att() if plan.att else None)
+        return out, plan
+    Ho, Wo = 2 * Hi, 2 * Wi
+    if partials[k] is None:
+        partials[k] = torch.empty(lp.head_partial_elems(B, Ho, Wo, K), dtype=torch.float32, device=x.device)
+    up(plan, x, out, head_wpack, K, partials[k], att() if plan.att else None)
+    return _Partial(partials[k], B, Ho, Wo), plan
+
+
 def _combine(sizes, pl, ph, lo, hi, low_tanh, alpha, maps=None, high_tanh=True):
     """torch.ops.tgsr.lp_head_combine (tensor lists cannot hold None: an empty tensor stands for an absent entry); the
     shipped heads (no maps, tanh) through it, NetG_highweight's other forms through lp_head_combine_map."""
@@ -378,7 +372,7 @@ def _combine(sizes, pl, ph, lo, hi, low_tanh, alpha, maps=None, high_tanh=True):
 
 
 class _Partial:
-    """A NetG_highweight head whose per-tile partial sums an upBlock has written (LpExecutor.high_trunk)."""
+    """An image head whose per-tile partial sums an upBlock has written (_upblock), for a combine launch to finish."""
 
     def __init__(self, t, B, H, W):
         self.t, self.B, self.H, self.W = t, B, H, W
