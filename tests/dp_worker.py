@@ -112,7 +112,7 @@ def main():
                           d["class_ids"][lo:hi])
     torch.cuda.synchronize()
     res["damsm_loss"], res["damsm_flat"] = float(dl), dt.bucket.flat.cpu()
-    # ---- updates replayed from hipGraphs under data parallelism (train.py `_capture_g` / `_capture_d_update`: segments with the
+    # ---- updates replayed from hipGraphs under data parallelism (train.py `_capture_update`, for the generators and for each discriminator: segments with the
     # bucket's all-reduce BETWEEN them) against the eager data-parallel step, same initial weights, same shards, same noise: bit
     # for bit - the generator-only step and the G/D alternation
     # (the discriminators are built for 64 / 128 / 256-pixel images: the G/D runs take a 32 x 32 batch)

@@ -379,7 +379,7 @@ def test_measured_graph_policy_settles_and_changes_no_bit():
             for k, tr in enumerate(trs):
                 torch.manual_seed(100 + step)
                 out[k].append(float(tr.step(cap.to(DEV), lens.tolist(), LR.to(DEV), LRb.to(DEV), hr)))
-            forms.append(None if trs[0]._auto is None else trs[0]._auto["form"])
+            forms.append(None if trs[0]._auto is None else trs[0]._auto.form)
         a = trs[0]
         assert forms[:train.GRAPH_G_WARMUP + train.GRAPH_G_TRIALS] == ["eager"] * (train.GRAPH_G_WARMUP + train.GRAPH_G_TRIALS)
         assert forms[train.GRAPH_G_SETTLED - 1] is None and a._auto is None, forms          # settled

@@ -370,7 +370,7 @@ def _dconv_grads(x, weight, draw, kind, need_dx, need_dw):
     w = weight.detach()
     def side(fn):
         # the weight gradient is a leaf of the backward graph: beside the data-gradient chain when the trainer has registered a
-        # side stream for this update (train.SRTrainer._d_wgrad_side) and the gradient lands in its bucket slot unaccumulated
+        # side stream for this update (train.SRTrainer._wgrad_side) and the gradient lands in its bucket slot unaccumulated
         adopted = dw._base is not None and weight.grad is None and not torch.is_grad_enabled()
         if adopted and wgrad_stream(dev) is not None:
             _ADOPTED.append((weight, dw.data_ptr()))

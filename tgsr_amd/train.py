@@ -16,22 +16,34 @@ Data parallel: gradients live in one flat bucket, one all-reduce per step (tgsr_
 """
 import contextlib
 import os
+import statistics
 import time
+import warnings
 
+import numpy as np
 import torch
+import torch.distributed as dist
 
+from . import autograd, metrics, model, parallel
 from .miscc import losses
 from .miscc.config import cfg
 from .miscc.utils import copy_G_params, load_params  # noqa: F401  (miscc/utils.py:467-474: the generator EMA helpers)
 from .model import CNN_ENCODER, G_SR_NET_low, NetG_highweight, RNN_ENCODER
-from .parallel import FlatGradBucket
-from .trainer import caption_mask, distinct_streams
+from .optim import FlatAdam
+from .parallel import FlatGradBucket, RcclDirect, dp_world
+from .trainer import SRPipeline, caption_mask, distinct_streams
 
 
 def prepare_labels(batch_size, device):
     """trainer_objective.py:43-53."""
     return (torch.ones(batch_size, device=device), torch.zeros(batch_size, device=device),
             torch.arange(batch_size, device=device))
+
+
+def snapshot_due(epoch, max_epoch=None):
+    """The snapshot rule of the reference's training loops (pretrain_DAMSM.py:286-287)."""
+    max_epoch = cfg.TRAIN.MAX_EPOCH if max_epoch is None else max_epoch
+    return epoch % cfg.TRAIN.SNAPSHOT_INTERVAL == 0 or epoch == max_epoch
 
 
 # eager G/D steps before the discriminator updates are captured (allocator, streams and Adam state warm)
@@ -42,6 +54,62 @@ GRAPH_G_WARMUP = 3
 GRAPH_G_TRIALS = 3
 # ... and the number of steps after which that choice has been made (warm-up, eager trials, the capturing step, replayed trials)
 GRAPH_G_SETTLED = GRAPH_G_WARMUP + 2 * GRAPH_G_TRIALS + 1
+
+
+class GraphPolicy:
+    """Which form the generators' update takes - eager or replayed from hipGraphs - and, for TGSR_GRAPH_G=auto, the measurement that
+    decides it.  `graph` is the form in force (the first guess until measured, then the faster one, or whatever `pin` was given);
+    while `measuring`, step k's form is a function of k alone: steps [WARMUP, WARMUP + TRIALS) are timed eager, step
+    WARMUP + TRIALS captures (untimed), the next TRIALS are timed replays, and the end of step GRAPH_G_SETTLED - 1 decides by the
+    medians.  The owner supplies `clock()` (seconds, the device idle) and `reduce_max(te, tp)` (the slowest rank's times, so that
+    every rank takes the same form).  `report` is what the trainer publishes as `graph_policy`."""
+
+    def __init__(self, mode, prior, measuring, clock=time.perf_counter, reduce_max=lambda te, tp: (te, tp)):
+        self.mode, self.graph, self.measuring = mode, bool(prior), bool(measuring)
+        self.clock, self.reduce_max = clock, reduce_max
+        self.eager_s, self.replay_s, self.t0, self.form = [], [], None, None
+        self.report = {"mode": mode, "prior": "replay" if prior else "eager"}
+
+    def pin(self, graph):
+        """An explicit choice: it ends the measurement."""
+        self.graph, self.measuring = bool(graph), False
+
+    def replays(self, k):
+        """Does step k take the replayed form (once the warm-up is over)?"""
+        return (self.form == "replay" if self.measuring else self.graph) and k >= GRAPH_G_WARMUP
+
+    def begin(self, k):
+        """The top of step k: its form while the policy is measuring, and the start of its clock if it is a timed one."""
+        if not self.measuring:
+            return
+        self.form = "eager" if k < GRAPH_G_WARMUP + GRAPH_G_TRIALS else "replay"
+        timed = GRAPH_G_WARMUP <= k and k != GRAPH_G_WARMUP + GRAPH_G_TRIALS
+        self.t0 = self.clock() if timed else None
+
+    def end(self, k, replayed):
+        """The end of step k (`replayed`: it really ran from the graphs); the last measured step decides."""
+        if not self.measuring:
+            return
+        if self.t0 is not None:
+            dt = self.clock() - self.t0
+            if self.form == "replay":
+                self.replay_s.append(dt if replayed else float("inf"))     # (the capture failed or the configuration has none)
+            else:
+                self.eager_s.append(dt)
+        if k + 1 < GRAPH_G_SETTLED:
+            return
+        inf = float("inf")
+        te = statistics.median(self.eager_s) if self.eager_s else inf      # (steps that raised may have left a form untimed)
+        tp = statistics.median(self.replay_s) if self.replay_s else inf
+        te, tp = self.reduce_max(te, tp)
+        if te == inf:                                               # nothing to compare with: the first guess stands
+            self.pin(self.graph)
+            self.report["chosen"] = "replay" if self.graph else "eager"
+            return
+        self.pin(tp <= te)
+        self.report.update({"eager_ms": round(te * 1e3, 3), "replay_ms": None if tp == inf else round(tp * 1e3, 3),
+                            "chosen": "replay" if tp <= te else "eager",
+                            "trials": "median of %d steps of each form, device idle on both sides" % GRAPH_G_TRIALS})
 
 
 class SRTrainer:
@@ -61,18 +129,10 @@ class SRTrainer:
         256 pixels: 32 x 32 LR) with the other generator parameters (flat gradient bucket, Adam, EMA); use_act=False drops
         the heads' Tanh."""
         self.device = torch.device(device)
+        cuda = self.device.type == "cuda"
         # data parallel: the DAMSM ranking term on the gathered global batch (parallel.GATHER_NEGATIVES, default on) or per shard
-        from . import parallel as _par
-        self.gather_negatives = _par.GATHER_NEGATIVES if gather_negatives is None else bool(gather_negatives)
-        # the generators' weight gradients run on a side stream beside the data-gradient chain while a step's backward
-        # is in flight (12.7 -> 11.7 ms per step at B=16: the small layers' weight-gradient kernels and the slab sums
-        # fill a fraction of the CUs); TGSR_WGRAD_SIDE=0 keeps everything on one stream
-        from . import autograd as _ag
-        self._packs = _ag.PackCache() if (self.device.type == "cuda" and os.environ.get("TGSR_PACK_CACHE", "1") != "0") else None
-        # (distinct_streams: torch hands out pool streams round robin - two "new" streams can be the same hip stream)
-        cur = [torch.cuda.current_stream(self.device).cuda_stream] if self.device.type == "cuda" else []
-        self._wside = distinct_streams(1, self.device, avoid=cur)[0] \
-            if self.device.type == "cuda" and os.environ.get("TGSR_WGRAD_SIDE", "1") != "0" else None
+        self.gather_negatives = parallel.GATHER_NEGATIVES if gather_negatives is None else bool(gather_negatives)
+        self._packs = autograd.PackCache() if (cuda and os.environ.get("TGSR_PACK_CACHE", "1") != "0") else None
         self.image_encoder = image_encoder
         self.text_encoder = RNN_ENCODER(n_words, nhidden=cfg.TEXT.EMBEDDING_DIM).to(self.device).eval()
         for p in self.text_encoder.parameters():
@@ -91,11 +151,9 @@ class SRTrainer:
         self._early_hi = None                                            # ... = flat[0:_early_hi], set once the bucket exists
         self._early_on = os.environ.get("TGSR_EARLY_ALLREDUCE", "1") != "0"
         self._early_left, self._early = -1, None
-        self._comm = distinct_streams(1, self.device, avoid=cur + ([self._wside.cuda_stream] if self._wside is not None else []))[0] \
-            if self.device.type == "cuda" else None
         for p in gh_params:
             p.register_post_accumulate_grad_hook(self._gh_grad_done)
-        self._fused_adam = self.device.type == "cuda" and os.environ.get("TGSR_FUSED_ADAM", "1") != "0"
+        self._fused_adam = cuda and os.environ.get("TGSR_FUSED_ADAM", "1") != "0"
         # The generators' update - forward, losses, backward, Adam, re-pack, EMA - holds no host decision once the text encoder has
         # produced the embeddings: it is replayed from hipGraphs (one per batch shape), in segments with the gradient all-reduce
         # BETWEEN them, so the replayed step also exists with more than one rank (`_capture_g`).  TGSR_GRAPH_G=0: eager.
@@ -111,156 +169,120 @@ class SRTrainer:
         # several ranks: the slowest rank's times, so that every rank takes the same one).  The rule above is only the form the
         # first steps take; assigning `_graph_g` by hand ends the measurement and pins the form.
         mode = os.environ.get("TGSR_GRAPH_G", "auto")
-        self._auto = None
-        self._graph_g = self.device.type == "cuda" and (mode == "1" or (mode == "auto" and bool(discriminators) and
-                                                                         image_encoder is None))
-        self._graph_capable = self.device.type == "cuda" and mode != "0"
-        if mode == "auto" and self.device.type == "cuda":
-            self._auto = {"eager_s": [], "replay_s": [], "t0": None, "form": None}
-        self.graph_policy = {"mode": mode, "prior": "replay" if self._graph_g else "eager"}
-        self._ggraphs, self._gsteps, self._ghyper, self._g_bump = {}, 0, None, None
+        self._graph_capable = cuda and mode != "0"
+        self._policy = GraphPolicy(mode, prior=cuda and (mode == "1" or (mode == "auto" and bool(discriminators) and image_encoder is None)),
+                                   measuring=cuda and mode == "auto", clock=self._idle_clock, reduce_max=self._max_over_ranks)
+        self._ggraphs, self._gsteps, self._ghyper = {}, 0, None
         # TGSR_FLAT_ADAM (default on, HIP only): parameters and moments re-homed into flat buffers beside the flat gradient bucket,
         # the update ONE launch of tgsr::adam_flat_ (optim.FlatAdam; the same rule as torch.optim.Adam); 0 = torch's fused Adam
-        self._flat_adam = self.device.type == "cuda" and os.environ.get("TGSR_FLAT_ADAM", "1") != "0"
+        self._flat_adam = cuda and os.environ.get("TGSR_FLAT_ADAM", "1") != "0"
         self._g_lr = lr or cfg.TRAIN.GENERATOR_LR
         self.ema_decay = ema_decay
         self.avg_param_G = copy_G_params(self.netGL) + copy_G_params(self.netGH)
         self.netsD, self.optsD, self.bucketsD = [], [], []
         self._graph_d, self._dgraphs, self._dsteps, self._d_bump = False, [], 0, []
         if discriminators:
-            from . import model
             self.netsD = list(discriminators) if not isinstance(discriminators, bool) else \
                 [model.D_NET64(), model.D_NET128(), model.D_NET256()]
             # A discriminator's update - forward on (real, fake.detach()), loss, backward, Adam - is a closed piece of device work
             # with no host decision in it: replayed from a hipGraph per discriminator once the step has run `GRAPH_D_WARMUP` times
-            # (with more than one rank as two graphs around the bucket's all-reduce: `_capture_d_update`).  ~1 000 of a step's ~1 570
+            # (with more than one rank as two graphs around the bucket's all-reduce: `_capture_update`).  ~1 000 of a step's ~1 570
             # launches leave the host that way; the step was issued no faster than 21-25 ms (profiles/HISTORY.md 3.18).  TGSR_GRAPH_D=0: eager.
-            self._graph_d = self.device.type == "cuda" and os.environ.get("TGSR_GRAPH_D", "1") != "0"
-            self._dgraphs, self._dsteps, self._d_bump = [None] * len(self.netsD), 0, [None] * len(self.netsD)
+            self._graph_d = cuda and os.environ.get("TGSR_GRAPH_D", "1") != "0"
+            self._dgraphs = [None] * len(self.netsD)
             for d in self.netsD:
                 d.to(self.device).train()
                 self.bucketsD.append(FlatGradBucket(d.parameters(), buffers=d.buffers()).attach())
                 # (fused: one pass over a discriminator's ~70 M parameters and their moments instead of the ~10 of the
                 # multi-tensor form - 2.0 ms of a G/D step were Adam kernels running alone on the device)
-                if self._flat_adam:
-                    from .optim import FlatAdam
-                    self.optsD.append(FlatAdam(self.bucketsD[-1].params, self.bucketsD[-1].flat, lr=d_lr or cfg.TRAIN.DISCRIMINATOR_LR,
-                                               betas=(0.5, 0.999)))
-                else:
-                    self.optsD.append(torch.optim.Adam(d.parameters(), lr=d_lr or cfg.TRAIN.DISCRIMINATOR_LR, betas=(0.5, 0.999),
-                                                       capturable=self._graph_d, fused=self._fused_adam))
-        if self.netsD:
+                self.optsD.append(self._adam(self.bucketsD[-1], d.parameters(), d_lr or cfg.TRAIN.DISCRIMINATOR_LR, self._graph_d))
+                self._d_bump.append(list(self.bucketsD[-1].params) + list(d.buffers()))
             # the generator loss runs the train-mode discriminators on the fake images once more (g_loss): their running
             # statistics move again, per rank, AFTER their own bucket's all-reduce - so they also ride the generators' bucket
             # and every rank leaves the step with the same discriminator buffers (a snapshot is the same file on every rank)
             self._bucket_bufs = self._bucket_bufs + [b for d in self.netsD for b in d.buffers()]
         self.bucket = FlatGradBucket(gh_params + list(self.netGL.parameters()), buffers=self._bucket_bufs).attach()
         self._early_hi = self.bucket.offsets[self._early_n][0] if self._early_n < len(self.bucket.params) else self.bucket.numel
-        if self._flat_adam:
-            from .optim import FlatAdam
-            self.opt = FlatAdam(self.bucket.params, self.bucket.flat, lr=self._g_lr, betas=(0.5, 0.999))
-        else:
-            self.opt = torch.optim.Adam(self.params, lr=self._g_lr, betas=(0.5, 0.999), fused=self._fused_adam,
-                                        capturable=self._graph_capable)
+        self.opt = self._adam(self.bucket, self.params, self._g_lr, self._graph_capable)
+        # what a replayed (or fused-Adam) update writes without telling autograd's version counters (`_bump`)
+        self._g_bump = list(self.params) + list(self._bucket_bufs)
         # TGSR_COMM=direct: the buckets' closing all-reduce through the library's own RCCL communicator (tgsr_allreduce_flat,
         # parallel.RcclDirect) instead of torch.distributed's; the early range and the DAMSM gather stay on the process group
         self._rccl = None
-        if os.environ.get("TGSR_COMM", "") == "direct" and self.device.type == "cuda":
-            from .parallel import RcclDirect, dp_world
-            if dp_world() > 1:
-                self._rccl = RcclDirect.create()
-                self._early_on = False
-                for b in [self.bucket] + self.bucketsD:
-                    b.comm = self._rccl
-        taken = cur + ([self._wside.cuda_stream] if self._wside is not None else []) + \
-            ([self._comm.cuda_stream] if self._comm is not None else [])
-        self._dstreams = distinct_streams(len(self.netsD), self.device, avoid=taken) \
-            if self.device.type == "cuda" and self.netsD and os.environ.get("TGSR_D_STREAMS", "1") != "0" else []
-        taken = taken + [st.cuda_stream for st in self._dstreams]
+        if os.environ.get("TGSR_COMM", "") == "direct" and cuda and dp_world() > 1:
+            self._rccl = RcclDirect.create()
+            self._early_on = False
+            for b in [self.bucket] + self.bucketsD:
+                b.comm = self._rccl
+        # Every stream of the trainer, each distinct from the current one and from all handed out before it
+        # (distinct_streams: torch hands out pool streams round robin - two "new" streams can be the same hip stream)
+        taken = [torch.cuda.current_stream(self.device).cuda_stream] if cuda else []
+
+        def streams(n):
+            out = distinct_streams(n, self.device, avoid=taken)
+            taken.extend(st.cuda_stream for st in out)
+            return out
+        # the generators' weight gradients run on a side stream beside the data-gradient chain while a step's backward
+        # is in flight (12.7 -> 11.7 ms per step at B=16: the small layers' weight-gradient kernels and the slab sums
+        # fill a fraction of the CUs); TGSR_WGRAD_SIDE=0 keeps everything on one stream
+        self._wside = streams(1)[0] if cuda and os.environ.get("TGSR_WGRAD_SIDE", "1") != "0" else None
+        self._comm = streams(1)[0] if cuda else None                     # the early all-reduce (`_fire_early`)
+        self._dstreams = streams(len(self.netsD)) if cuda and self.netsD and os.environ.get("TGSR_D_STREAMS", "1") != "0" else []
         # TGSR_D_WGRAD_SIDE=1 (opt-in): each discriminator's weight gradients on a side stream of its own, beside its data-gradient
         # chain - the 256^2 discriminator's update is the longest dependent chain of a G/D step and a quarter of its backward
         # kernels are weight gradients nothing waits for until Adam.  Built, bit-identical (the gan / dp suites pass with it), and
         # SLOWER on this chip: 20.8 against 19.6 ms per G/D step, 31.9 against 30.3 with the ranking term (same box) - the three
         # updates already run side by side, and six streams compete for four hardware queues (GPU_MAX_HW_QUEUES=8 is worse
         # still: 43.6 ms).  Left off.
-        self._dwside = distinct_streams(len(self._dstreams), self.device, avoid=taken) \
-            if self._dstreams and os.environ.get("TGSR_D_WGRAD_SIDE", "0") == "1" else []
-        taken = taken + [st.cuda_stream for st in self._dwside]
+        self._dwside = streams(len(self._dstreams)) if self._dstreams and os.environ.get("TGSR_D_WGRAD_SIDE", "0") == "1" else []
         # TGSR_ENC_EARLY=1 (opt-in): generator_loss's image encoder (CNN_ENCODER: ~190 launches of small GEMMs forward) reads the fake
         # image only - not the discriminators - so it can be issued BEFORE the discriminator updates, on a stream of its own (as a
         # hipGraph of its own when the step is replayed), and run beside them; its backward stays where it was.  Built, parity-green
         # (the early forms, eager and replayed, are bit-identical; against the late form the fake image's gradient adds its terms in
         # another order) and NOT faster: 29.6 / 29.8 against 28.7 / 29.6 ms (two pairs, one box) - "one kernel in flight" during the
         # 256^2 discriminator's update does not mean idle CUs: its GEMMs fill the chip, and the encoder's kernels only lengthen them.
-        self._encst = distinct_streams(1, self.device, avoid=taken)[0] \
-            if (self.device.type == "cuda" and image_encoder is not None and self.netsD and
-                os.environ.get("TGSR_ENC_EARLY", "0") == "1") else None
-        if self._encst is not None:
-            taken = taken + [self._encst.cuda_stream]
+        self._encst = streams(1)[0] if (cuda and image_encoder is not None and self.netsD and
+                                        os.environ.get("TGSR_ENC_EARLY", "0") == "1") else None
         # the stream the generators' graphs are captured on, and the branch their re-pack launches fork onto
-        self._gcap, self._gpack = distinct_streams(2, self.device, avoid=taken) if self._graph_capable else (None, None)
+        self._gcap, self._gpack = streams(2) if self._graph_capable else (None, None)
 
+    def _adam(self, bucket, params, lr, capturable):
+        """FlatAdam over this bucket (TGSR_FLAT_ADAM), else torch's Adam over `params`: Adam(lr, betas (0.5, 0.999)) either way."""
+        if self._flat_adam:
+            return FlatAdam(bucket.params, bucket.flat, lr=lr, betas=(0.5, 0.999))
+        return torch.optim.Adam(params, lr=lr, betas=(0.5, 0.999), capturable=capturable, fused=self._fused_adam)
+
+    # ------------------------------------------------------------------ TGSR_GRAPH_G: the form of the generators' update (GraphPolicy)
     @property
     def _graph_g(self):
-        return self._graph_g_value
+        return self._policy.graph
 
     @_graph_g.setter
     def _graph_g(self, v):
-        self._graph_g_value = bool(v)
-        self._auto = None                    # an explicit choice ends the measured policy
+        self._policy.pin(v)                  # an explicit choice ends the measured policy
 
-    # ------------------------------------------------------------------ TGSR_GRAPH_G=auto: the faster form, measured
-    def _auto_begin(self):
-        """Called at the top of a step: which form this step takes while the policy is still measuring (None = settled), and the
-        start of its clock.  Steps [WARMUP, WARMUP + TRIALS) are timed eager, step WARMUP + TRIALS captures (untimed), the next
-        TRIALS are timed replays; then `_auto_end` decides."""
-        a = self._auto
-        if a is None:
-            return
-        k = self._gsteps
-        a["form"] = "eager" if k < GRAPH_G_WARMUP + GRAPH_G_TRIALS else "replay"
-        timed = GRAPH_G_WARMUP <= k and k != GRAPH_G_WARMUP + GRAPH_G_TRIALS
-        if timed:
-            torch.cuda.synchronize(self.device)
-            a["t0"] = time.perf_counter()
-        else:
-            a["t0"] = None
+    @property
+    def _auto(self):
+        """The policy while it is still measuring, None once it has settled or was pinned."""
+        return self._policy if self._policy.measuring else None
 
-    def _auto_end(self, replayed):
-        a = self._auto
-        if a is None:
-            return
-        if a["t0"] is not None:
-            torch.cuda.synchronize(self.device)
-            dt = time.perf_counter() - a["t0"]
-            if a["form"] == "replay":
-                a["replay_s"].append(dt if replayed else float("inf"))     # (the capture failed or the configuration has none)
-            else:
-                a["eager_s"].append(dt)
-        if self._gsteps < GRAPH_G_SETTLED:
-            return
-        import statistics
-        inf = float("inf")
-        te = statistics.median(a["eager_s"]) if a["eager_s"] else inf      # (steps that raised may have left a form untimed)
-        tp = statistics.median(a["replay_s"]) if a["replay_s"] else inf
-        from .parallel import dp_world
+    @property
+    def graph_policy(self):
+        return self._policy.report
+
+    def _idle_clock(self):
+        torch.cuda.synchronize(self.device)
+        return time.perf_counter()
+
+    def _max_over_ranks(self, te, tp):
         if dp_world() > 1:
-            import torch.distributed as dist
             t = torch.tensor([te, tp], dtype=torch.float64, device=self.device if dist.get_backend() == "nccl" else "cpu")
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             te, tp = float(t[0]), float(t[1])
-        if te == inf:                                               # nothing to compare with: the first guess stands
-            self._graph_g = self._graph_g_value
-            self.graph_policy["chosen"] = "replay" if self._graph_g_value else "eager"
-            return
-        self._graph_g = tp <= te                                            # (the setter ends the measurement)
-        self.graph_policy.update({"eager_ms": round(te * 1e3, 3), "replay_ms": None if tp == float("inf") else round(tp * 1e3, 3),
-                                  "chosen": "replay" if tp <= te else "eager",
-                                  "trials": "median of %d steps of each form, device idle on both sides" % GRAPH_G_TRIALS})
+        return te, tp
 
     # ------------------------------------------------------------------ gradient all-reduce under the tail of backward
     def _arm_early(self):
-        from .parallel import dp_world
         self._early = None
         self._early_left = self._early_n if (self._early_on and dp_world() > 1 and self._comm is not None) else -1
 
@@ -367,7 +389,6 @@ class SRTrainer:
     @contextlib.contextmanager
     def _use_packs(self):
         """Scope in which the conv blocks take their packed weights from this trainer's autograd.PackCache."""
-        from . import autograd
         prev, autograd._PACKS = autograd._PACKS, self._packs
         try:
             yield
@@ -375,45 +396,18 @@ class SRTrainer:
             autograd._PACKS = prev
 
     @contextlib.contextmanager
-    def _wgrad_side(self):
-        """Scope in which autograd.ConvBnAct issues its weight gradients on this trainer's side stream; the stream is
-        joined on exit, before anything reads the gradients."""
-        from . import autograd
-        if self._wside is None:
+    def _wgrad_side(self, stream=None, bucket=None):
+        """Scope in which autograd.ConvBnAct issues its weight gradients on `stream` and they land in `bucket` (default: this
+        trainer's side stream and the generators' bucket; a discriminator's update passes its own pair).  The stream is joined into
+        the CURRENT stream on exit, before anything closes, reduces or reads the bucket; no stream: nothing to do."""
+        if bucket is None:
+            stream, bucket = self._wside, self.bucket
+        if stream is None:
             yield
             return
-        idx = self.device.index if self.device.index is not None else torch.cuda.current_device()
-        autograd.WGRAD_SIDE[idx] = self._wside
-        ok = False
-        try:
-            yield
-            ok = True
-        finally:
-            autograd.WGRAD_SIDE.pop(idx, None)
-            torch.cuda.current_stream(self.device).wait_stream(self._wside)      # the join comes first ...
-            if not ok:
-                autograd._ADOPTED.clear()
-        # ... then the check that autograd adopted every side-stream gradient in place.  A failure means the step's gradients
-        # are INVALID (an accumulation kernel read a slot the side stream was still writing): the bucket is zeroed so that
-        # nothing downstream (all-reduce, optimizer) can consume them, and the error propagates - the caller skips the step.
-        try:
-            autograd.check_adopted()
-        except Exception:
-            self.bucket.flat.zero_()
-            raise
-
-    @contextlib.contextmanager
-    def _d_wgrad_side(self, i):
-        """`_wgrad_side` for discriminator i's update: its weight gradients on the discriminator's side stream, joined into the
-        CURRENT stream (the discriminator's own) on exit, before the bucket is closed, reduced or read."""
-        from . import autograd
-        if not self._dwside:
-            yield
-            return
-        side = self._dwside[i]
         idx = self.device.index if self.device.index is not None else torch.cuda.current_device()
         prev = autograd.WGRAD_SIDE.get(idx)
-        autograd.WGRAD_SIDE[idx] = side
+        autograd.WGRAD_SIDE[idx] = stream
         ok = False
         try:
             yield
@@ -423,14 +417,31 @@ class SRTrainer:
                 autograd.WGRAD_SIDE.pop(idx, None)
             else:
                 autograd.WGRAD_SIDE[idx] = prev
-            torch.cuda.current_stream(self.device).wait_stream(side)
+            torch.cuda.current_stream(self.device).wait_stream(stream)          # the join comes first ...
             if not ok:
                 autograd._ADOPTED.clear()
+        # ... then the check that autograd adopted every side-stream gradient in place.  A failure means the step's gradients
+        # are INVALID (an accumulation kernel read a slot the side stream was still writing): the bucket is zeroed so that
+        # nothing downstream (all-reduce, optimizer) can consume them, and the error propagates - the caller skips the step.
         try:
             autograd.check_adopted()
         except Exception:
-            self.bucketsD[i].flat.zero_()
+            bucket.flat.zero_()
             raise
+
+    @contextlib.contextmanager
+    def _frozen_discriminators(self):
+        """Scope in which the discriminators only pass the gradient through to the images: the generator loss runs through them,
+        but their own parameter gradients would be discarded (the next discriminator update zeroes its bucket first), so they
+        are not computed."""
+        d_params = [p for b in self.bucketsD for p in b.params]
+        for p in d_params:
+            p.requires_grad_(False)
+        try:
+            yield
+        finally:
+            for p in d_params:
+                p.requires_grad_(True)
 
     # ------------------------------------------------------------------ updates replayed from hipGraphs
     @staticmethod
@@ -442,56 +453,75 @@ class SRTrainer:
         ids = tuple(int(st[k].data_ptr()) for k in ("exp_avg", "exp_avg_sq", "step") if torch.is_tensor(st.get(k)))
         return (id(o), ids) + tuple((g["lr"], tuple(g["betas"]), g["eps"], g["weight_decay"]) for g in o.param_groups)
 
-    def _d_hyper(self, i):
-        return self._opt_key(self.optsD[i])
-
-    def _bump_d(self, i):
+    @staticmethod
+    def _bump(tensors):
         """A replayed (or fused-Adam) update wrote parameters and running statistics without telling autograd's version counters,
         which every cache of derived tensors keys on (util._FusedParams, PackCache.get, ...)."""
-        if self._d_bump[i] is None:
-            self._d_bump[i] = list(self.bucketsD[i].params) + [b for b in self.netsD[i].buffers()]
-        torch.autograd.graph.increment_version(self._d_bump[i])
+        torch.autograd.graph.increment_version(tensors)
 
-    def _bump_g(self):
-        if self._g_bump is None:
-            self._g_bump = list(self.params) + list(self._bucket_bufs)
-        torch.autograd.graph.increment_version(self._g_bump)
+    def _capture_update(self, buf, refresh, bucket, stream, hyper, loss_fn, finish, message, before=()):
+        """One optimizer update captured for replay (nothing executes here: stream capture records).  `buf` holds the static input
+        buffers, clones the caller made; `refresh` names those that take new values before every replay (`_load`: one copy).
+        The segments, in one memory pool, recorded on `stream` unless they name their own:
+            `before`  [(name, stream, fn)], ahead of the update (a stream other than `stream` is forked from it and joined back);
+            "fb"      zero `bucket`, `loss_fn()` -> the loss (forward, loss, backward: gradients in place), close the bucket;
+            -- the bucket's all-reduce, eager, when there is more than one rank (`_replay_update`) --
+            "opt"     `finish()`: the optimizer and whatever follows it      (one rank: the tail of "fb", buf["opt"] stays None).
+        `hyper` is what the capture bakes in beside the shapes (`_opt_key`): whoever keeps the capture drops it when that changes.
+        Returns `buf` with the graphs and the loss buffer "err" - or False after a failure: the bucket is closed if it was open,
+        `message` says why, and the update stays eager (the eager path is always there)."""
+        split = dp_world() > 1                               # the all-reduce sits between the two segments
+        pool = torch.cuda.graph_pool_handle()
+        buf.update(hyper=hyper, opt=None, dst=[t for k in refresh for t in (buf[k] if isinstance(buf[k], list) else [buf[k]])])
+        opened, loss = False, None                           # (the loss, and with it its autograd graph, lives until the capture is over)
 
-    def _d_update_eager(self, i, fake, real, sent, real_labels, fake_labels):
-        d, b, o = self.netsD[i], self.bucketsD[i], self.optsD[i]
-        b.begin_step()
-        e = losses.discriminator_loss(d, real, fake, sent, real_labels, fake_labels)
-        with self._d_wgrad_side(i):
-            e.backward()
-        b.end_step()
-        b.all_reduce_mean()
-        o.step()
-        self._bump_d(i)
-        return e
+        def record(name, fn, st=stream):
+            buf[name] = torch.cuda.CUDAGraph()
+            if st is not stream:
+                st.wait_stream(stream)
+            with torch.cuda.graph(buf[name], stream=st, pool=pool):
+                fn()
+            if st is not stream:
+                stream.wait_stream(st)
 
-    def _d_update_graphed(self, i, fake, real, sent, real_labels, fake_labels):
-        """Discriminator i's update from its hipGraphs (captured on first use, on the discriminator's own stream, which is the
-        current one): the inputs are copied into the capture's buffers; segment "fb" zeroes the gradient bucket and runs forward,
-        loss and backward, the bucket's all-reduce follows on the same stream when there is more than one rank, segment "opt" is
-        Adam (one rank: one graph holds both).  Returns the loss (a buffer of the capture: valid until the next replay).  A batch
-        of another shape, or a capture that failed once, takes the eager update."""
-        g = self._dgraphs[i]
-        if g not in (None, False) and g["hyper"] != self._d_hyper(i):
-            g = self._dgraphs[i] = None                     # lr / betas / eps / the moment tensors changed since the capture: capture again
-        if g not in (None, False) and (tuple(fake.shape) != tuple(g["fake"].shape) or tuple(sent.shape) != tuple(g["sent"].shape)):
-            return self._d_update_eager(i, fake, real, sent, real_labels, fake_labels)
-        if g is None:
-            g = self._dgraphs[i] = self._capture_d_update(i, fake, real, sent, real_labels, fake_labels)
-        if g is False:                                       # the capture failed once: eager from then on
-            return self._d_update_eager(i, fake, real, sent, real_labels, fake_labels)
+        def fb():
+            nonlocal opened, loss
+            bucket.begin_step()
+            opened = True
+            loss = loss_fn()
+            bucket.end_step()
+            opened = False
+            if not split:
+                finish()
+            buf["err"] = loss.detach()
+
+        try:
+            for name, st, fn in before:
+                record(name, fn, st)
+            record("fb", fb)
+            if split:
+                record("opt", finish)
+        except Exception as ex:                               # noqa: BLE001
+            warnings.warn(message % (type(ex).__name__, ex))
+            if opened:
+                bucket.end_step()                             # close whatever begin_step opened
+            return False
+        return buf
+
+    @staticmethod
+    def _load(cap, srcs):
         with torch.no_grad():
-            torch._foreach_copy_([g["fake"], g["real"], g["sent"]], [fake.detach(), real, sent.detach()])
-        g["fb"].replay()
-        if g["opt"] is not None:
-            self.bucketsD[i].all_reduce_mean()
-            g["opt"].replay()
-        self._bump_d(i)
-        return g["err"]
+            torch._foreach_copy_(cap["dst"], srcs)
+
+    def _replay_update(self, cap, bucket, bump):
+        """Segments "fb" [-> all-reduce] -> "opt" of a captured update on the current stream; returns the loss (a buffer of the
+        capture: valid until the next replay)."""
+        cap["fb"].replay()
+        if cap["opt"] is not None:
+            bucket.all_reduce_mean()
+            cap["opt"].replay()
+        self._bump(bump)
+        return cap["err"]
 
     def reset_d_graphs(self):
         """Forget the captured updates (they are also dropped by themselves when an optimizer's hyper-parameters or state
@@ -499,52 +529,56 @@ class SRTrainer:
         self._dgraphs = [None] * len(self.netsD)
         self._ggraphs = {}
 
-    def _capture_d_update(self, i, fake, real, sent, real_labels, fake_labels):
-        from .parallel import dp_world
-        d, b, o, st = self.netsD[i], self.bucketsD[i], self.optsD[i], self._dstreams[i]
-        buf = {"fake": fake.detach().clone(), "real": real.clone(), "sent": sent.detach().clone(),
-               "rl": real_labels.clone(), "fl": fake_labels.clone(), "hyper": self._d_hyper(i), "opt": None}
-        split = dp_world() > 1                               # the all-reduce sits between the two segments
-        pool = torch.cuda.graph_pool_handle()
-        fb = torch.cuda.CUDAGraph()
-        try:
-            with torch.cuda.graph(fb, stream=st, pool=pool):
-                b.begin_step()
-                e = losses.discriminator_loss(d, buf["real"], buf["fake"], buf["sent"], buf["rl"], buf["fl"])
-                with self._d_wgrad_side(i):
-                    e.backward()
-                b.end_step()
-                if not split:
-                    o.step()
-                buf["err"] = e.detach()
-            if split:
-                buf["opt"] = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(buf["opt"], stream=st, pool=pool):
-                    o.step()
-        except Exception as ex:                               # noqa: BLE001 - the eager path is always there
-            import warnings
-            warnings.warn("discriminator %d: the update could not be captured (%s: %s); it stays eager" % (i, type(ex).__name__, ex))
-            b.end_step()                                      # close whatever begin_step opened
-            return False
-        buf["fb"] = fb
-        return buf
+    def _d_update(self, i, graphed, fake, real, sent, real_labels, fake_labels):
+        """Discriminator i's update on the current stream (the discriminator's own): zero its bucket, forward on (real,
+        fake.detach()), loss, backward, all-reduce, Adam.  `graphed`: from its hipGraphs (`_capture_update`, captured on first use;
+        the loss returned is then a buffer of the capture).  A batch of another shape, or a capture that failed once, takes the
+        eager update."""
+        d, b, o = self.netsD[i], self.bucketsD[i], self.optsD[i]
+
+        def loss_backward(real, fake, sent, rl, fl):
+            e = losses.discriminator_loss(d, real, fake, sent, rl, fl)
+            with self._wgrad_side(self._dwside[i] if self._dwside else None, b):
+                e.backward()
+            return e
+
+        g = self._dgraphs[i] if graphed else False
+        if g and g["hyper"] != self._opt_key(o):
+            g = self._dgraphs[i] = None                     # lr / betas / eps / the moment tensors changed since the capture: capture again
+        if g and (tuple(fake.shape) != tuple(g["fake"].shape) or tuple(sent.shape) != tuple(g["sent"].shape)):
+            g = False
+        if g is None:
+            buf = {"fake": fake.detach().clone(), "real": real.clone(), "sent": sent.detach().clone(),
+                   "rl": real_labels.clone(), "fl": fake_labels.clone()}
+            g = self._dgraphs[i] = self._capture_update(
+                buf, ("fake", "real", "sent"), b, self._dstreams[i], self._opt_key(o),
+                lambda: loss_backward(buf["real"], buf["fake"], buf["sent"], buf["rl"], buf["fl"]), o.step,
+                "discriminator %d: the update could not be captured (%%s: %%s); it stays eager" % i)
+        if not g:
+            b.begin_step()
+            e = loss_backward(real, fake, sent, real_labels, fake_labels)
+            b.end_step()
+            b.all_reduce_mean()
+            o.step()
+            self._bump(self._d_bump[i])
+            return e
+        self._load(g, [fake.detach(), real, sent.detach()])
+        return self._replay_update(g, b, self._d_bump[i])
 
     # ------------------------------------------------------------------ the generators' update from hipGraphs
     def _g_key(self, gan, LR, words_embs, cap_lens, class_ids):
-        from .parallel import dp_world
         key = (bool(gan), tuple(LR.shape), int(words_embs.shape[2]), dp_world())
         if self.image_encoder is not None:
             # the DAMSM kernels take the caption lengths (and the class mask) as launch arguments: part of what a capture bakes in
-            import numpy as np
             key += (tuple(int(v) for v in cap_lens),
                     None if class_ids is None else tuple(int(v) for v in np.asarray(class_ids).ravel()))
         return key
 
     def _g_graphs(self, gan, LR, LRb, hr_pyramid, words_embs, sent_emb, mask, cap_lens, class_ids):
         """The captured update for this step's shapes: a dict of graphs and their static buffers, or None = take the eager step
-        (warm-up, switched off, a configuration that needs a collective inside the loss, or a capture that failed)."""
-        from .parallel import dp_world
-        use = (self._graph_g if self._auto is None else self._auto["form"] == "replay") and self._gsteps >= GRAPH_G_WARMUP
+        (warm-up, switched off, a configuration that needs a collective inside the loss, or a capture that failed).  A change of
+        the optimizer's state or hyper-parameters drops every shape's capture, the failed ones included."""
+        use = self._policy.replays(self._gsteps)
         self._gsteps += 1
         if not use or (self.image_encoder is not None and self.gather_negatives and dp_world() > 1):
             return None                     # (DAMSM on the gathered global batch all-gathers inside generator_loss)
@@ -597,94 +631,59 @@ class SRTrainer:
         if captured and self._packs is not None:
             torch.cuda.current_stream(self.device).wait_stream(self._gpack)      # join the pack branch before the capture ends
 
+    def _g_loss_backward(self, gan, nets, LR, LRb, words_embs, sent_emb, mask, cap_lens, hr_pyramid, class_ids, enc_out=None,
+                         early=True):
+        """With the generators' bucket open: [both generators forward,] the loss, backward.  G/D alternation: `nets`, the
+        generators' outputs, were computed ahead of the discriminator updates, and the loss runs through the frozen
+        discriminators.  Returns (errG, nets)."""
+        if gan:
+            with self._frozen_discriminators():
+                errG = self.g_loss(*nets, words_embs, sent_emb, cap_lens, hr_pyramid, class_ids, enc_out=enc_out)
+                self._g_backward(errG, early)
+        else:
+            with self._use_packs():
+                nets = self._forward_nets(LR, LRb, words_embs, sent_emb, mask)
+                errG = self._loss_from(*nets, words_embs, sent_emb, cap_lens, hr_pyramid, class_ids)
+            self._g_backward(errG, early)
+        return errG, nets
+
     def _capture_g(self, gan, LR, LRb, hr_pyramid, words_embs, sent_emb, mask, cap_lens, class_ids):
-        """Capture the generators' update for one batch shape.  Nothing executes here (stream capture records); `_g_run` replays.
-        Segments, all in one memory pool, the autograd graph of "fwd" alive while "fb" is recorded:
+        """Capture the generators' update for one batch shape (`_capture_update`; `_step` replays).  Its segments, the autograd graph
+        of "fwd" alive while "fb" is recorded:
             "fwd" (G/D alternation only)  both generators forward - the discriminator updates run between it and "fb";
+            "enc" (TGSR_ENC_EARLY)        the image encoder's forward, captured on ITS stream as the origin (its branch forks are then
+                                          plain diamonds) and replayed beside the discriminators' graphs; its autograd node stays alive;
             "fb"   zero the bucket, [forward,] losses, backward (weight gradients on the side branch), gradients in place;
-            -- the bucket's all-reduce, eager, when there is more than one rank --
-            "opt"  fused Adam, every weight pack re-derived (a branch of its own), EMA      (one rank: part of "fb")."""
-        from .parallel import dp_world
-        split = dp_world() > 1
-        st = self._gcap
+            "opt"  fused Adam, every weight pack re-derived (a branch of its own, joined before the capture ends), EMA."""
         buf = {"LR": LR.clone(), "LRb": LRb.clone(), "hr": [h.clone() for h in hr_pyramid], "words": words_embs.clone(),
-               "sent": sent_emb.clone(), "mask": mask.clone(), "fwd": None, "opt": None, "enc": None}
-        buf["dst"] = [buf["LR"], buf["LRb"], buf["words"], buf["sent"], buf["mask"]] + buf["hr"]
-        pool = torch.cuda.graph_pool_handle()
+               "sent": sent_emb.clone(), "mask": mask.clone(), "fwd": None, "enc": None}
         cap_lens = [int(v) for v in cap_lens]
-        d_params = [p for b in self.bucketsD for p in b.params]
         if self._packs is not None:
             self._packs.settle(self.device)
-        opened = False
-        try:
-            if gan:
-                buf["fwd"] = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(buf["fwd"], stream=st, pool=pool):
-                    with self._use_packs():
-                        nets = self._forward_nets(buf["LR"], buf["LRb"], buf["words"], buf["sent"], buf["mask"])
-                buf["fine"] = nets[1]
-                if self._encst is not None:
-                    # the image encoder's forward as a graph of its own, captured on ITS stream as the origin (its branch forks are
-                    # then plain diamonds) and replayed beside the discriminators' graphs; its autograd node stays alive for "fb"
-                    buf["enc"] = torch.cuda.CUDAGraph()
-                    self._encst.wait_stream(st)
-                    with torch.cuda.graph(buf["enc"], stream=self._encst, pool=pool):
-                        buf["enc_out"] = self.image_encoder(nets[1][len(self.netsD) - 1])
-                    st.wait_stream(self._encst)
-            fb = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(fb, stream=st, pool=pool):
-                self.bucket.begin_step()
-                opened = True
-                if gan:
-                    for p in d_params:
-                        p.requires_grad_(False)
-                    errG = self.g_loss(nets[0], nets[1], nets[2], nets[3], buf["words"], buf["sent"], cap_lens, buf["hr"], class_ids,
-                                       enc_out=buf.get("enc_out"))
-                else:
-                    with self._use_packs():
-                        nets = self._forward_nets(buf["LR"], buf["LRb"], buf["words"], buf["sent"], buf["mask"])
-                        errG = self._loss_from(nets[0], nets[1], nets[2], nets[3], buf["words"], buf["sent"], cap_lens, buf["hr"],
-                                               class_ids)
-                self._g_backward(errG, early=False)
-                self.bucket.end_step()
-                opened = False
-                if not split:
-                    self._g_finish(captured=True)
-                buf["err"] = errG.detach()
-            if split:
-                buf["opt"] = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(buf["opt"], stream=st, pool=pool):
-                    self._g_finish(captured=True)
-        except Exception as ex:                               # noqa: BLE001 - the eager path is always there
-            import warnings
-            warnings.warn("the generators' update could not be captured (%s: %s); it stays eager" % (type(ex).__name__, ex))
-            if opened:
-                self.bucket.end_step()
-            return False
-        finally:
-            for p in d_params:
-                p.requires_grad_(True)
-        buf["fb"] = fb
-        del nets, errG
-        return buf
+        live = []                                            # the networks' outputs, alive until the capture is over
+        before = []
 
-    def _g_load(self, g, LR, LRb, hr_pyramid, words_embs, sent_emb, mask):
-        with torch.no_grad():
-            torch._foreach_copy_(g["dst"], [LR, LRb, words_embs, sent_emb, mask] + list(hr_pyramid))
-        if self._packs is not None:
-            self._packs.settle(self.device)
+        def fwd():
+            with self._use_packs():
+                live.append(self._forward_nets(buf["LR"], buf["LRb"], buf["words"], buf["sent"], buf["mask"]))
+            buf["fine"] = live[0][1]
 
-    def _g_update_replay(self, g):
-        """Segments "fb" [-> all-reduce] -> "opt" of a captured update; returns the loss (a buffer of the capture)."""
-        g["fb"].replay()
-        if g["opt"] is not None:
-            self._early, self._early_left = None, -1
-            self.bucket.all_reduce_mean()
-            g["opt"].replay()
-        self._bump_g()
-        if self._packs is not None:
-            self._packs.mark_fresh()
-        return g["err"]
+        def enc():
+            buf["enc_out"] = self.image_encoder(buf["fine"][len(self.netsD) - 1])
+
+        def loss_backward():
+            errG, nets = self._g_loss_backward(gan, live[0] if gan else None, buf["LR"], buf["LRb"], buf["words"], buf["sent"], buf["mask"],
+                                               cap_lens, buf["hr"], class_ids, enc_out=buf.get("enc_out"), early=False)
+            live.append(nets)
+            return errG
+
+        if gan:
+            before.append(("fwd", self._gcap, fwd))
+            if self._encst is not None:
+                before.append(("enc", self._encst, enc))
+        return self._capture_update(buf, ("LR", "LRb", "words", "sent", "mask", "hr"), self.bucket, self._gcap, self._ghyper,
+                                    loss_backward, lambda: self._g_finish(captured=True),
+                                    "the generators' update could not be captured (%s: %s); it stays eager", before)
 
     def _d_updates(self, fine_im, hr_pyramid, sent_emb):
         """Every discriminator's update on (real, fake.detach()): each on a stream of its own - replayed from its hipGraphs once
@@ -694,7 +693,7 @@ class SRTrainer:
         B = sent_emb.shape[0]
         real_labels, fake_labels, _ = prepare_labels(B, self.device)
         if not self._dstreams:
-            return [self._d_update_eager(i, fine_im[i], hr_pyramid[i], sent_emb, real_labels, fake_labels)
+            return [self._d_update(i, False, fine_im[i], hr_pyramid[i], sent_emb, real_labels, fake_labels)
                     for i in range(len(self.netsD))]
         # the three discriminators are independent of each other: each one's forward, backward, all-reduce and Adam
         # step run on a stream of their own (the 64^2 / 128^2 discriminators' layers leave most CUs idle)
@@ -705,84 +704,67 @@ class SRTrainer:
             with torch.cuda.stream(st):
                 for t in (fine_im[i], hr_pyramid[i], sent_emb):
                     t.record_stream(st)
-                upd = self._d_update_graphed if graphed else self._d_update_eager
-                errsD.append(upd(i, fine_im[i], hr_pyramid[i], sent_emb, real_labels, fake_labels))
+                errsD.append(self._d_update(i, graphed, fine_im[i], hr_pyramid[i], sent_emb, real_labels, fake_labels))
         for st in self._dstreams:
             main.wait_stream(st)
         return errsD
+
+    def _step(self, gan, captions, cap_lens, LR, LRb, hr_pyramid, class_ids):
+        """One step of either kind: (errG, [errD_i]), detached (buffers of the captures when the step is replayed).  gan: both
+        generators forward once, every discriminator's update on (real, fake.detach()) - the image encoder's forward beside them
+        when it runs early - then the generators' update through the UPDATED discriminators on the same fake images."""
+        k = self._gsteps
+        self._policy.begin(k)
+        words_embs, sent_emb, mask = self._text(captions, cap_lens)
+        g = self._g_graphs(gan, LR, LRb, hr_pyramid, words_embs, sent_emb, mask, cap_lens, class_ids)
+        errsD, nets, enc_out = [], None, None
+        if g is not None:
+            self._load(g, [LR, LRb, words_embs, sent_emb, mask] + list(hr_pyramid))
+            if self._packs is not None:
+                self._packs.settle(self.device)
+            if gan:
+                g["fwd"].replay()
+                if g["enc"] is not None:                        # the image encoder's forward beside the discriminator updates
+                    self._encst.wait_stream(torch.cuda.current_stream(self.device))
+                    with torch.cuda.stream(self._encst):
+                        g["enc"].replay()
+                errsD = self._d_updates(g["fine"], g["hr"], g["sent"])
+                if g["enc"] is not None:
+                    torch.cuda.current_stream(self.device).wait_stream(self._encst)
+            self._early, self._early_left = None, -1
+            errG = self._replay_update(g, self.bucket, self._g_bump)
+            if self._packs is not None:
+                self._packs.mark_fresh()
+            self._policy.end(k, True)
+            return errG, [e.detach() for e in errsD]
+        if gan:
+            with self._use_packs():
+                nets = self._forward_nets(LR, LRb, words_embs, sent_emb, mask)
+            enc_out = self._encode_early(nets[1][len(self.netsD) - 1])          # beside the discriminator updates
+            errsD = self._d_updates(nets[1], hr_pyramid, sent_emb)
+            self._encode_join(enc_out)
+        self._zero(self.bucket)
+        try:
+            errG, _nets = self._g_loss_backward(gan, nets, LR, LRb, words_embs, sent_emb, mask, cap_lens, hr_pyramid, class_ids, enc_out)
+        finally:
+            self.bucket.end_step()               # also after a failed step: `.grad` views restored, slots closed
+        self._all_reduce()
+        self._g_finish()
+        self._bump(self._g_bump)
+        self._policy.end(k, False)
+        return errG.detach(), [e.detach() for e in errsD]
 
     def step_gan(self, captions, cap_lens, LR, LRb, hr_pyramid, class_ids=None):
         """One G/D alternation: forward the generators once; update every discriminator on (real, fake.detach());
         then update the generators through the UPDATED discriminators on the same fake images.  Returns
         (errG, [errD_i]) as detached tensors (buffers of the captures when the step is replayed: valid until the next step)."""
-        self._auto_begin()
-        words_embs, sent_emb, mask = self._text(captions, cap_lens)
-        g = self._g_graphs(True, LR, LRb, hr_pyramid, words_embs, sent_emb, mask, cap_lens, class_ids)
-        if g is not None:
-            self._g_load(g, LR, LRb, hr_pyramid, words_embs, sent_emb, mask)
-            g["fwd"].replay()
-            if g["enc"] is not None:                        # the image encoder's forward beside the discriminator updates
-                main = torch.cuda.current_stream(self.device)
-                self._encst.wait_stream(main)
-                with torch.cuda.stream(self._encst):
-                    g["enc"].replay()
-            errsD = self._d_updates(g["fine"], g["hr"], g["sent"])
-            if g["enc"] is not None:
-                torch.cuda.current_stream(self.device).wait_stream(self._encst)
-            errG = self._g_update_replay(g)
-            self._auto_end(True)
-            return errG, [e.detach() for e in errsD]
-        with self._use_packs():
-            fake_imgL, fine_im, mu, logvar = self._forward_nets(LR, LRb, words_embs, sent_emb, mask)
-        enc_out = self._encode_early(fine_im[len(self.netsD) - 1])          # beside the discriminator updates
-        errsD = self._d_updates(fine_im, hr_pyramid, sent_emb)
-        self._encode_join(enc_out)
-        self._zero(self.bucket)
-        # the discriminators only pass the gradient through to the images here: their own parameter gradients would be
-        # discarded (the next discriminator update zeroes its bucket first), so they are not computed
-        d_params = [p for b in self.bucketsD for p in b.params]
-        for p in d_params:
-            p.requires_grad_(False)
-        try:
-            errG = self.g_loss(fake_imgL, fine_im, mu, logvar, words_embs, sent_emb, cap_lens, hr_pyramid, class_ids, enc_out=enc_out)
-            self._g_backward(errG)
-        finally:
-            for p in d_params:
-                p.requires_grad_(True)
-            self.bucket.end_step()
-        self._all_reduce()
-        self._g_finish()
-        self._bump_g()
-        self._auto_end(False)
-        return errG.detach(), [e.detach() for e in errsD]
+        return self._step(True, captions, cap_lens, LR, LRb, hr_pyramid, class_ids)
 
     def step(self, captions, cap_lens, LR, LRb, hr_pyramid, class_ids=None):
         """forward + backward + gradient all-reduce (if distributed) + Adam + EMA.  Returns the loss tensor.  With
         discriminators this is `step_gan` (the generator loss is returned).  After GRAPH_G_WARMUP eager steps the update is
         replayed from hipGraphs (`_capture_g`), bit-identical to the eager one."""
-        if self.netsD:
-            return self.step_gan(captions, cap_lens, LR, LRb, hr_pyramid, class_ids)[0]
-        self._auto_begin()
-        words_embs, sent_emb, mask = self._text(captions, cap_lens)
-        g = self._g_graphs(False, LR, LRb, hr_pyramid, words_embs, sent_emb, mask, cap_lens, class_ids)
-        if g is not None:
-            self._g_load(g, LR, LRb, hr_pyramid, words_embs, sent_emb, mask)
-            err = self._g_update_replay(g)
-            self._auto_end(True)
-            return err
-        self._zero(self.bucket)
-        try:
-            with self._use_packs():
-                nets = self._forward_nets(LR, LRb, words_embs, sent_emb, mask)
-                errG = self._loss_from(nets[0], nets[1], nets[2], nets[3], words_embs, sent_emb, cap_lens, hr_pyramid, class_ids)
-            self._g_backward(errG)
-        finally:
-            self.bucket.end_step()               # also after a failed step: `.grad` views restored, slots closed
-        self._all_reduce()
-        self._g_finish()
-        self._bump_g()
-        self._auto_end(False)
-        return errG.detach()
+        return self._step(bool(self.netsD), captions, cap_lens, LR, LRb, hr_pyramid, class_ids)[0]
 
     # ------------------------------------------------------------------ validation, snapshots, resume
     @contextlib.contextmanager
@@ -806,7 +788,7 @@ class SRTrainer:
                 if ema:
                     backup = [p.detach().clone() for p in self.params]
                     torch._foreach_copy_([p.data for p in self.params], self.avg_param_G)
-                    self._bump_g()                           # the eval modules' folded / packed weights key on the version counters
+                    self._bump(self._g_bump)                           # the eval modules' folded / packed weights key on the version counters
             for m in nets:
                 m.eval()
             yield
@@ -814,7 +796,7 @@ class SRTrainer:
             with torch.no_grad():
                 if backup is not None:
                     torch._foreach_copy_([p.data for p in self.params], backup)
-                    self._bump_g()
+                    self._bump(self._g_bump)
             for m, mode in zip(nets, modes):
                 m.train(mode)
             if fresh is not None:
@@ -833,9 +815,6 @@ class SRTrainer:
         Returns {"fine": [per scale], "fake": [per scale]}, per scale {"psnr": [N], "rmse", "psnr_y", "rmse_y", "ssim_y", "n": N,
         "mean": {...}} over the N images seen.  Afterwards the trainer is exactly as it was (`_eval_weights`).
         Data parallel: every rank passes ITS batches; the rows are gathered in rank order and every rank returns the same dict."""
-        from . import metrics
-        from .parallel import dp_world
-        from .trainer import SRPipeline
         if getattr(self, "_eval_pipe", None) is None:
             self._eval_pipe = SRPipeline.from_modules(self.text_encoder, self.netGL, self.netGH, device=self.device)
         book = metrics.ScoreBook(shave)
@@ -852,7 +831,6 @@ class SRTrainer:
                     for i, hr in enumerate(hr_pyramid):
                         book.add((name, i), out[name][i].contiguous(), hr.contiguous())
         if dp_world() > 1:
-            import torch.distributed as dist
             mine = ({s: book.rows(s) for s in book.scales()}, dict(book._size))
             every = [None] * dist.get_world_size()
             dist.all_gather_object(every, mine)
@@ -864,9 +842,7 @@ class SRTrainer:
         return {name: [res[(name, i)] for i in range(nscales)] for name in ("fine", "fake")}
 
     def snapshot_due(self, epoch, max_epoch=None):
-        """The snapshot rule of the reference's training loops (pretrain_DAMSM.py:286-287), for the generators."""
-        max_epoch = cfg.TRAIN.MAX_EPOCH if max_epoch is None else max_epoch
-        return epoch % cfg.TRAIN.SNAPSHOT_INTERVAL == 0 or epoch == max_epoch
+        return snapshot_due(epoch, max_epoch)
 
     @staticmethod
     def snapshot_paths(model_dir, epoch):
@@ -923,7 +899,7 @@ class SRTrainer:
         self.netGH.load_state_dict(sd_h, strict=True)
         with torch.no_grad():
             torch._foreach_copy_(self.avg_param_G, [p.data for p in self.params])
-        self._bump_g()
+        self._bump(self._g_bump)
         if self._packs is not None:
             self._packs.repack(force=True)
         return start
@@ -948,8 +924,7 @@ class DAMSMTrainer:
         if trunk is not None and inception is not None:
             raise ValueError("DAMSMTrainer: pass `trunk` or `inception`, not both")
         self.device = torch.device(device)
-        from . import parallel as _par
-        self.gather_negatives = _par.GATHER_NEGATIVES if gather_negatives is None else bool(gather_negatives)
+        self.gather_negatives = parallel.GATHER_NEGATIVES if gather_negatives is None else bool(gather_negatives)
         self.text_encoder = RNN_ENCODER(n_words, nhidden=cfg.TEXT.EMBEDDING_DIM).to(self.device).train()
         if inception is not None:
             self.image_encoder = CNN_ENCODER(cfg.TEXT.EMBEDDING_DIM, inception=inception).to(self.device)
@@ -1013,15 +988,12 @@ class DAMSMTrainer:
         return self.evaluate_features(through_trunk())
 
     def snapshot_due(self, epoch, max_epoch=None):
-        """pretrain_DAMSM.py:286-287."""
-        max_epoch = cfg.TRAIN.MAX_EPOCH if max_epoch is None else max_epoch
-        return epoch % cfg.TRAIN.SNAPSHOT_INTERVAL == 0 or epoch == max_epoch
+        return snapshot_due(epoch, max_epoch)
 
     def snapshot(self, model_dir, epoch):
         """pretrain_DAMSM.py:288-291: `image_encoder%d.pth` / `text_encoder%d.pth` state_dicts (no optimizer state: the
         reference rebuilds Adam every epoch anyway).  Under data parallelism call it on rank 0 (parameters are identical
         on every rank after the all-reduced step)."""
-        import os
         os.makedirs(model_dir, exist_ok=True)
         pi, pt = "%s/image_encoder%d.pth" % (model_dir, epoch), "%s/text_encoder%d.pth" % (model_dir, epoch)
         torch.save(self.image_encoder.state_dict(), pi)
