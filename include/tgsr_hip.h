@@ -668,6 +668,30 @@ int tgsr_gaussian_blur_u8(const uint8_t* in, int N, int H, int W, int radius, ui
 int tgsr_u8_normalize(const uint8_t* in, float* out, int64_t n, void* stream);
 
 /*
+ * The transform chain in front of that pyramid, for a ragged batch in one call (datasets.py:115-123 bounding-box crop,
+ * transforms.Resize + RandomCrop + RandomHorizontalFlip of test1.py:184-186, Resize + CenterCrop of datasets.py:1558-1560):
+ * per image byte-identical to Pillow's
+ *     img.crop((x1, y1, x2, y2)).resize((ow, oh), BILINEAR).crop((left, top, left + S, top + S))   [mirrored if flip]
+ * of which only the S x S window is computed.
+ *   tgsr_augment_u8     packed: B decoded images back to back, each interleaved uint8 [H][W][3]; nbytes: size of that buffer
+ *       (< 2^31).  table: int32 [B][12] = (byte offset, H, W, x1, y1, x2, y2, oh, ow, top, left, flip), once in host memory
+ *       (table_host, checked here) and once in device memory (table_dev, what the kernels read - they skip an image whose
+ *       descriptor fails the same checks, so no read leaves `packed`).  TGSR_EINVAL unless for every image: H, W in [1, 4096];
+ *       offset >= 0 and offset + 3 H W <= nbytes; 0 <= x1 < x2 <= W, 0 <= y1 < y2 <= H; S <= oh, ow <= 65536;
+ *       0 <= top <= oh - S, 0 <= left <= ow - S; x2 - x1 <= 16 ow and y2 - y1 <= 16 oh (at most 33 taps); flip in {0, 1}.
+ *       ws: tgsr_augment_ws_elems(B, S) int32 (the taps of the window's rows and columns, computed on the device in fp64
+ *       exactly like Pillow's precompute_coeffs).  out: planar uint8 [B][3][S][S].  1 <= S <= 4096, B <= 65535.
+ *       Two launches on `stream`, plain loads and stores only.
+ *   tgsr_resize_coeffs  that coefficient step on its own: bounds int32 [out_size][2] = (first input index, tap count),
+ *       taps int32 [out_size][ksize] in 22-bit fixed point, zero behind the count; ksize must be Pillow's
+ *       2 ceil(max(in_size / out_size, 1)) + 1.  Sizes in [1, 65536], in_size <= 16 out_size.  Both device memory.
+ */
+int64_t tgsr_augment_ws_elems(int B, int S);
+int tgsr_augment_u8(const uint8_t* packed, int64_t nbytes, const int32_t* table_host, const int32_t* table_dev, int B, int S,
+                    int32_t* ws, uint8_t* out, void* stream);
+int tgsr_resize_coeffs(int in_size, int out_size, int ksize, int32_t* bounds, int32_t* taps, void* stream);
+
+/*
  * Image quality of SR output against ground truth, on uint8 images as the reference's caller saves them.
  *   tgsr_sr_metrics  sr, hr: dense NCHW [B][3][H][W], each independently float32 (sr_f32 / hr_f32 != 0: quantised in the kernel
  *       by tgsr_to_uint8's rule) or uint8.  shave >= 0 pixels are removed from every border first; the crop must be at least

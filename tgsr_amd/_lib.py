@@ -141,6 +141,9 @@ SIGNATURES = {
     "tgsr_resize_bilinear_u8": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp]),
     "tgsr_gaussian_blur_u8": (_i, [_vp, _i, _i, _i, _i, ctypes.c_uint32, ctypes.c_uint32, _i, _vp, _vp, _vp]),
     "tgsr_u8_normalize": (_i, [_vp, _vp, _i64, _vp]),
+    "tgsr_augment_ws_elems": (_i64, [_i, _i]),
+    "tgsr_augment_u8": (_i, [_vp, _i64, _vp, _vp, _i, _i, _vp, _vp, _vp]),
+    "tgsr_resize_coeffs": (_i, [_i, _i, _i, _vp, _vp, _vp]),
     "tgsr_to_uint8": (_i, [_vp, _vp, _i64, _vp]),
     "tgsr_sr_metrics_ws_elems": (_i64, [_i, _i, _i, _i]),
     "tgsr_sr_metrics": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp]),

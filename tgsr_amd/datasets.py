@@ -5,6 +5,11 @@
     `transforms.Resize` and `ImageFilter.GaussianBlur` delegate to), restated in integer HIP kernels
     (tgsr_resize_bilinear_u8 / tgsr_gaussian_blur_u8 / tgsr_u8_normalize): byte-identical pyramids, so an end-to-end
     run is no longer bound by the CPU image library.
+  * `RaggedImages`, `DeviceAugment`, `SRBatcher` - what stands in front of that pyramid in the reference's loaders, for a
+    batch of decoded images of different sizes: the CUB bounding-box crop (datasets.py:115-123, `crop_box`),
+    `transforms.Resize` (`resized_size`), RandomCrop + RandomHorizontalFlip (test1.py:184-186) or CenterCrop
+    (datasets.py:1558-1560), fused into one launch that computes only the window (tgsr_augment_u8), byte-identical to the
+    Pillow chain.  A caller's `Dataset.__getitem__` shrinks to "decode, return the array and the bbox".
   * `prepare_data` / `prepare_datablur` - datasets.py:33-109: sort the batch by caption length (descending, the
     pack_padded_sequence order) and move it to the device; same tuple layout as the reference.
   * `load_caption_pickle` - the `[captions, ixtoword, wordtoix]` pickle test1.py:118-127 writes and the datasets read.
@@ -113,6 +118,156 @@ class GpuImagePyramid:
             return ret, bic, retb, bicb
         n = self.normalize
         return [n(t) for t in ret], [n(t) for t in bic], [n(t) for t in retb], [n(t) for t in bicb]
+
+
+def crop_box(bbox, width: int, height: int):
+    """datasets.py:115-123, integer for integer: the square of radius 0.75 max(w, h) about the centre of the CUB bounding
+    box `bbox` = (x, y, w, h), clamped to the image -> (x1, y1, x2, y2) as `img.crop` takes them."""
+    r = int(max(bbox[2], bbox[3]) * 0.75)
+    center_x = int((2 * bbox[0] + bbox[2]) / 2)
+    center_y = int((2 * bbox[1] + bbox[3]) / 2)
+    y1 = max(0, center_y - r)
+    y2 = min(int(height), center_y + r)
+    x1 = max(0, center_x - r)
+    x2 = min(int(width), center_x + r)
+    return int(x1), int(y1), int(x2), int(y2)
+
+
+def resized_size(w: int, h: int, size: int):
+    """torchvision's `Resize(size)` rule for an int size: the shorter side becomes `size`, the other
+    int(size * long / short) -> (ow, oh)."""
+    if w <= h:
+        return int(size), int(size * h / w)
+    return int(size * w / h), int(size)
+
+
+class RaggedImages:
+    """A batch of decoded images of different sizes as ONE buffer: each H x W x 3 uint8 (interleaved, as a decoder leaves
+    it), back to back.  `sizes` = [(H, W)], `offsets` = byte offset of each image, `data` = the flat uint8 buffer.
+
+        batch = RaggedImages.pack(list_of_arrays)             # pinned host buffer + one non_blocking copy to the device
+        DataLoader(..., collate_fn=lambda items: (RaggedImages.pack([it[0] for it in items], device=None), ...))
+                                                              # in a worker: host only; `.to("cuda")` in the main process
+    """
+
+    def __init__(self, data: torch.Tensor, sizes, offsets):
+        self.data, self.sizes, self.offsets = data, list(sizes), list(offsets)
+
+    def __len__(self):
+        return len(self.sizes)
+
+    @property
+    def nbytes(self) -> int:
+        return int(self.data.numel())
+
+    @classmethod
+    def pack(cls, images, device="cuda", pin=None):
+        """images: a list of H x W x 3 uint8 numpy arrays or tensors.  pin: page-lock the host buffer (default: whenever a HIP
+        device is there, so that the copy is asynchronous); device=None keeps the batch on the host."""
+        if len(images) < 1:
+            raise TgsrError("RaggedImages.pack: an empty batch")
+        views, sizes, offsets, n = [], [], [], 0
+        for i, im in enumerate(images):
+            t = im if torch.is_tensor(im) else (torch.from_numpy(np.ascontiguousarray(im)) if isinstance(im, np.ndarray) else None)
+            if t is None or t.dtype != torch.uint8 or t.dim() != 3 or t.shape[2] != 3 or t.shape[0] < 1 or t.shape[1] < 1:
+                raise TgsrError("RaggedImages.pack: image %d is not an H x W x 3 uint8 array (%s)" % (
+                    i, type(im).__name__ if t is None else "%s %s" % (t.dtype, tuple(t.shape))))
+            views.append(t)
+            sizes.append((int(t.shape[0]), int(t.shape[1])))
+            offsets.append(n)
+            n += 3 * sizes[-1][0] * sizes[-1][1]
+        if n >= 2 ** 31:
+            raise TgsrError("RaggedImages.pack: %d bytes in one batch (the descriptors hold int32 offsets)" % n)
+        pin = torch.cuda.is_available() if pin is None else pin
+        host = torch.empty(n, dtype=torch.uint8, pin_memory=bool(pin))
+        for t, (h, w), o in zip(views, sizes, offsets):
+            host[o:o + 3 * h * w].view(h, w, 3).copy_(t)
+        batch = cls(host, sizes, offsets)
+        return batch if device is None else batch.to(device)
+
+    def to(self, device):
+        return RaggedImages(self.data.to(device, non_blocking=True), self.sizes, self.offsets)
+
+
+class DeviceAugment:
+    """The transform chain of the reference's loaders for a ragged batch on the device, in one launch (ops.augment_u8):
+    CUB bounding-box crop (datasets.py:115-123), `Resize(int(imsize * ratio))`, then
+      mode="train": RandomCrop(imsize) + RandomHorizontalFlip() (test1.py:184-186, ratio 76/64);
+      mode="eval" : CenterCrop(imsize) (datasets.py:1558-1560 with ratio 72/64).
+    ratio 1 (or None) leaves the Resize out: the bare CenterCrop(imsize) of datasets.py:1726-1727.
+
+        aug = DeviceAugment(256)
+        plan = aug.plan(batch.sizes, bboxes, generator=g)     # host: int32 [B, 12] descriptors (ops.AUG_DESC)
+        hr_u8 = aug(batch, plan)                              # [B, 3, 256, 256] uint8 = what GpuImagePyramid takes
+
+    The random draws are this class's own stream: per image `top` from [0, oh - S], then `left` from [0, ow - S], then the flip
+    with probability 1/2 - torchvision's order, from the given host torch.Generator, but not torchvision's numbers bit for bit.
+    A source that reaches the crop smaller than `imsize` is refused (torchvision would pad it; the reference never
+    meets one)."""
+
+    def __init__(self, imsize: int, ratio: float = 76 / 64, mode: str = "train", device="cuda"):
+        if mode not in ("train", "eval"):
+            raise TgsrError("DeviceAugment: mode is 'train' or 'eval', got %r" % (mode,))
+        self.imsize, self.ratio, self.mode = int(imsize), ratio, mode
+        self.size = None if ratio is None or ratio == 1 else int(self.imsize * ratio)      # None: no Resize in the chain
+        if self.imsize < 1 or (self.size is not None and self.size < self.imsize):
+            raise TgsrError("DeviceAugment: Resize(%s) cannot hold a window of %d" % (self.size, self.imsize))
+        self.device = torch.device(device)
+
+    def plan(self, sizes, bboxes=None, generator=None) -> torch.Tensor:
+        """sizes: [(H, W)] in pack order (or a RaggedImages); bboxes: None, or per image None / (x, y, w, h)."""
+        if isinstance(sizes, RaggedImages):
+            sizes = sizes.sizes
+        if bboxes is not None and len(bboxes) != len(sizes):
+            raise TgsrError("DeviceAugment.plan: %d bounding boxes for %d images" % (len(bboxes), len(sizes)))
+        S, rows, off = self.imsize, [], 0
+        for i, (H, W) in enumerate(sizes):
+            H, W = int(H), int(W)
+            box = (0, 0, W, H) if bboxes is None or bboxes[i] is None else crop_box(bboxes[i], W, H)
+            cw, ch = box[2] - box[0], box[3] - box[1]
+            if cw < 1 or ch < 1:
+                raise TgsrError("DeviceAugment.plan: image %d (%d x %d) has an empty crop box %s" % (i, W, H, box))
+            ow, oh = (cw, ch) if self.size is None else resized_size(cw, ch, self.size)
+            if oh < S or ow < S:
+                raise TgsrError("DeviceAugment.plan: image %d resizes to %d x %d, smaller than the %d window" % (i, ow, oh, S))
+            if self.mode == "train":
+                top = int(torch.randint(0, oh - S + 1, (1,), generator=generator))
+                left = int(torch.randint(0, ow - S + 1, (1,), generator=generator))
+                flip = int(float(torch.rand(1, generator=generator)) < 0.5)
+            else:
+                top, left, flip = int(round((oh - S) / 2.)), int(round((ow - S) / 2.)), 0
+            rows.append((off, H, W) + box + (oh, ow, top, left, flip))
+            off += 3 * H * W
+        if off >= 2 ** 31:
+            raise TgsrError("DeviceAugment.plan: %d bytes in one batch (the descriptors hold int32 offsets)" % off)
+        return ops.check_augment_table(torch.tensor(rows, dtype=torch.int64).to(torch.int32), S, max(off, 1))
+
+    def __call__(self, ragged: RaggedImages, plan: torch.Tensor) -> torch.Tensor:
+        if len(plan) != len(ragged):
+            raise TgsrError("DeviceAugment: a plan of %d images for a batch of %d" % (len(plan), len(ragged)))
+        if ragged.data.device != self.device and not (ragged.data.is_cuda and self.device.index is None):
+            ragged = ragged.to(self.device)
+        with torch.cuda.device(ragged.data.device):
+            return ops.augment_u8(ragged.data, plan, self.imsize)
+
+
+class SRBatcher:
+    """From decoded images to the pyramids of a training or evaluation step: DeviceAugment, then GpuImagePyramid.
+
+        imgs, bic, imgsblur, bicblur = SRBatcher((32, 64, 128, 256), mode="train")(batch, bboxes, generator=g)
+
+    the four lists `prepare_datablur` hands on (each float32 [B, 3, s, s] in [-1, 1] per scale; `u8=True`: the uint8 pyramids)."""
+
+    def __init__(self, sizes=(32, 64, 128, 256), mode: str = "train", ratio: float = 76 / 64, blur_radius: float = 2.0, device="cuda"):
+        self.augment = DeviceAugment(int(sizes[-1]), ratio, mode, device)
+        self.pyramid = GpuImagePyramid(sizes, blur_radius, device)
+
+    def __call__(self, ragged: RaggedImages, bboxes=None, generator=None, plan=None, u8: bool = False):
+        if plan is None:
+            plan = self.augment.plan(ragged.sizes, bboxes, generator)
+        hr = self.augment(ragged, plan)
+        with torch.cuda.device(hr.device):
+            return self.pyramid(hr, u8=u8)
 
 
 def _sorted_to(dev, cap_lens, lists):

@@ -1663,6 +1663,93 @@ def u8_normalize(x: torch.Tensor) -> torch.Tensor:
     return out
 
 
+# ----------------------------------------------------------------------------------------- crop / resize / window / flip
+AUG_DESC = 12            # int32 per image: byte offset, H, W, x1, y1, x2, y2, oh, ow, top, left, flip
+AUG_MAX_SIDE = 4096      # source H, W
+AUG_MAX_OUT = 65536      # resized oh, ow
+AUG_MAX_RATIO = 16       # reduction per axis (Pillow's tap count 33)
+
+
+def resize_ksize(in_size: int, out_size: int) -> int:
+    """Pillow's tap-table width for a bilinear resample of in_size -> out_size: 2 ceil(max(in / out, 1)) + 1."""
+    support = max(in_size / out_size, 1.0)
+    c = int(support)
+    return 2 * (c + (c < support)) + 1
+
+
+def check_augment_table(table, S: int, nbytes: int) -> torch.Tensor:
+    """The descriptor checks of tgsr_augment_u8 (include/tgsr_hip.h), on the host and with a message: returns the table as a
+    contiguous int32 [B, 12] host tensor or raises TgsrError.  Touches no device."""
+    t = torch.as_tensor(table)
+    if t.is_cuda or t.dtype != torch.int32 or t.dim() != 2 or t.shape[1] != AUG_DESC or t.shape[0] < 1:
+        raise TgsrError("augment: the descriptor table is a host int32 [B, %d] tensor, got %s %s on %s"
+                        % (AUG_DESC, t.dtype, tuple(t.shape), t.device))
+    if not 1 <= int(S) <= AUG_MAX_SIDE:
+        raise TgsrError("augment: window size %r is outside [1, %d]" % (S, AUG_MAX_SIDE))
+    if not 1 <= int(nbytes) < 2 ** 31:
+        raise TgsrError("augment: a packed buffer of %d bytes (must be in [1, 2^31))" % nbytes)
+    t = t.contiguous()
+    off, H, W, x1, y1, x2, y2, oh, ow, top, left, flip = (c.to(torch.int64) for c in t.unbind(1))
+    rules = (
+        ("a source side outside [1, %d]" % AUG_MAX_SIDE, (H < 1) | (W < 1) | (H > AUG_MAX_SIDE) | (W > AUG_MAX_SIDE)),
+        ("an image outside the packed buffer", (off < 0) | (off + 3 * H * W > nbytes)),
+        ("an empty crop box or one outside its image", (x1 < 0) | (x2 <= x1) | (x2 > W) | (y1 < 0) | (y2 <= y1) | (y2 > H)),
+        ("a resized image smaller than the window", (oh < S) | (ow < S)),
+        ("a resized side above %d" % AUG_MAX_OUT, (oh > AUG_MAX_OUT) | (ow > AUG_MAX_OUT)),
+        ("a window outside the resized image", (top < 0) | (top > oh - S) | (left < 0) | (left > ow - S)),
+        ("a reduction above %dx" % AUG_MAX_RATIO, (x2 - x1 > AUG_MAX_RATIO * ow) | (y2 - y1 > AUG_MAX_RATIO * oh)),
+        ("a flip flag that is not 0 or 1", (flip != 0) & (flip != 1)),
+    )
+    for what, bad in rules:
+        if bool(bad.any()):
+            b = int(bad.nonzero()[0])
+            raise TgsrError("augment: image %d has %s (descriptor %s, S = %d)" % (b, what, t[b].tolist(), S))
+    return t
+
+
+def augment_u8(packed: torch.Tensor, table, S: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """One launch of crop -> Pillow `resize(BILINEAR)` -> window -> mirror over a ragged batch: `packed` uint8, the decoded
+    H x W x 3 images back to back on the device; `table` the host int32 [B, 12] descriptors (check_augment_table).  Returns
+    planar uint8 [B, 3, S, S] (`out` if given: dense, on the same device), per image the bytes of
+    `img.crop((x1, y1, x2, y2)).resize((ow, oh), BILINEAR).crop((left, top, left + S, top + S))`, mirrored where flip is set."""
+    if not torch.is_tensor(packed) or packed.dtype != torch.uint8 or packed.dim() != 1:
+        raise TgsrError("augment: the packed buffer is a flat uint8 tensor")
+    packed = packed.contiguous()
+    t = check_augment_table(table, S, packed.numel())
+    B = t.shape[0]
+    if B > 65535:
+        raise TgsrError("augment: at most 65535 images per launch, got %d" % B)
+    if out is not None and (out.dtype != torch.uint8 or tuple(out.shape) != (B, 3, S, S) or not out.is_contiguous()):
+        raise TgsrError("augment: out must be a dense uint8 [%d, 3, %d, %d] tensor" % (B, S, S))
+    _need_hip(packed, out)
+    L = _lib.lib()
+    tdev = t.to(packed.device, non_blocking=True)
+    ws = torch.empty(L.tgsr_augment_ws_elems(B, S), dtype=torch.int32, device=packed.device)
+    if out is None:
+        out = torch.empty(B, 3, S, S, dtype=torch.uint8, device=packed.device)
+    check(L.tgsr_augment_u8(_p(packed), packed.numel(), _p(t), _p(tdev), B, S, _p(ws), _p(out), _stream()), "tgsr_augment_u8")
+    return out
+
+
+def resize_coeffs_device(in_size: int, out_size: int, device="cuda") -> Tuple[torch.Tensor, torch.Tensor]:
+    """Pillow's precompute_coeffs (bilinear) computed on the device in fp64, the step augment_u8 runs per image and axis:
+    (bounds int32 [out_size, 2] = (first input index, tap count), taps int32 [out_size, ksize] in 22-bit fixed point)."""
+    in_size, out_size = int(in_size), int(out_size)
+    if not (1 <= in_size <= AUG_MAX_OUT and 1 <= out_size <= AUG_MAX_OUT):
+        raise TgsrError("resize_coeffs: sizes must lie in [1, %d], got %d -> %d" % (AUG_MAX_OUT, in_size, out_size))
+    if in_size > AUG_MAX_RATIO * out_size:
+        raise TgsrError("resize_coeffs: %d -> %d is a reduction above %dx" % (in_size, out_size, AUG_MAX_RATIO))
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        raise TgsrError("resize_coeffs_device computes on a HIP device, got %s" % dev)
+    ks = resize_ksize(in_size, out_size)
+    with torch.cuda.device(dev):
+        bounds = torch.empty(out_size, 2, dtype=torch.int32, device=dev)
+        taps = torch.empty(out_size, ks, dtype=torch.int32, device=dev)
+        check(_lib.lib().tgsr_resize_coeffs(in_size, out_size, ks, _p(bounds), _p(taps), _stream()), "tgsr_resize_coeffs")
+    return bounds, taps
+
+
 # ----------------------------------------------------------------------------------------- stand-alone GLU
 def glu(x: torch.Tensor) -> torch.Tensor:
     """GLU.forward (util.py:45-53): x[:, :C/2] * sigmoid(x[:, C/2:]) for x [B, C, ...] with C even."""
