@@ -204,6 +204,10 @@ int tgsr_conv_to3_fwd(const float* x, int64_t x_bstride, int B, int Cin, int H, 
  *               (`mask.repeat(queryL,1)`, GlobalAttention.py:111); 1 = per-sample masking (mask[b])
  * src_ws   workspace, B*idf*32 floats (the projected words, zero padded to 32).  With words == w_ctx == NULL the
  *          projection is skipped and src_ws is read as the output of tgsr_word_project_fwd.
+ * With `words` the projection stages one sample's words in LDS, cdf * 128 bytes: cdf <= 1024 (TGSR_EUNSUPPORTED beyond; above
+ * cdf = 512 the launcher opts the kernel in to more than 64 KB of dynamic LDS, once per device).  w_ctx needs no more than its
+ * 4-byte alignment: its rows are read as float4 only where w_ctx is 16-byte aligned and cdf % 4 == 0, one float at a time otherwise
+ * (the same products in the same order: the same bits).
  * c_code   [B][idf][Q] (batch stride c_bstride);  attn [B][T][Q] dense (may be NULL: not written)
  */
 int tgsr_word_attention_fwd(const float* h, int64_t h_bstride, const float* words, const float* w_ctx,
@@ -291,8 +295,8 @@ int tgsr_bilstm_bwd(const int32_t* cap_lens, int B, int Tmax, int H, const float
  * DAMSM word/region attention for the whole (image, caption) grid in one launch: func_attention
  * (GlobalAttention.py:33-74) as driven by words_loss (losses.py:73-113) - the B-iteration Python loop, word.repeat,
  * both softmaxes, the two bmm and the cosine / exp / sum / log tail.
- * words [B][ndf][Tw] dense (Tw <= 32), cap_lens int32 [B] (NULL = Tw for all), ctx [B][ndf][S] dense
- * (S = 17*17 <= 320), ndf % 32 == 0, ndf <= 512.
+ * words [B][ndf][Tw] dense (Tw <= 32), cap_lens int32 [B] (NULL = Tw for all; a length outside [1, Tw] is clamped into it, here and
+ * in tgsr_damsm_words_bwd), ctx [B][ndf][S] dense (S = 17*17 <= 320), ndf % 32 == 0, ndf <= 512.
  * sim      [B_img][B_cap] = log sum_{w < len} exp(gamma2 * cos(word_w, region-context_w))   (losses.py:102-109;
  *          the caller multiplies by gamma3 and applies the class mask / cross entropy)
  * att_diag NULL or [B][Tw][S]: attention of image i on caption i, rows >= cap_lens[i] zero       (losses.py:93)

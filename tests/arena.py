@@ -14,7 +14,8 @@ outside the process's memory.
 The buffer is int32 words; PATTERN is a quiet NaN no arithmetic produces (the payload of a NaN an operation makes is the canonical
 0x7FC00000 or an operand's), so "this word was never written" is a bit comparison.  Guard bands, the gaps between the samples of a
 strided operand and every input hold PATTERN / their values before the call and must hold the same bits after it; the interior of
-an output must hold no PATTERN word and only finite values; a workspace may be left partly unwritten but not overrun.
+an output must hold no PATTERN word and only finite values; a workspace may be left partly unwritten but not overrun.  A uint8
+input (a mask) is padded to whole words, the padding bytes holding PATTERN's.
 """
 import ctypes
 
@@ -59,6 +60,8 @@ class Region:
 
     def read(self):
         """The interior as a host tensor of the operand's shape and type."""
+        if self.dtype == torch.uint8:          # a byte operand: whole words, the padding bytes behind the last element dropped
+            return self.words().view(torch.uint8)[:int(np.prod(self.shape))].reshape(self.shape).clone()
         return self.words().view(self.dtype).reshape(self.shape).clone()
 
 
@@ -93,8 +96,17 @@ class Arena:
 
     def place_input(self, t, bstride=None, align=16, skew=0):
         """Copies host tensor `t` in; with `bstride` its samples (dim 0) lie that many words apart, PATTERN in between.
-        `skew` words are added to the aligned offset (an operand that is deliberately NOT `align`-aligned)."""
+        `skew` words are added to the aligned offset (an operand that is deliberately NOT `align`-aligned).
+        A uint8 tensor (a mask) is one dense run of bytes padded to whole words, the padding bytes holding PATTERN's bytes."""
         t = t.detach().cpu().contiguous()
+        if t.dtype == torch.uint8:
+            assert bstride is None, "a byte operand is dense"
+            n = t.numel()
+            assert n >= 1
+            host = torch.full(((n + 3) // 4,), PATTERN, dtype=torch.int32)
+            host.view(torch.uint8)[:n] = t.reshape(-1)
+            shape = tuple(int(s) for s in t.shape) or (1,)
+            return self._place(_INPUT, shape, 1, host.numel(), None, align, skew, torch.uint8, host)
         shape, nb, per = self._split(t.shape, t.dtype, bstride is not None)
         return self._place(_INPUT, shape, nb, per, bstride, align, skew, t.dtype, t.reshape(-1).view(torch.int32).clone())
 

@@ -149,7 +149,9 @@ def test_lp_conv_to3(K, act, B, H, W, cp, name, td, ulp):
 
 
 @pytest.mark.parametrize("name,td,ulp", DTYPES)
-@pytest.mark.parametrize("B,H,W,T,correct", [(3, 8, 32, 7, False), (2, 32, 32, 18, False), (5, 16, 64, 12, True), (1, 4, 32, 1, False)])
+@pytest.mark.parametrize("B,H,W,T,correct", [(3, 8, 32, 7, False), (2, 32, 32, 18, False), (5, 16, 64, 12, True), (1, 4, 32, 1, False),
+                                             # B > 256: mask rows read from global memory; capped grid: a second trip of the tile loop
+                                             (257, 36, 32, 5, False)])
 def test_lp_word_attention(B, H, W, T, correct, name, td, ulp):
     from tgsr_amd import lp, ops
     g = torch.Generator().manual_seed(B * 10 + T)
@@ -159,6 +161,10 @@ def test_lp_word_attention(B, H, W, T, correct, name, td, ulp):
     lens = torch.randint(1, T + 1, (B,), generator=g)
     lens[0] = T
     mask = torch.arange(T)[None, :] >= lens[:, None]
+    if B > 256:       # the row read from global memory must not look like the cached row a wrapped index would give
+        lens[256] = 2
+        mask = torch.arange(T)[None, :] >= lens[:, None]
+        assert bool((mask[256] != mask[0]).any())
     c_ref, a_ref = OL.word_attention(h, words, wctx, mask, td, correct_mask=correct)
     img = lp.from_nchw(h.to(DEV), name, cpitch=64)
     src = ops.word_project(words.to(DEV), [wctx.to(DEV)])[0]

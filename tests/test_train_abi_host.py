@@ -83,6 +83,39 @@ def test_arena_check_passes_a_clean_call_and_trips_on_every_violation():
     assert bool((a.buffer()[ws.offset + 7:ws.offset + 7 + GUARD] == PATTERN).all())
 
 
+def test_arena_byte_operands_are_padded_to_whole_words_with_the_pattern():
+    """A uint8 input (a mask): dense bytes, padded to whole words with PATTERN's bytes, read back as bytes; a write into the
+    operand or into its padding trips check()."""
+    pat = torch.tensor([PATTERN], dtype=torch.int32).view(torch.uint8).tolist()
+    for shape in ((3, 7), (2, 4), (1, 1), (257, 3)):
+        n = shape[0] * shape[1]
+        m = (torch.arange(n) % 3 == 0).to(torch.uint8).view(shape)
+        a = Arena("cpu")
+        x = a.place_input(torch.ones(5))
+        r = a.place_input(m)
+        s = a.place_input(m, skew=1)
+        out = a.place_output((3,))
+        assert r.per == r.span == (n + 3) // 4 and r.shape == shape and r.address % 16 == 0 and s.address % 16 == 4
+        assert r.offset - (x.offset + x.span) >= GUARD and out.offset - (s.offset + s.span) >= GUARD
+        assert torch.equal(r.read(), m) and r.read().dtype == torch.uint8 and torch.equal(s.read(), m)
+        raw = a.buffer()[r.offset:r.offset + r.per].view(torch.uint8)
+        assert raw[:n].tolist() == m.view(-1).tolist()
+        assert raw[n:].tolist() == pat[n % 4:] if n % 4 else raw.numel() == n      # the padding bytes hold the pattern's
+        assert bool((a.buffer()[r.offset - GUARD:r.offset] == PATTERN).all())
+        a.buffer().view(torch.float32)[out.offset:out.offset + 3] = 0.5
+        a.check()
+        for byte in sorted({0, n - 1, 4 * r.per - 1}):                            # first, last and (where there is one) a padding byte
+            view = a.buffer()[r.offset:r.offset + r.per].view(torch.uint8)
+            keep = int(view[byte])
+            view[byte] = keep ^ 1
+            v = a.violations()
+            assert len(v) == 1 and "were written" in v[0] and "input" in v[0], (shape, byte, v)
+            view[byte] = keep
+            a.check()
+    with pytest.raises(AssertionError):
+        Arena("cpu").place_input(torch.zeros(2, 3, dtype=torch.uint8), bstride=8)
+
+
 # ---- the instance table against the library's planners ----
 def _L():
     from tgsr_amd import _lib

@@ -17,7 +17,8 @@
 namespace tgsr {
 
 // grid (B, idf / 8), 256 threads: thread (i = 8 * blockIdx.y + tid / 32, t = tid % 32) owns one output; the
-// sample's words are staged once in LDS as [c][32] (zero padded), the weight row is a half-wave-uniform float4 stream.
+// sample's words are staged once in LDS as [c][32] (zero padded), the weight row is a half-wave-uniform float4 stream
+// where every row starts on 16 bytes (w_ctx 16-byte aligned and cdf % 4 == 0), a scalar stream otherwise.
 __global__ __launch_bounds__(256) void word_project_kernel(const float* __restrict__ words,
                                                            const float* __restrict__ w_ctx, float* __restrict__ src,
                                                            int idf, int cdf, int T) {
@@ -33,7 +34,7 @@ __global__ __launch_bounds__(256) void word_project_kernel(const float* __restri
   const float* wr = w_ctx + (int64_t)i * cdf;
   float acc = 0.f;
   int c = 0;
-  if ((cdf & 3) == 0) {
+  if ((cdf & 3) == 0 && (reinterpret_cast<uintptr_t>(w_ctx) & 15) == 0) {
 #pragma unroll 4
     for (; c < cdf; c += 4) {
       const float4 wv = *reinterpret_cast<const float4*>(wr + c);
@@ -203,8 +204,22 @@ extern "C" int tgsr_word_attention_fwd(const float* h, int64_t h_bstride, const 
   hipStream_t s = as_stream(stream);
   if (words) {   // else: src_ws already holds the projection (tgsr_word_project_fwd)
     if (cdf > 1024) return TGSR_EUNSUPPORTED;   // words of one sample are staged in LDS (cdf * 128 bytes)
-    hipLaunchKernelGGL(word_project_kernel, dim3(B, idf / 8), dim3(256), (size_t)cdf * 32 * sizeof(float), s, words,
-                       w_ctx, src_ws, idf, cdf, T);
+    const size_t lds = (size_t)cdf * 32 * sizeof(float);
+    if (lds > 64 * 1024) {                      // > 64 KB of dynamic LDS needs the opt-in, once per DEVICE (as damsm_launch)
+      static bool attr_set[64] = {false};
+      int dev = 0;
+      if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
+      if (!attr_set[dev]) {
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(word_project_kernel),
+                                                  hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
+        if (e != hipSuccess) {   // its own status: the runtime need not have latched it for hipGetLastError
+          (void)hipGetLastError();
+          return note_launch(e, "hipFuncSetAttribute(word_project_kernel)");
+        }
+        attr_set[dev] = true;
+      }
+    }
+    hipLaunchKernelGGL(word_project_kernel, dim3(B, idf / 8), dim3(256), lds, s, words, w_ctx, src_ws, idf, cdf, T);
     int rc = note_launch(hipGetLastError(), "word_project_kernel");
     if (rc) return rc;
   }

@@ -217,9 +217,12 @@ static int damsm_launch(DamsmArgs a, void* stream) {
   int dev = 0;                          // belongs to the device's code object, not to the process)
   if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
   if (!attr_set[dev]) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(damsm_pair_kernel),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
-      return note_launch(hipGetLastError(), "hipFuncSetAttribute(damsm_pair_kernel)");
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(damsm_pair_kernel),
+                                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    if (e != hipSuccess) {   // its own status: the runtime need not have latched it for hipGetLastError
+      (void)hipGetLastError();
+      return note_launch(e, "hipFuncSetAttribute(damsm_pair_kernel)");
+    }
     attr_set[dev] = true;
   }
   hipLaunchKernelGGL(damsm_pair_kernel, dim3(pairs), dim3(256), lds, as_stream(stream), a);

@@ -410,9 +410,12 @@ extern "C" int tgsr_damsm_words_bwd(const float* words, const int32_t* cap_lens,
   int dev = 0;                          // process (one process driving two GPUs would otherwise fail on the second)
   if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
   if (!attr_set[dev]) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(damsm_pair_bwd_kernel),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
-      return note_launch(hipGetLastError(), "hipFuncSetAttribute(damsm_pair_bwd_kernel)");
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(damsm_pair_bwd_kernel),
+                                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    if (e != hipSuccess) {   // its own status: the runtime need not have latched it for hipGetLastError
+      (void)hipGetLastError();
+      return note_launch(e, "hipFuncSetAttribute(damsm_pair_bwd_kernel)");
+    }
     attr_set[dev] = true;
   }
   hipStream_t s = as_stream(stream);
