@@ -440,8 +440,15 @@ int tgsr_axpy_images(int n, float* const* out, const float* const* t, const floa
  * tgsr_plane_mean(_bwd): the 8 x 8 global average (F.avg_pool2d(x, 8) on an 8 x 8 map).  tgsr_relu_mask: out = dy * (y > 0).
  * tgsr_bilinear_*: nn.Upsample(size = (OH, OW), mode = 'bilinear') (align_corners = False), util.py:310, on dense planes.
  */
-int tgsr_gconv_set_form(int split); /*
- * out[k] = ((parts[0][k] + parts[1][k]) + ...) over n dense tensors of m floats stacked back to back (m % 4 == 0, 16-byte aligned):
+/*
+ * tgsr_gconv_set_form: 1 (default; TGSR_GCONV_SPLIT=0 in the environment turns it off): tgsr_gconv / tgsr_gconv_stats run on the bf16
+ * matrix pipe with exact three-piece fp32 operands where K % 16 == 0, KH KW <= 25 taps, the data gradient at stride 1, A 16-byte
+ * aligned and S within 2^31 bytes; 0: fp32 MFMA everywhere.  Returns the old value.  Process-wide, and it is one of TWO switches in
+ * front of that form: tgsr_dconv_set_split(0) takes the generic taps off it as well.
+ */
+int tgsr_gconv_set_form(int split);
+/*
+ * tgsr_sum_stack: out[k] = ((parts[0][k] + parts[1][k]) + ...) over n dense tensors of m floats stacked back to back (m % 4 == 0, 16-byte aligned):
  * the branches' contributions to a Mixed block's input gradient (util.py:281-298's blocks), each written by its own branch's stream,
  * summed in the order a one-stream walk accumulates them.
  */
@@ -456,7 +463,8 @@ int tgsr_sum_stack(const float* parts, int n, int64_t m, float* out, void* strea
 int tgsr_interleave2x2(const float* t00, const float* t01, const float* t10, const float* t11, float* dx, int64_t planes, int H, int W,
                        int accumulate, const float* mask, void* stream);
 
-/* 1 (default): three-piece bf16 form where K % 16 == 0, <= 25 taps, stride-1 data gradient; 0: fp32 MFMA.  Returns the old value */
+/* The planners of tgsr_gconv (host arithmetic, reads of the one launch plan): the K slabs the fill heuristic asks for at GEMM size
+ * M x N x K (1 = no split; TGSR_GCONV_FILL) and the workspace they take.  They depend on neither switch. */
 int tgsr_gconv_nsplit(int M, int N, int K);
 int64_t tgsr_gconv_ws_elems(int B, int M, int PH, int PW, int K);
 int tgsr_gconv(int dgrad, const float* A, const float* S, int64_t s_bstride, int B, int Hs, int Ws, int M, int K, int PH, int PW,
@@ -611,10 +619,13 @@ int tgsr_bn_train_bwd(const float* dout, const float* raw, int B, int C, int HW,
  * products accumulated in fp32 (what is left out is <= 2^-26 of a product; measured error against fp64: below the fp32 MFMA's) -
  * fp32 in, fp32 out, 2.4x the fp32 MFMA rate; shapes it does not take (K % 16 != 0, ...) and on == 0 use the fp32 MFMA.
  * Returns the previous setting.  Process-wide; not meant to be flipped while launches are being issued from other threads.
+ * on == 0 also takes the Inception trunk's generic taps (tgsr_gconv, tgsr_gconv_stats) off that form: it is the same kernel.
  */
 int tgsr_dconv_set_split(int on);
-/* 1 when tgsr_conv4x4s2_{fwd (op 0), dgrad (1), wgrad (2)} takes the split form for this shape under the current setting (operand
- * alignment aside: the calls themselves also require 16-byte aligned w / dy / ws): what a caller's bookkeeping needs to price a launch. */
+/* 1 when tgsr_conv4x4s2_{fwd (op 0), dgrad (1), wgrad (2)} takes the split form for this shape under the current setting: what a
+ * caller's bookkeeping needs to price a launch.  These and *_ws_elems read the launchers' own plan, evaluated for 16-byte aligned
+ * operands (the calls themselves test w and ws - forward, 4x4 data gradient - or dy - weight gradient - and fall back to the fp32
+ * MFMA otherwise) and bounding the convolution's tensors, not the kernel's operands, by 4 GB. */
 int tgsr_conv4x4s2_split_form(int op, int B, int Cin, int H, int W, int Cout);
 int tgsr_conv3x3_gemm_split_form(int op, int B, int Cin, int H, int W, int Cout);
 int64_t tgsr_conv4x4s2_ws_elems(int op, int B, int Cin, int H, int W, int Cout);

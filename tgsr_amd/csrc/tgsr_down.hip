@@ -13,14 +13,14 @@
 //   wgrad       : dw[co][j] = sum_pixels dy[co][p] S(p, j)                                         M = Cout, N = j, K = pixels
 // BatchNorm (batch statistics) + LeakyReLU(0.2) is tgsr_bn_train_fwd / _bwd with act = 2 (tgsr_bn.hip); the first layer
 // (no BatchNorm) takes the LeakyReLU in this kernel's epilogue.  SURVEY.md 8(f)1.
-#include "tgsr_common.h"
+#include "tgsr_igemm_plan.h"
 
 #include <type_traits>
 
 namespace tgsr {
 
 enum { kFwd4 = 0, kFwd3 = 1, kDgrad4 = 2, kDgrad3 = 3, kWgrad4 = 4, kWgrad3 = 5,
-       // generic taps (CNN_ENCODER's frozen trunk, tgsr_igemm.hip): any KH x KW <= 32 taps, forward stride 1 | 2, data gradient stride 1
+       // generic taps (CNN_ENCODER's frozen trunk, tgsr_igemm.hip): any KH x KW <= 25 taps, forward stride 1 | 2, data gradient stride 1
        kFwdG = 6, kDgradG = 7 };
 
 struct IgArgs {
@@ -47,7 +47,7 @@ struct IgArgs {
   int grelu, gacc;
 };
 
-constexpr int kIgKC = 16, kIgP = 132;   // K-chunk; LDS pitch: (4 k + m) mod 64 is a bijection over a wave's writes
+constexpr int kIgP = 132;   // LDS pitch (K-chunk kIgKC = 16): (4 k + m) mod 64 is a bijection over a wave's writes
 
 // decode a column index j = (channel, taps) of the gathered operand into (element offset, row shift, column shift)
 template <int MODE>
@@ -881,98 +881,98 @@ __global__ void leaky_kernel(const float* __restrict__ g, const float* __restric
   }
 }
 
-// reduction splits: enough workgroups for two per CU, at least 8 chunks (128 reduction elements) per split
-static bool ig_wide(int kind, int op, int64_t M) { return kind == 4 && op != 2 && M <= 64; }   // fwd / dgrad of the 4x4 conv
-
-static int ig_nsplit(int64_t M, int64_t N, int64_t K, int ncls, bool wide = false) {
-  const int64_t tiles = wide ? ((M + 63) / 64) * ((N + 255) / 256) * ncls : ((M + 127) / 128) * ((N + 127) / 128) * ncls;
-  int64_t s = (512 + tiles - 1) / tiles;
-  const int64_t cap = (K + 8 * kIgKC - 1) / (8 * kIgKC);
-  if (s > cap) s = cap;
-  return (int)(s < 1 ? 1 : (s > 256 ? 256 : s));
-}
-
-// Shapes of one convolution in GEMM terms.  kind: 4 = 4x4 stride 2 pad 1, 3 = 3x3 stride 1 pad 1; op: 0 forward,
-// 1 data gradient, 2 weight gradient.  out_elems = elements of the tensor the GEMM produces.
-struct IgShape { int64_t M, N, K, out_elems; int ncls, nsplit; };
-static IgShape ig_shape(int kind, int op, int B, int Cin, int H, int W, int Cout) {
-  const int T = kind == 4 ? 16 : 9, Ho = kind == 4 ? H / 2 : H, Wo = kind == 4 ? W / 2 : W;
-  IgShape s;
-  s.ncls = 1;
-  if (op == 0) { s.M = Cout; s.N = (int64_t)B * Ho * Wo; s.K = (int64_t)Cin * T; s.out_elems = (int64_t)B * Cout * Ho * Wo; }
-  else if (op == 1 && kind == 4) { s.M = Cin; s.N = (int64_t)B * Ho * Wo; s.K = 4ll * Cout; s.ncls = 4; s.out_elems = (int64_t)B * Cin * H * W; }
-  else if (op == 1) { s.M = Cin; s.N = (int64_t)B * H * W; s.K = 9ll * Cout; s.out_elems = (int64_t)B * Cin * H * W; }
-  else { s.M = Cout; s.N = (int64_t)Cin * T; s.K = (int64_t)B * Ho * Wo; s.out_elems = (int64_t)Cout * Cin * T; }
-  s.nsplit = ig_nsplit(s.M, s.N, s.K, s.ncls, ig_wide(kind, op, s.M));
-  return s;
-}
-
-// 1 (default): the 4x4 convolution's GEMMs run on the bf16 matrix pipe with three-piece operands (dconv_igemm6_kernel) where
+// 1 (default): the discriminators' GEMMs run on the bf16 matrix pipe with three-piece operands (dconv_igemm6_kernel) where
 // the shape allows; 0: fp32 MFMA everywhere.  TGSR_DCONV_SPLIT=0 | tgsr_dconv_set_split(0).
 // Bits: 1 = on; 2 = the weights pre-split into LDS images by a pass of their own (forward / data gradient).  (The a0 b0 products in
 // accumulators of their own - HILO, 2.5-3x less error than the fp32 MFMA - need 64 registers more than two waves per SIMD leave.)
+// Process-wide, and the trunk's generic taps stand behind it too (ig6_enabled): they run on the three-piece form only while this
+// switch AND tgsr_igemm.hip's g_gconv_form are on.
 static int g_ig_split = [] {
   const char* e = getenv("TGSR_DCONV_SPLIT");
   return e ? (atoi(e) & 3) : 1;
 }();
+bool ig6_enabled() { return g_ig_split != 0; }
 
-// floats of workspace the split images of the A operand take (dconv_igemm6_kernel: forward = the weight, data gradient = its four
-// parity-class regroupings; 6 bytes per element, rows padded to whole tiles); 0 for shapes the split form does not take
-static int64_t ig6_image_elems(int kind, int op, int64_t M, int64_t K) {
-  if (!(g_ig_split & 2) || kind != 4 || op == 2 || K % kIgKC != 0) return 0;       // (only the pre-split variant needs them)
-  const int64_t MB = ig_wide(kind, op, M) ? 64 : 128, mt = (M + MB - 1) / MB;
-  return (op == 1 ? 4 : 1) * mt * MB * K * 3 / 2;
+// The plan of one discriminator convolution.  kind: 4 = 4x4 stride 2 pad 1, 3 = 3x3 stride 1 pad 1; op: 0 forward, 1 data gradient,
+// 2 weight gradient; H, W = the input's size.  launch: a launcher asks, and `align` is the OR of the addresses dconv_igemm6_kernel's
+// 16-byte loads of A start from (forward and 4x4 data gradient: w and ws; weight gradient: dy; the 3x3 data gradient reads w by
+// dwords: none).  !launch: an exported planner asks - alignment unknown: assumed - and the 4 GB bound is the one the planners have
+// always answered with (`conv_bounds` below), not the launch's.
+static IgPlan ig_plan(int kind, int op, int B, int Cin, int H, int W, int Cout, bool launch, uintptr_t align = 0) {
+  const int T = kind == 4 ? 16 : 9;
+  const int64_t px = kind == 4 ? (int64_t)(H / 2) * (W / 2) : (int64_t)H * W;                                      // output pixels per image
+  const int64_t xe = (int64_t)B * Cin * H * W, ye = (int64_t)B * Cout * px, we = (int64_t)Cout * Cin * T;          // elements of x, y | dy, w
+  IgPlan p = {};
+  p.ncls = 1;
+  if (op == 0) { p.M = Cout; p.N = B * px; p.K = (int64_t)Cin * T; p.slab_stride = ye; }
+  else if (op == 1) { p.M = Cin; p.N = B * px; p.K = (kind == 4 ? 4ll : 9ll) * Cout; p.ncls = kind == 4 ? 4 : 1; p.slab_stride = xe; }
+  else { p.M = Cout; p.N = (int64_t)Cin * T; p.K = B * px; p.slab_stride = we; }
+  ig_tile(p, kind == 4 && op != 2 && p.M <= 64);                               // WIDE: forward / data gradient of the 4x4 conv
+  // the head of the workspace: the split images of A (pre-split variant only: forward = the weight, data gradient = its four
+  // parity-class regroupings; 6 bytes per element, rows padded to whole tiles), or the data gradient's fp32 parity-class pack
+  const bool canpre = (g_ig_split & 2) && kind == 4 && op != 2;
+  const int64_t img = canpre && p.K % kIgKC == 0 ? (op == 1 ? 4 : 1) * ((p.M + p.MB - 1) / p.MB) * p.MB * p.K * 3 / 2 : 0;
+  const int64_t pack = (kind == 4 && op == 1) ? 16ll * Cin * Cout : 0;
+  p.head = img > pack ? img : pack;
+  // reduction splits: enough workgroups for two per CU, at least 8 chunks (128 reduction elements) per split
+  const int64_t tiles = ig_tiles(p), cap = (p.K + 8 * kIgKC - 1) / (8 * kIgKC);
+  int64_t asked = (512 + tiles - 1) / tiles;
+  if (asked > cap) asked = cap;
+  ig_split(p, asked < 1 ? 1 : (asked > 256 ? 256 : asked));
+  p.a_bytes = canpre ? img * 4 : (op == 2 ? ye : we) * 4;
+  p.s_bytes = (op == 1 ? ye : xe) * 4;
+  // The three-piece form: whole chunks (weight gradient: a chunk's sixteen pixels inside one image), 16-byte loads of A, and A and S
+  // inside a buffer descriptor's 32-bit num_records - the fixed-tap modes only add unsigned in-image byte offsets to it, so 2^32.
+  const int64_t lim = 1ll << 32;
+  // (What the planners bound instead: the 3x3 form all three tensors; the 4x4 form x and the fp32 weight - not its images - forward,
+  // dy alone for the data gradient, x and dy for the weight gradient.  Kept as it was; the launch decides by `a_bytes` / `s_bytes`.)
+  const bool conv_bounds = kind == 3 ? (xe * 4 < lim && ye * 4 < lim && we * 4 < lim)
+                                     : (op == 0 ? (xe * 4 < lim && we * 4 < lim) : (op == 1 ? ye * 4 < lim : (xe * 4 < lim && ye * 4 < lim)));
+  const bool fits = launch ? (!(align & 15) && p.a_bytes < lim && p.s_bytes < lim) : conv_bounds;
+  // the image layer's data gradient: M = Cin rows of a 128-row GEMM tile would idle 97 % of the matrix pipe (dconv_dgrad4_image_kernel)
+  if (kind == 4 && op == 1 && Cin <= 4 && (int64_t)Cout * Cin * 64 <= 64 * 1024) p.form = kIgImage;
+  else if (!(g_ig_split && (op == 2 ? px : p.K) % kIgKC == 0 && fits)) p.form = kIgFp32;
+  else p.form = canpre ? kIgSplitPre : kIgSplit;
+  return p;
 }
-// the head of the workspace: the A images, or (data gradient on the fp32 MFMA) the fp32 parity-class pack; slabs follow
-static int64_t ig_ws_head(int kind, int op, const IgShape& s, int Cin, int Cout) {
-  const int64_t img = ig6_image_elems(kind, op, s.M, s.K), pack = (kind == 4 && op == 1) ? 16ll * Cin * Cout : 0;
-  return img > pack ? img : pack;
-}
 
-static int64_t ig_ws_elems(int kind, int op, int B, int Cin, int H, int W, int Cout) {
-  const IgShape s = ig_shape(kind, op, B, Cin, H, W, Cout);
-  const int64_t n = (s.nsplit > 1 ? s.nsplit * s.out_elems : 0) + ig_ws_head(kind, op, s, Cin, Cout);
-  return n > 0 ? n : 1;
-}
-
-
+// fills the GEMM terms of `a` from the plan and launches the instance of MODE the plan names
 template <int MODE, bool WIDE = false>
-static int ig_launch(IgArgs a, const IgShape& sh, float* slabs, float* out, hipStream_t s, const char* what, bool split = false) {
-  if (sh.M >= (1ll << 31) || sh.N >= (1ll << 31) || sh.K >= (1ll << 31) || sh.out_elems >= (1ll << 31)) return TGSR_EUNSUPPORTED;
-  a.M = (int)sh.M; a.N = (int)sh.N; a.K = (int)sh.K;
-  a.nsplit = sh.nsplit;
-  const int chunks = (int)((sh.K + kIgKC - 1) / kIgKC);
-  a.chunks_per_split = (chunks + sh.nsplit - 1) / sh.nsplit;
-  a.nsplit = (chunks + a.chunks_per_split - 1) / a.chunks_per_split;     // no empty splits
-  a.slab_stride = a.nsplit > 1 ? sh.out_elems : 0;
-  a.out = a.nsplit > 1 ? slabs : out;
-  if (a.nsplit > 1) a.act = 0;                                           // the slab sum applies it
-  const dim3 grid(WIDE ? (unsigned)((sh.N + 255) / 256) : (unsigned)((sh.N + 127) / 128),
-                  WIDE ? (unsigned)((sh.M + 63) / 64) : (unsigned)((sh.M + 127) / 128), (unsigned)(a.nsplit * sh.ncls));
-  if (split) {
-    constexpr bool CANPRE = MODE == kFwd4 || MODE == kDgrad4;
-    const bool pre = CANPRE && (g_ig_split & 2);
-    if constexpr (CANPRE) {
-      if (pre) hipLaunchKernelGGL((dconv_igemm6_kernel<MODE, WIDE, true>), grid, dim3(256), 0, s, a);
-    }
-    if (!pre) hipLaunchKernelGGL((dconv_igemm6_kernel<MODE, WIDE, false>), grid, dim3(256), 0, s, a);
-    return note_launch(hipGetLastError(), "dconv_igemm6_kernel");
+static int ig_launch(IgArgs a, const IgPlan& p, float* slabs, float* out, hipStream_t s, const char* what) {
+  if (p.M >= (1ll << 31) || p.N >= (1ll << 31) || p.K >= (1ll << 31) || p.slab_stride >= (1ll << 31)) return TGSR_EUNSUPPORTED;
+  a.M = (int)p.M; a.N = (int)p.N; a.K = (int)p.K;
+  a.nsplit = p.nsplit; a.chunks_per_split = p.cps;
+  a.slab_stride = p.nsplit > 1 ? p.slab_stride : 0;
+  a.out = p.nsplit > 1 ? slabs : out;
+  if (p.nsplit > 1) a.act = 0;                                           // the slab sum applies it
+  a.a_bytes = p.a_bytes; a.s_bytes = p.s_bytes;
+  if (p.form == kIgFp32) {
+    hipLaunchKernelGGL((dconv_igemm_kernel<MODE, WIDE>), p.grid, dim3(256), 0, s, a);
+    return note_launch(hipGetLastError(), what);
   }
-  hipLaunchKernelGGL((dconv_igemm_kernel<MODE, WIDE>), grid, dim3(256), 0, s, a);
-  return note_launch(hipGetLastError(), what);
+  if constexpr (MODE == kFwd4 || MODE == kDgrad4) {
+    if (p.form == kIgSplitPre) hipLaunchKernelGGL((dconv_igemm6_kernel<MODE, WIDE, true>), p.grid, dim3(256), 0, s, a);
+  }
+  if (p.form != kIgSplitPre) hipLaunchKernelGGL((dconv_igemm6_kernel<MODE, WIDE, false>), p.grid, dim3(256), 0, s, a);
+  return note_launch(hipGetLastError(), "dconv_igemm6_kernel");
 }
 
-static int ig_finish(const IgArgs& a, int nsplit_used, int act, const float* slabs, float* out, int64_t n, hipStream_t s) {
-  if (nsplit_used <= 1) return TGSR_OK;
+// the one dispatch over (kind, op, WIDE), then the slab sum (+ the forward's activation) where K was split
+static int dconv_launch(int kind, int op, const IgArgs& a, const IgPlan& p, float* slabs, float* out, hipStream_t s) {
+  int rc;
+  if (op == 0) rc = kind == 3 ? ig_launch<kFwd3>(a, p, slabs, out, s, "dconv_igemm_kernel<fwd3>")
+                   : p.wide ? ig_launch<kFwd4, true>(a, p, slabs, out, s, "dconv_igemm_kernel<fwd4, wide>")
+                            : ig_launch<kFwd4>(a, p, slabs, out, s, "dconv_igemm_kernel<fwd4>");
+  else if (op == 1) rc = kind == 3 ? ig_launch<kDgrad3>(a, p, slabs, out, s, "dconv_igemm_kernel<dgrad3>")
+                        : p.wide ? ig_launch<kDgrad4, true>(a, p, slabs, out, s, "dconv_igemm_kernel<dgrad4, wide>")
+                                 : ig_launch<kDgrad4>(a, p, slabs, out, s, "dconv_igemm_kernel<dgrad4>");
+  else rc = kind == 3 ? ig_launch<kWgrad3>(a, p, slabs, out, s, "dconv_igemm_kernel<wgrad3>")
+                      : ig_launch<kWgrad4>(a, p, slabs, out, s, "dconv_igemm_kernel<wgrad4>");
+  if (rc || p.nsplit <= 1) return rc;
+  const int64_t n = p.slab_stride;
   const int rb = (int)((n + 255) / 256 < 4096 ? (n + 255) / 256 : 4096);
-  hipLaunchKernelGGL(slab_sum_kernel, dim3(rb), dim3(256), 0, s, slabs, out, n, nsplit_used, act);
+  hipLaunchKernelGGL(slab_sum_kernel, dim3(rb), dim3(256), 0, s, slabs, out, n, p.nsplit, a.act);
   return note_launch(hipGetLastError(), "slab_sum_kernel");
-}
-
-static int ig_used_splits(const IgShape& sh) {
-  const int chunks = (int)((sh.K + kIgKC - 1) / kIgKC);
-  const int cps = (chunks + sh.nsplit - 1) / sh.nsplit;
-  return (chunks + cps - 1) / cps;
 }
 
 static int dconv_fwd(int kind, const float* x, int B, int Cin, int H, int W, const float* w, int Cout, int act, float* ws,
@@ -980,34 +980,21 @@ static int dconv_fwd(int kind, const float* x, int B, int Cin, int H, int W, con
   if (!x || !w || !out || !ws || B < 1 || Cin < 1 || Cout < 1 || H < 2 || W < 2) return TGSR_EINVAL;
   if (kind == 4 && ((H | W) & 1)) return TGSR_EUNSUPPORTED;
   if ((int64_t)B * Cin * H * W >= (1ll << 31)) return TGSR_EUNSUPPORTED;        // 32-bit gather offsets
-  const IgShape sh = ig_shape(kind, 0, B, Cin, H, W, Cout);
+  const IgPlan p = ig_plan(kind, 0, B, Cin, H, W, Cout, true, reinterpret_cast<uintptr_t>(ws) | reinterpret_cast<uintptr_t>(w));
   IgArgs a = {};
   a.A = w; a.S = x; a.C = Cin; a.Hs = H; a.Ws = W;
   a.PH = kind == 4 ? H / 2 : H; a.PW = kind == 4 ? W / 2 : W; a.OH = a.PH; a.OW = a.PW; a.act = act ? 1 : 0;
   hipStream_t s = as_stream(stream);
-  float* slabs = ws + ig_ws_head(kind, 0, sh, Cin, Cout);
-  const bool wide = ig_wide(kind, 0, sh.M);
-  const int64_t img = ig6_image_elems(kind, 0, sh.M, sh.K);
-  a.s_bytes = (int64_t)B * Cin * H * W * 4;
-  a.a_bytes = (g_ig_split & 2) ? img * 4 : (int64_t)Cout * sh.K * 4;
-  if (kind == 3) a.a_bytes = (int64_t)Cout * sh.K * 4;
-  // split form: whole chunks (3x3: 9 Cin % 16 == 0), 16-byte rows of w, both tensors inside a 4 GB descriptor
-  const bool split = g_ig_split && sh.K % kIgKC == 0 && !(reinterpret_cast<uintptr_t>(ws) & 15) &&
-                     !(reinterpret_cast<uintptr_t>(w) & 15) && a.s_bytes < (1ll << 32) && a.a_bytes < (1ll << 32);
-  if (split && (g_ig_split & 2) && kind == 4) {   // the weight, split into three bf16 pieces, as the kernel's LDS images
-    const int64_t MB = wide ? 64 : 128, total = ((sh.M + MB - 1) / MB) * MB * (sh.K / 8);
+  if (p.form == kIgSplitPre) {   // the weight, split into three bf16 pieces, as the kernel's LDS images
+    const int64_t total = (int64_t)p.grid.y * p.MB * (p.K / 8);
     const int pb = (int)((total + 255) / 256 < 8192 ? (total + 255) / 256 : 8192);
-    if (wide) hipLaunchKernelGGL(ig6_split_rows_kernel<64>, dim3(pb), dim3(256), 0, s, w, reinterpret_cast<unsigned*>(ws), (int)sh.M, (int)sh.K, total);
-    else hipLaunchKernelGGL(ig6_split_rows_kernel<128>, dim3(pb), dim3(256), 0, s, w, reinterpret_cast<unsigned*>(ws), (int)sh.M, (int)sh.K, total);
+    if (p.wide) hipLaunchKernelGGL(ig6_split_rows_kernel<64>, dim3(pb), dim3(256), 0, s, w, reinterpret_cast<unsigned*>(ws), (int)p.M, (int)p.K, total);
+    else hipLaunchKernelGGL(ig6_split_rows_kernel<128>, dim3(pb), dim3(256), 0, s, w, reinterpret_cast<unsigned*>(ws), (int)p.M, (int)p.K, total);
     const int prc = note_launch(hipGetLastError(), "ig6_split_rows_kernel");
     if (prc) return prc;
     a.A = ws;
   }
-  const int rc = kind == 4 ? (wide ? ig_launch<kFwd4, true>(a, sh, slabs, out, s, "dconv_igemm_kernel<fwd4, wide>", split)
-                                   : ig_launch<kFwd4>(a, sh, slabs, out, s, "dconv_igemm_kernel<fwd4>", split))
-                           : ig_launch<kFwd3>(a, sh, slabs, out, s, "dconv_igemm_kernel<fwd3>", split);
-  if (rc) return rc;
-  return ig_finish(a, ig_used_splits(sh), act ? 1 : 0, slabs, out, sh.out_elems, s);
+  return dconv_launch(kind, 0, a, p, ws + p.head, out, s);
 }
 
 static int dconv_dgrad(int kind, const float* dy, int B, int Cin, int H, int W, const float* w, int Cout, float* ws,
@@ -1015,14 +1002,12 @@ static int dconv_dgrad(int kind, const float* dy, int B, int Cin, int H, int W, 
   if (!dy || !w || !ws || !dx || B < 1 || Cin < 1 || Cout < 1 || H < 2 || W < 2) return TGSR_EINVAL;
   if (kind == 4 && ((H | W) & 1)) return TGSR_EUNSUPPORTED;
   if ((int64_t)B * Cout * H * W >= (1ll << 31)) return TGSR_EUNSUPPORTED;       // 32-bit gather offsets (dy is at most this)
-  const IgShape sh = ig_shape(kind, 1, B, Cin, H, W, Cout);
+  const IgPlan p = ig_plan(kind, 1, B, Cin, H, W, Cout, true,
+                           kind == 4 ? reinterpret_cast<uintptr_t>(ws) | reinterpret_cast<uintptr_t>(w) : 0);
   hipStream_t s = as_stream(stream);
   IgArgs a = {};
   a.S = dy; a.C = Cout; a.OH = H; a.OW = W;
-  int rc;
-  float* slabs = ws;
-  if (kind == 4 && Cin <= 4 && (int64_t)Cout * Cin * 64 <= 64 * 1024) {
-    // the image layer: M = Cin rows of a 128-row GEMM tile would idle 97 % of the matrix pipe (dconv_dgrad4_image_kernel)
+  if (p.form == kIgImage) {
     const dim3 grid((unsigned)((W / 2 + 63) / 64), (unsigned)((H / 2 + 3) / 4), (unsigned)B);
     const size_t lds = (size_t)Cout * Cin * 16 * sizeof(float);
     switch (Cin) {
@@ -1033,40 +1018,27 @@ static int dconv_dgrad(int kind, const float* dy, int B, int Cin, int H, int W, 
     }
     return note_launch(hipGetLastError(), "dconv_dgrad4_image_kernel");
   }
-  if (kind == 4) {
-    const bool wide = ig_wide(4, 1, sh.M);
-    const int64_t img = ig6_image_elems(4, 1, sh.M, sh.K);
-    a.s_bytes = (int64_t)B * Cout * (H / 2) * (W / 2) * 4;
-    a.a_bytes = (g_ig_split & 2) ? img * 4 : 64ll * Cin * Cout;
-    const bool split = g_ig_split && sh.K % kIgKC == 0 && !(reinterpret_cast<uintptr_t>(ws) & 15) && !(reinterpret_cast<uintptr_t>(w) & 15) &&
-                       a.s_bytes < (1ll << 32) && a.a_bytes < (1ll << 32);
-    if (split && (g_ig_split & 2)) {   // regrouped by parity class AND split into three bf16 pieces, as the kernel's LDS images
-      const int64_t MB = wide ? 64 : 128, mt = (sh.M + MB - 1) / MB, total = mt * MB * (Cout / 2);
-      const int pb = (int)((total + 255) / 256 < 8192 ? (total + 255) / 256 : 8192);
-      if (wide) hipLaunchKernelGGL(ig6_pack_dgrad_kernel<64>, dim3(pb), dim3(256), 0, s, w, reinterpret_cast<unsigned*>(ws), Cout, Cin, (int)mt, total);
-      else hipLaunchKernelGGL(ig6_pack_dgrad_kernel<128>, dim3(pb), dim3(256), 0, s, w, reinterpret_cast<unsigned*>(ws), Cout, Cin, (int)mt, total);
-      rc = note_launch(hipGetLastError(), "ig6_pack_dgrad_kernel");
-    } else {
-      const int64_t total = 16ll * Cin * Cout;
-      const int64_t nf = (int64_t)Cin * Cout;
-      const int pb = (int)((nf + 255) / 256 < 4096 ? (nf + 255) / 256 : 4096);
-      hipLaunchKernelGGL(conv4x4s2_pack_dgrad_kernel, dim3(pb), dim3(256), 0, s, w, ws, Cout, Cin, total);
-      rc = note_launch(hipGetLastError(), "conv4x4s2_pack_dgrad_kernel");
-    }
-    if (rc) return rc;
-    slabs = ws + ig_ws_head(4, 1, sh, Cin, Cout);
-    a.A = ws; a.Hs = H / 2; a.Ws = W / 2; a.PH = H / 2; a.PW = W / 2;
-    rc = wide ? ig_launch<kDgrad4, true>(a, sh, slabs, dx, s, "dconv_igemm_kernel<dgrad4, wide>", split)
-              : ig_launch<kDgrad4>(a, sh, slabs, dx, s, "dconv_igemm_kernel<dgrad4>", split);
-  } else {
+  if (kind == 3) {
     a.A = w; a.Hs = H; a.Ws = W; a.PH = H; a.PW = W;
-    a.s_bytes = (int64_t)B * Cout * H * W * 4;
-    a.a_bytes = 36ll * Cin * Cout;
-    const bool split = g_ig_split && sh.K % kIgKC == 0 && a.s_bytes < (1ll << 32) && a.a_bytes < (1ll << 32);
-    rc = ig_launch<kDgrad3>(a, sh, slabs, dx, s, "dconv_igemm_kernel<dgrad3>", split);
+    return dconv_launch(3, 1, a, p, ws, dx, s);
+  }
+  int rc;
+  if (p.form == kIgSplitPre) {   // regrouped by parity class AND split into three bf16 pieces, as the kernel's LDS images
+    const int64_t mt = p.grid.y, total = mt * p.MB * (Cout / 2);
+    const int pb = (int)((total + 255) / 256 < 8192 ? (total + 255) / 256 : 8192);
+    if (p.wide) hipLaunchKernelGGL(ig6_pack_dgrad_kernel<64>, dim3(pb), dim3(256), 0, s, w, reinterpret_cast<unsigned*>(ws), Cout, Cin, (int)mt, total);
+    else hipLaunchKernelGGL(ig6_pack_dgrad_kernel<128>, dim3(pb), dim3(256), 0, s, w, reinterpret_cast<unsigned*>(ws), Cout, Cin, (int)mt, total);
+    rc = note_launch(hipGetLastError(), "ig6_pack_dgrad_kernel");
+  } else {
+    const int64_t total = 16ll * Cin * Cout;
+    const int64_t nf = (int64_t)Cin * Cout;
+    const int pb = (int)((nf + 255) / 256 < 4096 ? (nf + 255) / 256 : 4096);
+    hipLaunchKernelGGL(conv4x4s2_pack_dgrad_kernel, dim3(pb), dim3(256), 0, s, w, ws, Cout, Cin, total);
+    rc = note_launch(hipGetLastError(), "conv4x4s2_pack_dgrad_kernel");
   }
   if (rc) return rc;
-  return ig_finish(a, ig_used_splits(sh), 0, slabs, dx, sh.out_elems, s);
+  a.A = ws; a.Hs = H / 2; a.Ws = W / 2; a.PH = H / 2; a.PW = W / 2;
+  return dconv_launch(4, 1, a, p, ws + p.head, dx, s);
 }
 
 static int dconv_wgrad(int kind, const float* dy, const float* x, int B, int Cin, int H, int W, int Cout, float* ws,
@@ -1074,88 +1046,39 @@ static int dconv_wgrad(int kind, const float* dy, const float* x, int B, int Cin
   if (!dy || !x || !ws || !dw || B < 1 || Cin < 1 || Cout < 1 || H < 2 || W < 2) return TGSR_EINVAL;
   if (kind == 4 && ((H | W) & 1)) return TGSR_EUNSUPPORTED;
   if ((int64_t)B * Cin * H * W >= (1ll << 31)) return TGSR_EUNSUPPORTED;        // 32-bit gather offsets
-  const IgShape sh = ig_shape(kind, 2, B, Cin, H, W, Cout);
+  const IgPlan p = ig_plan(kind, 2, B, Cin, H, W, Cout, true, reinterpret_cast<uintptr_t>(dy));
   IgArgs a = {};
   a.A = dy; a.S = x; a.C = Cin; a.Hs = H; a.Ws = W;
   a.PH = kind == 4 ? H / 2 : H; a.PW = kind == 4 ? W / 2 : W; a.OH = a.PH; a.OW = a.PW;
-  hipStream_t s = as_stream(stream);
-  // split form: 16-byte rows of dy; a chunk's sixteen pixels inside one image
-  a.a_bytes = (int64_t)B * Cout * a.PH * a.PW * 4;
-  a.s_bytes = (int64_t)B * Cin * H * W * 4;
-  const bool split = g_ig_split && (a.PH * a.PW) % kIgKC == 0 && !(reinterpret_cast<uintptr_t>(dy) & 15) &&
-                     a.s_bytes < (1ll << 32) && a.a_bytes < (1ll << 32);
-  const int rc = kind == 4 ? ig_launch<kWgrad4>(a, sh, ws, dw, s, "dconv_igemm_kernel<wgrad4>", split)
-                           : ig_launch<kWgrad3>(a, sh, ws, dw, s, "dconv_igemm_kernel<wgrad3>", split);
-  if (rc) return rc;
-  return ig_finish(a, ig_used_splits(sh), 0, ws, dw, sh.out_elems, s);
+  return dconv_launch(kind, 2, a, p, ws, dw, as_stream(stream));
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-// Generic-tap convolutions (CNN_ENCODER's frozen trunk: tgsr_igemm.hip owns the entry point, the fp32-MFMA fallback and the slab
-// finish) on dconv_igemm6_kernel: forward (stride 1 | 2) and stride-1 data gradient of any KH x KW <= 32 taps with K % 16 == 0.
-// Returns TGSR_EUNSUPPORTED for shapes this form does not take - the caller then uses its own kernel.
-int ig6_gconv_launch(int dgrad, const float* A, const float* S, int64_t s_bstride, int64_t s_bytes, int B, int Hs, int Ws, int M, int K,
-                     int PH, int PW, int KH, int KW, int stride, int padh, int padw, const float* bias, int relu, int accumulate,
-                     const float* mask, float* out, int64_t o_bstride, float* slabs, int nsplit, int chunks_per_split, hipStream_t s) {
-  const int KK = KH * KW;
-  if (!g_ig_split || KK > 25 || K % kIgKC != 0 || (dgrad && stride != 1) || (stride != 1 && stride != 2)) return TGSR_EUNSUPPORTED;
-  const int64_t a_bytes = (int64_t)M * K * 4;
-  if ((reinterpret_cast<uintptr_t>(A) & 15) || s_bytes >= (1ll << 31) || a_bytes >= (1ll << 32)) return TGSR_EUNSUPPORTED;
-  const int64_t N = (int64_t)B * PH * PW;
-  if (N >= (1ll << 31)) return TGSR_EUNSUPPORTED;
+// Generic-tap convolutions (CNN_ENCODER's frozen trunk: tgsr_igemm.hip owns the entry points, the plan - gc_plan decides which shapes
+// come here - the fp32-MFMA kernel and the slab finish) on dconv_igemm6_kernel: forward (stride 1 | 2), its statistics form, and the
+// stride-1 data gradient of any KH x KW <= 25 taps with K % 16 == 0.
+int ig6_gconv_launch(const IgPlan& p, int mode, const GcArgs& g, hipStream_t s) {
+  const int KK = g.KH * g.KW;
   IgArgs a = {};
-  a.A = A; a.S = S; a.out = nsplit > 1 ? slabs : out;
-  a.M = M; a.N = (int)N; a.K = K; a.C = K / KK; a.Hs = Hs; a.Ws = Ws; a.PH = PH; a.PW = PW; a.OH = PH; a.OW = PW;
-  a.nsplit = nsplit; a.chunks_per_split = chunks_per_split;
-  a.slab_stride = nsplit > 1 ? (int64_t)B * M * PH * PW : 0;
-  a.act = 0;
-  a.a_bytes = a_bytes; a.s_bytes = s_bytes;
-  a.gKH = KH; a.gKW = KW; a.gKK = KK; a.gst = stride; a.gpadh = padh; a.gpadw = padw;
-  a.gmKK = (unsigned)((65536 + KK - 1) / KK); a.gmKW = (unsigned)((65536 + KW - 1) / KW);
-  a.s_bstride = s_bstride; a.o_bstride = o_bstride;
-  a.gbias = bias; a.gmask = mask; a.grelu = relu; a.gacc = accumulate;
-  const bool wide = M <= 64;
-  const dim3 grid(wide ? (unsigned)((N + 255) / 256) : (unsigned)((N + 127) / 128), wide ? (unsigned)((M + 63) / 64) : (unsigned)((M + 127) / 128),
-                  (unsigned)nsplit);
-  if (dgrad) {
-    if (wide) hipLaunchKernelGGL((dconv_igemm6_kernel<kDgradG, true, false>), grid, dim3(256), 0, s, a);
-    else hipLaunchKernelGGL((dconv_igemm6_kernel<kDgradG, false, false>), grid, dim3(256), 0, s, a);
-  } else {
-    if (wide) hipLaunchKernelGGL((dconv_igemm6_kernel<kFwdG, true, false>), grid, dim3(256), 0, s, a);
-    else hipLaunchKernelGGL((dconv_igemm6_kernel<kFwdG, false, false>), grid, dim3(256), 0, s, a);
+  a.A = g.A; a.S = g.S; a.out = g.out;
+  a.M = g.M; a.N = g.N; a.K = g.K; a.C = g.K / KK; a.Hs = g.Hs; a.Ws = g.Ws; a.PH = g.PH; a.PW = g.PW; a.OH = g.PH; a.OW = g.PW;
+  a.nsplit = g.nsplit; a.chunks_per_split = g.chunks_per_split;
+  a.slab_stride = g.nsplit > 1 ? g.slab_stride : 0;
+  a.a_bytes = p.a_bytes; a.s_bytes = p.s_bytes;
+  a.gKH = g.KH; a.gKW = g.KW; a.gKK = KK; a.gst = g.SH; a.gpadh = g.PADH; a.gpadw = g.PADW;
+  a.gmKK = (unsigned)((65536 + KK - 1) / KK); a.gmKW = (unsigned)((65536 + g.KW - 1) / g.KW);
+  a.s_bstride = g.s_bstride; a.o_bstride = g.o_bstride;
+  a.gbias = g.bias; a.grelu = g.relu; a.gacc = g.accumulate;
+  a.gmask = g.mask;                                        // (the union: mode 2's gstat = g.st)
+  switch (2 * mode + (p.wide ? 1 : 0)) {
+    case 0: hipLaunchKernelGGL((dconv_igemm6_kernel<kFwdG, false, false>), p.grid, dim3(256), 0, s, a); break;
+    case 1: hipLaunchKernelGGL((dconv_igemm6_kernel<kFwdG, true, false>), p.grid, dim3(256), 0, s, a); break;
+    case 2: hipLaunchKernelGGL((dconv_igemm6_kernel<kDgradG, false, false>), p.grid, dim3(256), 0, s, a); break;
+    case 3: hipLaunchKernelGGL((dconv_igemm6_kernel<kDgradG, true, false>), p.grid, dim3(256), 0, s, a); break;
+    case 4: hipLaunchKernelGGL((dconv_igemm6_kernel<kFwdG, false, false, true>), p.grid, dim3(256), 0, s, a); break;
+    default: hipLaunchKernelGGL((dconv_igemm6_kernel<kFwdG, true, false, true>), p.grid, dim3(256), 0, s, a); break;
   }
-  return note_launch(hipGetLastError(), "dconv_igemm6_kernel<generic taps>");
-}
-
-// The forward above in its statistics form (one slab: the caller splits K through ig6_gconv_launch and takes the statistics in its
-// slab finish): the raw convolution into its channel slice plus st [M][nslots][2], nslots = the grid's N tiles.
-int ig6_gconv_stats_launch(const float* A, const float* S, int64_t s_bstride, int64_t s_bytes, int B, int Hs, int Ws, int M, int K,
-                           int PH, int PW, int KH, int KW, int stride, int padh, int padw, float* out, int64_t o_bstride, float* st,
-                           int nslots, hipStream_t s) {
-  const int KK = KH * KW;
-  if (!g_ig_split || KK > 25 || K % kIgKC != 0 || (stride != 1 && stride != 2)) return TGSR_EUNSUPPORTED;
-  const int64_t a_bytes = (int64_t)M * K * 4;
-  if ((reinterpret_cast<uintptr_t>(A) & 15) || s_bytes >= (1ll << 31) || a_bytes >= (1ll << 32)) return TGSR_EUNSUPPORTED;
-  const int64_t N = (int64_t)B * PH * PW;
-  if (N >= (1ll << 31)) return TGSR_EUNSUPPORTED;
-  IgArgs a = {};
-  a.A = A; a.S = S; a.out = out;
-  a.M = M; a.N = (int)N; a.K = K; a.C = K / KK; a.Hs = Hs; a.Ws = Ws; a.PH = PH; a.PW = PW; a.OH = PH; a.OW = PW;
-  a.nsplit = 1; a.chunks_per_split = K / kIgKC;
-  a.slab_stride = 0;
-  a.act = 0;
-  a.a_bytes = a_bytes; a.s_bytes = s_bytes;
-  a.gKH = KH; a.gKW = KW; a.gKK = KK; a.gst = stride; a.gpadh = padh; a.gpadw = padw;
-  a.gmKK = (unsigned)((65536 + KK - 1) / KK); a.gmKW = (unsigned)((65536 + KW - 1) / KW);
-  a.s_bstride = s_bstride; a.o_bstride = o_bstride;
-  a.gbias = nullptr; a.grelu = 0; a.gacc = 0;
-  a.gstat = st;                                            // (the union's gmask: none)
-  const bool wide = M <= 64;
-  const dim3 grid(wide ? (unsigned)((N + 255) / 256) : (unsigned)((N + 127) / 128), wide ? (unsigned)((M + 63) / 64) : (unsigned)((M + 127) / 128), 1);
-  if ((int)grid.x != nslots) return TGSR_EINVAL;
-  if (wide) hipLaunchKernelGGL((dconv_igemm6_kernel<kFwdG, true, false, true>), grid, dim3(256), 0, s, a);
-  else hipLaunchKernelGGL((dconv_igemm6_kernel<kFwdG, false, false, true>), grid, dim3(256), 0, s, a);
-  return note_launch(hipGetLastError(), "dconv_igemm6_kernel<generic taps, stats>");
+  return note_launch(hipGetLastError(), mode == 2 ? "dconv_igemm6_kernel<generic taps, stats>" : "dconv_igemm6_kernel<generic taps>");
 }
 
 }  // namespace tgsr
@@ -1168,24 +1091,27 @@ extern "C" int tgsr_dconv_set_split(int on) {
   return was;
 }
 
-extern "C" int tgsr_conv4x4s2_split_form(int op, int B, int Cin, int H, int W, int Cout) {
-  if (!g_ig_split || op < 0 || op > 2 || B < 1 || Cin < 1 || Cout < 1 || H < 2 || W < 2 || ((H | W) & 1)) return 0;
-  const IgShape sh = ig_shape(4, op, B, Cin, H, W, Cout);
-  const int64_t xb = (int64_t)B * Cin * H * W * 4, yb = (int64_t)B * Cout * (H / 2) * (W / 2) * 4, lim = 1ll << 32;
-  if (op == 0) return sh.K % kIgKC == 0 && xb < lim && (int64_t)Cout * sh.K * 4 < lim;
-  if (op == 1) return !(Cin <= 4 && (int64_t)Cout * Cin * 64 <= 64 * 1024) && sh.K % kIgKC == 0 && yb < lim;
-  return ((H / 2) * (W / 2)) % kIgKC == 0 && xb < lim && yb < lim;
+// The exported planners: ig_plan for 16-byte aligned operands.
+static int dconv_split_form(int kind, int op, int B, int Cin, int H, int W, int Cout) {
+  if (op < 0 || op > 2 || B < 1 || Cin < 1 || Cout < 1 || H < 2 || W < 2 || (kind == 4 && ((H | W) & 1))) return 0;
+  const IgForm f = ig_plan(kind, op, B, Cin, H, W, Cout, false).form;
+  return f == kIgSplit || f == kIgSplitPre;
+}
+static int64_t dconv_ws_elems(int kind, int op, int B, int Cin, int H, int W, int Cout) {
+  if (op < 0 || op > 2) return 0;
+  const int64_t n = ig_plan(kind, op, B, Cin, H, W, Cout, false).ws_elems;
+  return n > 0 ? n : 1;
 }
 
+extern "C" int tgsr_conv4x4s2_split_form(int op, int B, int Cin, int H, int W, int Cout) {
+  return dconv_split_form(4, op, B, Cin, H, W, Cout);
+}
 extern "C" int tgsr_conv3x3_gemm_split_form(int op, int B, int Cin, int H, int W, int Cout) {
-  if (!g_ig_split || op < 0 || op > 2 || B < 1 || Cin < 1 || Cout < 1 || H < 2 || W < 2) return 0;
-  const int64_t xb = (int64_t)B * Cin * H * W * 4, yb = (int64_t)B * Cout * H * W * 4, wb = 36ll * Cin * Cout, lim = 1ll << 32;
-  if (xb >= lim || yb >= lim || wb >= lim) return 0;
-  return op == 0 ? (9 * Cin) % kIgKC == 0 : (op == 1 ? (9 * Cout) % kIgKC == 0 : (H * W) % kIgKC == 0);
+  return dconv_split_form(3, op, B, Cin, H, W, Cout);
 }
 
 extern "C" int64_t tgsr_conv4x4s2_ws_elems(int op, int B, int Cin, int H, int W, int Cout) {
-  return (op < 0 || op > 2) ? 0 : ig_ws_elems(4, op, B, Cin, H, W, Cout);
+  return dconv_ws_elems(4, op, B, Cin, H, W, Cout);
 }
 extern "C" int tgsr_conv4x4s2_fwd(const float* x, int B, int Cin, int H, int W, const float* w, int Cout, int act,
                                   float* ws, float* out, void* stream) {
@@ -1201,7 +1127,7 @@ extern "C" int tgsr_conv4x4s2_wgrad(const float* dy, const float* x, int B, int 
 }
 
 extern "C" int64_t tgsr_conv3x3_gemm_ws_elems(int op, int B, int Cin, int H, int W, int Cout) {
-  return (op < 0 || op > 2) ? 0 : ig_ws_elems(3, op, B, Cin, H, W, Cout);
+  return dconv_ws_elems(3, op, B, Cin, H, W, Cout);
 }
 extern "C" int tgsr_conv3x3_gemm_fwd(const float* x, int B, int Cin, int H, int W, const float* w, int Cout, float* ws,
                                      float* out, void* stream) {

@@ -15,28 +15,9 @@
 //   util.py:310) - each forward and backward, all deterministic (gather form, no atomics).
 // Few output pixels against a long reduction (the 8 x 8 stage: N = 1024, K up to 18 432) split K over blockIdx.z into slabs
 // that a finishing kernel sums in a fixed order (+ shift, ReLU, the slice write).
-#include "tgsr_common.h"
+#include "tgsr_igemm_plan.h"
 
 namespace tgsr {
-
-struct GcArgs {
-  const float* A;        // forward: w' [Cout][Cin KH KW]; data gradient: w'T [Cin][Cout KH KW]
-  const float* S;        // the gathered tensor (forward: x, data gradient: g), based at its channel slice
-  const float* bias;     // forward: shift [Cout]; nullptr: none
-  float* out;            // output based at its channel slice (or the slabs when nsplit > 1)
-  int M, N, K;
-  int Hs, Ws;            // spatial size of S
-  int PH, PW;            // the pixel grid N runs over (forward: output pixels; data gradient: input pixels)
-  int64_t s_bstride, o_bstride;      // batch strides (elements) of S and out
-  int KH, KW, SH, PADH, PADW;
-  int relu, accumulate;
-  union {
-    const float* mask;   // nullable; laid out like `out`: the contribution is kept where mask > 0 (the ReLU of the tensor whose gradient this is)
-    float* st;           // STATS (no mask): BatchNorm statistics partials [M][gridDim.x][2]
-  };
-  int nsplit, chunks_per_split;
-  int64_t slab_stride;
-};
 
 constexpr int kGcKC = 16;
 
@@ -523,36 +504,15 @@ __global__ __launch_bounds__(256) void bilinear_bwd_kernel(const float* __restri
   }
 }
 
-// tgsr_down.hip: the same GEMMs on the bf16 matrix pipe with exact three-piece fp32 operands (dconv_igemm6_kernel, generic-tap modes)
-int ig6_gconv_launch(int dgrad, const float* A, const float* S, int64_t s_bstride, int64_t s_bytes, int B, int Hs, int Ws, int M, int K,
-                     int PH, int PW, int KH, int KW, int stride, int padh, int padw, const float* bias, int relu, int accumulate,
-                     const float* mask, float* out, int64_t o_bstride, float* slabs, int nsplit, int chunks_per_split, hipStream_t s);
-// ... and its statistics form (forward, one slab: the raw convolution plus one (sum, sum of squares) pair per channel and N tile)
-int ig6_gconv_stats_launch(const float* A, const float* S, int64_t s_bstride, int64_t s_bytes, int B, int Hs, int Ws, int M, int K,
-                           int PH, int PW, int KH, int KW, int stride, int padh, int padw, float* out, int64_t o_bstride, float* st,
-                           int nslots, hipStream_t s);
+static_assert(kGcKC == kIgKC, "one K-chunk for the family: the plan counts chunks of kIgKC");
 
-static int g_gconv_form = [] {              // TGSR_GCONV_SPLIT=0: the fp32-MFMA kernel of this file everywhere
+// 1 (default): the generic taps run on the bf16 matrix pipe with exact three-piece operands (tgsr_down.hip's dconv_igemm6_kernel) where
+// the shape qualifies; 0: the fp32-MFMA kernel of this file everywhere.  TGSR_GCONV_SPLIT=0 | tgsr_gconv_set_form(0).  Process-wide, and
+// not alone: tgsr_down.hip's switch (ig6_enabled) must be on as well.
+static int g_gconv_form = [] {
   const char* e = getenv("TGSR_GCONV_SPLIT");
   return e ? atoi(e) : 1;
 }();
-
-static int gc_grid(int64_t total, int cap = 8192) {
-  const int64_t b = (total + 255) / 256;
-  return (int)(b < 1 ? 1 : (b > cap ? cap : b));
-}
-
-}  // namespace tgsr
-
-using namespace tgsr;
-
-// 1 (default): tgsr_gconv runs on the bf16 matrix pipe with exact three-piece operands where the shape qualifies; 0: fp32 MFMA
-// everywhere.  Returns the previous setting.  (TGSR_GCONV_SPLIT sets the initial value.)
-extern "C" int tgsr_gconv_set_form(int split) {
-  const int was = g_gconv_form;
-  g_gconv_form = split ? 1 : 0;
-  return was;
-}
 
 // Workgroups a launch should reach before the reduction is split no further (TGSR_GCONV_FILL; default 224 = a little under one per
 // CU: the trunk's branches run side by side on streams of their own, inception.py, so a launch need not fill the chip alone.
@@ -564,117 +524,139 @@ static int g_gconv_fill = [] {
   return v < 1 ? 224 : v;
 }();
 
-// How many K slabs a shape is split into (1 = none): fill ~g_gconv_fill workgroups when M x N alone cannot.
-extern "C" int tgsr_gconv_nsplit(int M, int N, int K) {
-  const bool wide = M <= 64;
-  const int64_t tiles = (int64_t)((M + (wide ? 63 : 127)) / (wide ? 64 : 128)) * ((N + (wide ? 255 : 127)) / (wide ? 256 : 128));
-  const int chunks = (K + kGcKC - 1) / kGcKC;
-  if (tiles >= 192 || tiles * 5 >= g_gconv_fill * 3 || chunks < 16) return 1;   // (every split costs a finishing launch: ~7 us each)
-  int64_t s = (g_gconv_fill + tiles - 1) / tiles;
-  if (s > chunks / 8) s = chunks / 8;                      // at least 8 chunks (128 k) per slab
-  if (s > 32) s = 32;
-  return (int)(s < 1 ? 1 : s);
+static int gc_grid(int64_t total, int cap = 8192) {
+  const int64_t b = (total + 255) / 256;
+  return (int)(b < 1 ? 1 : (b > cap ? cap : b));
 }
 
-extern "C" int64_t tgsr_gconv_ws_elems(int B, int M, int PH, int PW, int K) {
-  const int ns = tgsr_gconv_nsplit(M, B * PH * PW, K);
-  return ns > 1 ? (int64_t)ns * B * M * PH * PW : 0;
+// The plan of one generic-tap call.  mode: 0 forward, 1 data gradient, 2 the forward with BatchNorm statistics; GEMM M x N x K, N =
+// B PH PW pixels, `slab` = B M PH PW output elements, KK taps.  s_bytes: what S spans from its slice's base; a_align: A's address.
+// The exported planners know neither taps nor addresses and read only tile, split, workspace and slots: they ask as for a 1 x 1 layer.
+static IgPlan gc_plan(int mode, int M, int64_t N, int K, int64_t slab, int KK = 1, int stride = 1, bool mask = false,
+                      int64_t s_bytes = 0, uintptr_t a_align = 0) {
+  IgPlan p = {};
+  p.M = M; p.N = N; p.K = K; p.ncls = 1; p.slab_stride = slab;
+  ig_tile(p, M <= 64);
+  // K slabs: fill ~g_gconv_fill workgroups when M x N alone cannot (every split costs a finishing launch: ~7 us each)
+  const int64_t tiles = ig_tiles(p);
+  const int chunks = (K + kIgKC - 1) / kIgKC;
+  int64_t asked = 1;
+  if (!(tiles >= 192 || tiles * 5 >= g_gconv_fill * 3 || chunks < 16)) {
+    asked = (g_gconv_fill + tiles - 1) / tiles;
+    if (asked > chunks / 8) asked = chunks / 8;                 // at least 8 chunks (128 k) per slab
+    if (asked > 32) asked = 32;
+  }
+  ig_split(p, asked < 1 ? 1 : asked);
+  // statistics: one slot per N tile of the GEMM, or per kGcStatR pixels when K is split and the slab finish takes them
+  p.slot_px = p.nsplit > 1 ? kGcStatR : p.NB;
+  p.nslots = (int)((N + p.slot_px - 1) / p.slot_px);
+  p.a_bytes = (int64_t)M * K * 4;
+  p.s_bytes = s_bytes;
+  // The three-piece form (~2.4x the fp32 MFMA's rate): both switches on, whole chunks, <= 25 taps (the trunk's largest filter is
+  // 5 x 5; the kernel's tap mask would hold 32), the data gradient at stride 1 only, 16-byte loads of A, A inside a buffer descriptor's
+  // 32-bit num_records - and S inside 2^31 bytes, not 2^32: the generic modes form a tap's byte offset in SIGNED 32-bit arithmetic
+  // ((channel HsWs +- tap) * 4, negative for the data gradient) and add it mod 2^32 to an anchor that may lie before the image.
+  if (mode == 1 && M <= 4 && !mask && (int64_t)M * K * 4 <= 48 * 1024) p.form = kIgImage;   // an image's gradient: one thread per pixel
+  else if (g_gconv_form && ig6_enabled() && KK <= 25 && K % kIgKC == 0 && !(mode == 1 && stride != 1) && !(a_align & 15) &&
+           s_bytes < (1ll << 31) && p.a_bytes < (1ll << 32)) p.form = kIgSplit;
+  else p.form = kIgFp32;
+  return p;
 }
+
+// tgsr_gconv (mode 0 | 1) and tgsr_gconv_stats (mode 2: bias / relu / accumulate / mask none, st = stat_partial)
+static int gc_run(int mode, const float* A, const float* S, int64_t s_bstride, int B, int Hs, int Ws, int M, int K, int PH, int PW, int KH,
+                  int KW, int stride, int padh, int padw, const float* bias, int relu, int accumulate, const float* mask, float* out,
+                  int64_t o_bstride, float* ws, float* st, void* stream) {
+  if (!A || !S || !out || (mode == 2 && !st) || B < 1 || M < 1 || K < 1 || Hs < 1 || Ws < 1 || PH < 1 || PW < 1) return TGSR_EINVAL;
+  if (KH < 1 || KW < 1 || KH * KW > 64 || KH > 255 || KW > 255 || (stride != 1 && stride != 2) || padh < 0 || padw < 0) return TGSR_EUNSUPPORTED;
+  if (K % (KH * KW)) return TGSR_EINVAL;
+  if (mode == 1 && (bias || relu)) return TGSR_EINVAL;
+  const int64_t N64 = (int64_t)B * PH * PW;
+  if (N64 >= (1ll << 31) || (int64_t)M * K >= (1ll << 31)) return TGSR_EUNSUPPORTED;
+  const int N = (int)N64, KK = KH * KW;
+  const IgPlan p = gc_plan(mode, M, N64, K, (int64_t)B * M * PH * PW, KK, stride, mask != nullptr,
+                           ((int64_t)(B - 1) * s_bstride + (int64_t)(K / KK) * Hs * Ws) * 4, reinterpret_cast<uintptr_t>(A));
+  hipStream_t s = as_stream(stream);
+  if (p.form == kIgImage) {
+    const size_t lds = (size_t)M * K * sizeof(float);
+    const int Cout = K / KK;
+    const dim3 g1(gc_grid(N64, 16384));
+    switch (M) {
+      case 1: hipLaunchKernelGGL(gconv_image_dgrad_kernel<1>, g1, dim3(256), lds, s, A, S, out, Cout, Hs, Ws, PH, PW, KH, KW, stride, padh, padw, s_bstride, o_bstride, B, accumulate); break;
+      case 2: hipLaunchKernelGGL(gconv_image_dgrad_kernel<2>, g1, dim3(256), lds, s, A, S, out, Cout, Hs, Ws, PH, PW, KH, KW, stride, padh, padw, s_bstride, o_bstride, B, accumulate); break;
+      case 3: hipLaunchKernelGGL(gconv_image_dgrad_kernel<3>, g1, dim3(256), lds, s, A, S, out, Cout, Hs, Ws, PH, PW, KH, KW, stride, padh, padw, s_bstride, o_bstride, B, accumulate); break;
+      default: hipLaunchKernelGGL(gconv_image_dgrad_kernel<4>, g1, dim3(256), lds, s, A, S, out, Cout, Hs, Ws, PH, PW, KH, KW, stride, padh, padw, s_bstride, o_bstride, B, accumulate); break;
+    }
+    return note_launch(hipGetLastError(), "gconv_image_dgrad_kernel");
+  }
+  if (p.nsplit > 1 && !ws) return TGSR_EINVAL;
+  const bool stats = mode == 2 && p.nsplit == 1;           // in the GEMM's epilogue; with a K split the slab finish takes them
+  GcArgs a;
+  a.A = A; a.S = S; a.bias = bias; a.out = p.nsplit > 1 ? ws : out;
+  a.M = M; a.N = N; a.K = K; a.Hs = Hs; a.Ws = Ws; a.PH = PH; a.PW = PW;
+  a.s_bstride = s_bstride; a.o_bstride = o_bstride;
+  a.KH = KH; a.KW = KW; a.SH = stride; a.PADH = padh; a.PADW = padw;
+  a.relu = relu; a.accumulate = accumulate; a.mask = mask;
+  if (stats) a.st = st;                                    // (the union's mask: none)
+  a.nsplit = p.nsplit; a.chunks_per_split = p.cps; a.slab_stride = p.slab_stride;
+  int rc;
+  if (p.form == kIgSplit) {
+    rc = ig6_gconv_launch(p, stats ? 2 : mode & 1, a, s);
+  } else {
+    switch ((stats ? 4 : 2 * (mode & 1)) + (p.wide ? 1 : 0)) {
+      case 0: hipLaunchKernelGGL((gconv_igemm_kernel<false, false>), p.grid, dim3(256), 0, s, a); break;
+      case 1: hipLaunchKernelGGL((gconv_igemm_kernel<false, true>), p.grid, dim3(256), 0, s, a); break;
+      case 2: hipLaunchKernelGGL((gconv_igemm_kernel<true, false>), p.grid, dim3(256), 0, s, a); break;
+      case 3: hipLaunchKernelGGL((gconv_igemm_kernel<true, true>), p.grid, dim3(256), 0, s, a); break;
+      case 4: hipLaunchKernelGGL((gconv_igemm_kernel<false, false, true>), p.grid, dim3(256), 0, s, a); break;
+      default: hipLaunchKernelGGL((gconv_igemm_kernel<false, true, true>), p.grid, dim3(256), 0, s, a); break;
+    }
+    rc = note_launch(hipGetLastError(), stats ? "gconv_igemm_kernel<stats>" : "gconv_igemm_kernel");
+  }
+  if (rc || p.nsplit == 1) return rc;
+  if (mode == 2) {
+    hipLaunchKernelGGL(gconv_finish_stats_kernel, dim3(p.nslots, M), dim3(256), 0, s, ws, p.nsplit, p.slab_stride, out, M, PH * PW, N,
+                       o_bstride, st, p.nslots);
+    return note_launch(hipGetLastError(), "gconv_finish_stats_kernel");
+  }
+  hipLaunchKernelGGL(gconv_finish_kernel, dim3(gc_grid(p.slab_stride)), dim3(256), 0, s, ws, p.nsplit, p.slab_stride, bias, out, M, PH * PW,
+                     p.slab_stride, o_bstride, relu, accumulate, mask);
+  return note_launch(hipGetLastError(), "gconv_finish_kernel");
+}
+
+}  // namespace tgsr
+
+using namespace tgsr;
+
+// The arithmetic form of tgsr_gconv / tgsr_gconv_stats (g_gconv_form).  Returns the previous setting.
+extern "C" int tgsr_gconv_set_form(int split) {
+  const int was = g_gconv_form;
+  g_gconv_form = split ? 1 : 0;
+  return was;
+}
+
+// The exported planners: reads of gc_plan.  K slabs the fill heuristic asks for (1 = none), and the workspace they take.
+extern "C" int tgsr_gconv_nsplit(int M, int N, int K) { return gc_plan(0, M, N, K, 0).asked; }
+extern "C" int64_t tgsr_gconv_ws_elems(int B, int M, int PH, int PW, int K) {
+  return gc_plan(0, M, (int64_t)B * PH * PW, K, (int64_t)B * M * PH * PW).ws_elems;
+}
+
+// Statistics slots per channel of tgsr_gconv_stats and pixels per slot (the last slot holds the remainder).
+static IgPlan gc_stats_plan(int B, int M, int PH, int PW, int K) {
+  const int64_t N = (int64_t)B * PH * PW;
+  if (B < 1 || M < 1 || PH < 1 || PW < 1 || K < 1 || N >= (1ll << 31)) return IgPlan{};
+  return gc_plan(2, M, N, K, N * M);
+}
+extern "C" int tgsr_gconv_stats_nslots(int B, int M, int PH, int PW, int K) { return gc_stats_plan(B, M, PH, PW, K).nslots; }
+extern "C" int tgsr_gconv_stats_slot_pixels(int B, int M, int PH, int PW, int K) { return gc_stats_plan(B, M, PH, PW, K).slot_px; }
 
 // dgrad = 0: forward (S = x [.., Cin = K / (KH KW), Hs, Ws], pixel grid = output PH x PW); 1: data gradient (S = g [.., Cout, Hs, Ws]
 // = the forward's OUTPUT grid, pixel grid = the forward's input PH x PW).  A = the matching pack of tgsr_gconv_pack.
 extern "C" int tgsr_gconv(int dgrad, const float* A, const float* S, int64_t s_bstride, int B, int Hs, int Ws, int M, int K, int PH,
                           int PW, int KH, int KW, int stride, int padh, int padw, const float* bias, int relu, int accumulate,
                           const float* mask, float* out, int64_t o_bstride, float* ws, void* stream) {
-  if (!A || !S || !out || B < 1 || M < 1 || K < 1 || Hs < 1 || Ws < 1 || PH < 1 || PW < 1) return TGSR_EINVAL;
-  if (KH < 1 || KW < 1 || KH * KW > 64 || KH > 255 || KW > 255 || (stride != 1 && stride != 2) || padh < 0 || padw < 0) return TGSR_EUNSUPPORTED;
-  if (K % (KH * KW)) return TGSR_EINVAL;
-  if (dgrad && (bias || relu)) return TGSR_EINVAL;
-  const int64_t N64 = (int64_t)B * PH * PW;
-  if (N64 >= (1ll << 31) || (int64_t)M * K >= (1ll << 31)) return TGSR_EUNSUPPORTED;
-  const int N = (int)N64;
-  GcArgs a;
-  a.A = A; a.S = S; a.bias = bias; a.out = out;
-  a.M = M; a.N = N; a.K = K; a.Hs = Hs; a.Ws = Ws; a.PH = PH; a.PW = PW;
-  a.s_bstride = s_bstride; a.o_bstride = o_bstride;
-  a.KH = KH; a.KW = KW; a.SH = stride; a.PADH = padh; a.PADW = padw;
-  a.relu = relu; a.accumulate = accumulate; a.mask = mask;
-  if (dgrad && M <= 4 && !mask && (int64_t)M * K * 4 <= 48 * 1024) {
-    // the gradient with respect to an image: one thread per pixel (gconv_image_dgrad_kernel)
-    const size_t lds = (size_t)M * K * sizeof(float);
-    const int Cout = K / (KH * KW);
-    const dim3 g1(gc_grid(N64, 16384));
-    hipStream_t s1 = as_stream(stream);
-    switch (M) {
-      case 1: hipLaunchKernelGGL(gconv_image_dgrad_kernel<1>, g1, dim3(256), lds, s1, A, S, out, Cout, Hs, Ws, PH, PW, KH, KW, stride, padh, padw, s_bstride, o_bstride, B, accumulate); break;
-      case 2: hipLaunchKernelGGL(gconv_image_dgrad_kernel<2>, g1, dim3(256), lds, s1, A, S, out, Cout, Hs, Ws, PH, PW, KH, KW, stride, padh, padw, s_bstride, o_bstride, B, accumulate); break;
-      case 3: hipLaunchKernelGGL(gconv_image_dgrad_kernel<3>, g1, dim3(256), lds, s1, A, S, out, Cout, Hs, Ws, PH, PW, KH, KW, stride, padh, padw, s_bstride, o_bstride, B, accumulate); break;
-      default: hipLaunchKernelGGL(gconv_image_dgrad_kernel<4>, g1, dim3(256), lds, s1, A, S, out, Cout, Hs, Ws, PH, PW, KH, KW, stride, padh, padw, s_bstride, o_bstride, B, accumulate); break;
-    }
-    return note_launch(hipGetLastError(), "gconv_image_dgrad_kernel");
-  }
-  const int chunks = (K + kGcKC - 1) / kGcKC;
-  int ns = tgsr_gconv_nsplit(M, N, K);
-  if (ns > 1 && !ws) return TGSR_EINVAL;
-  a.chunks_per_split = (chunks + ns - 1) / ns;
-  ns = (chunks + a.chunks_per_split - 1) / a.chunks_per_split;
-  a.nsplit = ns;
-  a.slab_stride = (int64_t)B * M * PH * PW;
-  if (ns > 1) a.out = ws;
-  hipStream_t s = as_stream(stream);
-  const bool wide = M <= 64;
-  const dim3 grid((N + (wide ? 255 : 127)) / (wide ? 256 : 128), (M + (wide ? 63 : 127)) / (wide ? 64 : 128), ns);
-  // the three-piece bf16 form where the shape qualifies (K % 16 == 0, <= 25 taps, stride-1 data gradient): ~2.4x the fp32 MFMA's rate
-  int rc6 = TGSR_EUNSUPPORTED;
-  if (g_gconv_form) {
-    const int64_t s_bytes = ((int64_t)(B - 1) * s_bstride + (int64_t)(K / (KH * KW)) * Hs * Ws) * 4;
-    rc6 = ig6_gconv_launch(dgrad, A, S, s_bstride, s_bytes, B, Hs, Ws, M, K, PH, PW, KH, KW, stride, padh, padw, bias, relu, accumulate,
-                           mask, out, o_bstride, ws, ns, a.chunks_per_split, s);
-    if (rc6 != TGSR_OK && rc6 != TGSR_EUNSUPPORTED) return rc6;
-  }
-  if (rc6 == TGSR_OK) {
-    // (falls through to the slab finish below)
-  } else if (dgrad) {
-    if (wide) hipLaunchKernelGGL((gconv_igemm_kernel<true, true>), grid, dim3(256), 0, s, a);
-    else hipLaunchKernelGGL((gconv_igemm_kernel<true, false>), grid, dim3(256), 0, s, a);
-  } else {
-    if (wide) hipLaunchKernelGGL((gconv_igemm_kernel<false, true>), grid, dim3(256), 0, s, a);
-    else hipLaunchKernelGGL((gconv_igemm_kernel<false, false>), grid, dim3(256), 0, s, a);
-  }
-  int rc = note_launch(hipGetLastError(), "gconv_igemm_kernel");
-  if (rc || ns == 1) return rc;
-  const int64_t total = a.slab_stride;
-  hipLaunchKernelGGL(gconv_finish_kernel, dim3(gc_grid(total)), dim3(256), 0, s, ws, ns, a.slab_stride, bias, out, M, PH * PW, total,
-                     o_bstride, relu, accumulate, mask);
-  return note_launch(hipGetLastError(), "gconv_finish_kernel");
-}
-
-// The K split tgsr_gconv / tgsr_gconv_stats use for a forward shape: (slabs, chunks per slab).
-static void gc_split(int M, int N, int K, int& ns, int& cps) {
-  const int chunks = (K + kGcKC - 1) / kGcKC;
-  ns = tgsr_gconv_nsplit(M, N, K);
-  cps = (chunks + ns - 1) / ns;
-  ns = (chunks + cps - 1) / cps;
-}
-
-// Statistics slots per channel of tgsr_gconv_stats: one per N tile of the GEMM, or per kGcStatR pixels when K is split.
-extern "C" int tgsr_gconv_stats_nslots(int B, int M, int PH, int PW, int K) {
-  const int64_t N64 = (int64_t)B * PH * PW;
-  if (B < 1 || M < 1 || PH < 1 || PW < 1 || K < 1 || N64 >= (1ll << 31)) return 0;
-  const int N = (int)N64;
-  int ns, cps;
-  gc_split(M, N, K, ns, cps);
-  if (ns > 1) return (N + kGcStatR - 1) / kGcStatR;
-  return M <= 64 ? (N + 255) / 256 : (N + 127) / 128;
-}
-
-// Pixels per statistics slot of tgsr_gconv_stats (the last slot holds the remainder): the GEMM's N tile, or kGcStatR when K is split.
-extern "C" int tgsr_gconv_stats_slot_pixels(int B, int M, int PH, int PW, int K) {
-  const int64_t N64 = (int64_t)B * PH * PW;
-  if (B < 1 || M < 1 || PH < 1 || PW < 1 || K < 1 || N64 >= (1ll << 31)) return 0;
-  int ns, cps;
-  gc_split(M, (int)N64, K, ns, cps);
-  return ns > 1 ? kGcStatR : (M <= 64 ? 256 : 128);
+  return gc_run(dgrad ? 1 : 0, A, S, s_bstride, B, Hs, Ws, M, K, PH, PW, KH, KW, stride, padh, padw, bias, relu, accumulate, mask, out,
+                o_bstride, ws, nullptr, stream);
 }
 
 // Training-mode forward of a conv + BatchNorm layer, first half: the raw convolution (no bias, no ReLU) into its channel slice
@@ -683,50 +665,8 @@ extern "C" int tgsr_gconv_stats_slot_pixels(int B, int M, int PH, int PW, int K)
 extern "C" int tgsr_gconv_stats(const float* A, const float* S, int64_t s_bstride, int B, int Hs, int Ws, int M, int K, int PH,
                                 int PW, int KH, int KW, int stride, int padh, int padw, float* out, int64_t o_bstride, float* ws,
                                 float* stat_partial, void* stream) {
-  if (!A || !S || !out || !stat_partial || B < 1 || M < 1 || K < 1 || Hs < 1 || Ws < 1 || PH < 1 || PW < 1) return TGSR_EINVAL;
-  if (KH < 1 || KW < 1 || KH * KW > 64 || KH > 255 || KW > 255 || (stride != 1 && stride != 2) || padh < 0 || padw < 0) return TGSR_EUNSUPPORTED;
-  if (K % (KH * KW)) return TGSR_EINVAL;
-  const int64_t N64 = (int64_t)B * PH * PW;
-  if (N64 >= (1ll << 31) || (int64_t)M * K >= (1ll << 31)) return TGSR_EUNSUPPORTED;
-  const int N = (int)N64;
-  int ns, cps;
-  gc_split(M, N, K, ns, cps);
-  if (ns > 1 && !ws) return TGSR_EINVAL;
-  const int nslots = tgsr_gconv_stats_nslots(B, M, PH, PW, K);
-  hipStream_t s = as_stream(stream);
-  GcArgs a;
-  a.A = A; a.S = S; a.bias = nullptr; a.out = ns > 1 ? ws : out;
-  a.M = M; a.N = N; a.K = K; a.Hs = Hs; a.Ws = Ws; a.PH = PH; a.PW = PW;
-  a.s_bstride = s_bstride; a.o_bstride = o_bstride;
-  a.KH = KH; a.KW = KW; a.SH = stride; a.PADH = padh; a.PADW = padw;
-  a.relu = 0; a.accumulate = 0;
-  a.st = ns > 1 ? nullptr : stat_partial;                // (the union's mask: none)
-  a.nsplit = ns; a.chunks_per_split = cps; a.slab_stride = (int64_t)B * M * PH * PW;
-  const bool wide = M <= 64;
-  const dim3 grid((N + (wide ? 255 : 127)) / (wide ? 256 : 128), (M + (wide ? 63 : 127)) / (wide ? 64 : 128), ns);
-  int rc6 = TGSR_EUNSUPPORTED;
-  if (g_gconv_form) {
-    const int64_t s_bytes = ((int64_t)(B - 1) * s_bstride + (int64_t)(K / (KH * KW)) * Hs * Ws) * 4;
-    rc6 = ns > 1 ? ig6_gconv_launch(0, A, S, s_bstride, s_bytes, B, Hs, Ws, M, K, PH, PW, KH, KW, stride, padh, padw, nullptr, 0, 0,
-                                    nullptr, out, o_bstride, ws, ns, cps, s)
-                 : ig6_gconv_stats_launch(A, S, s_bstride, s_bytes, B, Hs, Ws, M, K, PH, PW, KH, KW, stride, padh, padw, out,
-                                          o_bstride, stat_partial, nslots, s);
-    if (rc6 != TGSR_OK && rc6 != TGSR_EUNSUPPORTED) return rc6;
-  }
-  if (rc6 == TGSR_OK) {
-    if (ns == 1) return TGSR_OK;
-  } else if (ns > 1) {                       // K split: the slabs of tgsr_gconv, then the statistics finish below
-    if (wide) hipLaunchKernelGGL((gconv_igemm_kernel<false, true>), grid, dim3(256), 0, s, a);
-    else hipLaunchKernelGGL((gconv_igemm_kernel<false, false>), grid, dim3(256), 0, s, a);
-  } else {
-    if (wide) hipLaunchKernelGGL((gconv_igemm_kernel<false, true, true>), grid, dim3(256), 0, s, a);
-    else hipLaunchKernelGGL((gconv_igemm_kernel<false, false, true>), grid, dim3(256), 0, s, a);
-  }
-  int rc = note_launch(hipGetLastError(), "gconv_igemm_kernel<stats>");
-  if (rc || ns == 1) return rc;
-  hipLaunchKernelGGL(gconv_finish_stats_kernel, dim3(nslots, M), dim3(256), 0, s, ws, ns, a.slab_stride, out, M, PH * PW, N, o_bstride,
-                     stat_partial, nslots);
-  return note_launch(hipGetLastError(), "gconv_finish_stats_kernel");
+  return gc_run(2, A, S, s_bstride, B, Hs, Ws, M, K, PH, PW, KH, KW, stride, padh, padw, nullptr, 0, 0, nullptr, out, o_bstride, ws,
+                stat_partial, stream);
 }
 
 extern "C" int tgsr_gconv_pack(const float* w, const float* scale, float* out, int Cout, int Cin, int KK, int dgrad, void* stream) {

@@ -1411,6 +1411,24 @@ def gconv_ws_elems(B: int, M: int, PH: int, PW: int, K: int) -> int:
     return int(_lib.lib().tgsr_gconv_ws_elems(B, M, PH, PW, K))
 
 
+def _gconv_check(name, dgrad, A, S, s_coff, s_ch, out, o_coff, kh, kw, stride, padh, padw, ws):
+    """The shape and workspace checks gconv and gconv_stats share; returns (B, Hs, Ws, M, K, PH, PW)."""
+    M, K = A.shape
+    B, Hs, Ws = S.shape[0], S.shape[2], S.shape[3]
+    PH, PW = out.shape[2], out.shape[3]
+    if K != s_ch * kh * kw or s_coff + s_ch > S.shape[1] or o_coff + M > out.shape[1] or out.shape[0] != B:
+        raise TgsrError("%s: A %s against %d channels of %s -> channels %d.. of %s" % (name, tuple(A.shape), s_ch, tuple(S.shape), o_coff,
+                                                                                       tuple(out.shape)))
+    (h_in, w_in), (h_out, w_out) = ((PH, PW), (Hs, Ws)) if dgrad else ((Hs, Ws), (PH, PW))
+    if h_out != (h_in + 2 * padh - kh) // stride + 1 or w_out != (w_in + 2 * padw - kw) // stride + 1:
+        raise TgsrError("%s: %dx%d / stride %d / pad (%d, %d) does not map %s to %s" % (name, kh, kw, stride, padh, padw, tuple(S.shape),
+                                                                                       tuple(out.shape)))
+    need = gconv_ws_elems(B, M, PH, PW, K)
+    if need and (ws is None or ws.numel() < need):
+        raise TgsrError("%s: %d floats of workspace needed" % (name, need))
+    return B, Hs, Ws, M, K, PH, PW
+
+
 def gconv(dgrad: bool, A: torch.Tensor, S: torch.Tensor, s_coff: int, s_ch: int, out: torch.Tensor, o_coff: int, kh: int, kw: int,
           stride: int, padh: int, padw: int, bias: Optional[torch.Tensor], relu: bool, accumulate: bool, ws: Optional[torch.Tensor],
           mask: Optional[torch.Tensor] = None):
@@ -1420,29 +1438,12 @@ def gconv(dgrad: bool, A: torch.Tensor, S: torch.Tensor, s_coff: int, s_ch: int,
     _need_hip(A, S, out, bias, ws, mask)
     if mask is not None and (mask.shape != out.shape or not mask.is_contiguous() or mask.dtype != torch.float32):
         raise TgsrError("gconv: the mask must be a dense fp32 tensor shaped like the output")
-    M, K = A.shape
-    B, Hs, Ws = S.shape[0], S.shape[2], S.shape[3]
-    PH, PW = out.shape[2], out.shape[3]
-    if K != s_ch * kh * kw or s_coff + s_ch > S.shape[1] or o_coff + M > out.shape[1] or out.shape[0] != B:
-        raise TgsrError("gconv: A %s against %d channels of %s -> channels %d.. of %s" % (tuple(A.shape), s_ch, tuple(S.shape), o_coff,
-                                                                                          tuple(out.shape)))
-    if dgrad:
-        ok = Hs == (PH + 2 * padh - kh) // stride + 1 and Ws == (PW + 2 * padw - kw) // stride + 1
-    else:
-        ok = PH == (Hs + 2 * padh - kh) // stride + 1 and PW == (Ws + 2 * padw - kw) // stride + 1
-    if not ok:
-        raise TgsrError("gconv: %dx%d / stride %d / pad (%d, %d) does not map %s to %s" % (kh, kw, stride, padh, padw, tuple(S.shape),
-                                                                                          tuple(out.shape)))
-    need = gconv_ws_elems(B, M, PH, PW, K)
-    if need and (ws is None or ws.numel() < need):
-        raise TgsrError("gconv: %d floats of workspace needed" % need)
+    B, Hs, Ws, M, K, PH, PW = _gconv_check("gconv", dgrad, A, S, s_coff, s_ch, out, o_coff, kh, kw, stride, padh, padw, ws)
     sp, sbs = _slice_ptr(S, s_coff)
     op, obs = _slice_ptr(out, o_coff)
     mp = None if mask is None else _slice_ptr(mask, o_coff)[0]
     check(_lib.lib().tgsr_gconv(1 if dgrad else 0, _p(A.contiguous()), sp, sbs, B, Hs, Ws, M, K, PH, PW, kh, kw, stride, padh, padw,
                                 _p(bias), 1 if relu else 0, 1 if accumulate else 0, mp, op, obs, _p(ws), _stream()), "tgsr_gconv")
-
-
 
 
 def gconv_stats_nslots(B: int, M: int, PH: int, PW: int, K: int) -> int:
@@ -1461,18 +1462,7 @@ def gconv_stats(A: torch.Tensor, S: torch.Tensor, s_coff: int, s_ch: int, out: t
     its BatchNorm batch statistics: per output channel and slot of gconv_stats_slot_pixels pixels the pair (sum, sum of squared
     deviations from the slot's mean), stat_partial [M, nslots, 2] (allocated when None).  Returns stat_partial."""
     _need_hip(A, S, out, ws, stat_partial)
-    M, K = A.shape
-    B, Hs, Ws = S.shape[0], S.shape[2], S.shape[3]
-    PH, PW = out.shape[2], out.shape[3]
-    if K != s_ch * kh * kw or s_coff + s_ch > S.shape[1] or o_coff + M > out.shape[1] or out.shape[0] != B:
-        raise TgsrError("gconv_stats: A %s against %d channels of %s -> channels %d.. of %s" % (tuple(A.shape), s_ch, tuple(S.shape),
-                                                                                                o_coff, tuple(out.shape)))
-    if PH != (Hs + 2 * padh - kh) // stride + 1 or PW != (Ws + 2 * padw - kw) // stride + 1:
-        raise TgsrError("gconv_stats: %dx%d / stride %d / pad (%d, %d) does not map %s to %s" % (kh, kw, stride, padh, padw,
-                                                                                                tuple(S.shape), tuple(out.shape)))
-    need = gconv_ws_elems(B, M, PH, PW, K)
-    if need and (ws is None or ws.numel() < need):
-        raise TgsrError("gconv_stats: %d floats of workspace needed" % need)
+    B, Hs, Ws, M, K, PH, PW = _gconv_check("gconv_stats", False, A, S, s_coff, s_ch, out, o_coff, kh, kw, stride, padh, padw, ws)
     ns = gconv_stats_nslots(B, M, PH, PW, K)
     if stat_partial is None:
         stat_partial = torch.empty(M, ns, 2, dtype=torch.float32, device=out.device)
