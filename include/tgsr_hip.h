@@ -194,6 +194,22 @@ int tgsr_conv_to3_fwd(const float* x, int64_t x_bstride, int B, int Cin, int H, 
                       int act, const float* addend, float alpha, float* out, void* stream);
 
 /*
+ * The closing launch of the fp32 inference step: tgsr_conv_to3_fwd(act = TGSR_ACT_NONE) of the LAST low-frequency head and the
+ * `+ a * SRb` of every NetG_highweight head (tgsr_axpy_images) in one launch.  n = 1..3 triples (fine[k], t[k], s[k]) of numel[k]
+ * dense floats; the last one (k = n - 1) is this head's scale: numel[n - 1] == B * 3 * H * W and s[n - 1] is not read, it is `out`.
+ *   out         = conv(x)                       exactly the image of tgsr_conv_to3_fwd
+ *   fine[n - 1] = fmaf(alpha, out, t[n - 1])    from the accumulators, in the same epilogue
+ *   fine[k]     = fmaf(alpha, s[k], t[k])       k < n - 1, in extra workgroups behind the tiles
+ * - the fma of tgsr_axpy_images, bit for bit.  Only the streaming form with 16-byte copies takes it: TGSR_EUNSUPPORTED where
+ * W % 4 != 0, x_bstride % 4 != 0, x / out / a triple's pointer is not 16-byte aligned, numel[k] % 4 != 0, n > 3, the filter takes
+ * more than 16 KB, the shape goes to the matrix-pipe form (K = 5 on large images) or tgsr_conv_to3_set_pipe(0) is in force;
+ * TGSR_EINVAL for a missing pointer, n < 1 or a last triple of another size.  A refused call writes nothing.
+ */
+int tgsr_conv_to3_finish_fwd(const float* x, int64_t x_bstride, int B, int Cin, int H, int W, const float* w, int K, float* out,
+                             int n, float* const* fine, const float* const* t, const float* const* s, const int64_t* numel,
+                             float alpha, void* stream);
+
+/*
  * Word-level attention of the generator (GlobalAttentionGeneral.forward, GlobalAttention.py:87-130) in two
  * launches: the 1x1 projection of the word embeddings (:100-102) and a fused QK^T -> mask -> softmax over words
  * -> PV kernel on MFMA (:107-128).

@@ -1,0 +1,291 @@
+"""The streaming image head (conv_to3_pipe_kernel) on every tile form, and the closing launch of the fp32 inference step built on
+it (tgsr_conv_to3_finish_fwd: G_SR_NET_low's last head + every `+ a * SRb` of NetG_highweight's heads).
+
+1. the streaming kernel == conv_to3_kernel (tgsr_conv_to3_set_pipe(0)) bit for bit on every tile form, and both within the
+   existing tolerance of F.conv2d;
+2. the closing launch == tgsr_conv_to3_fwd followed by tgsr_axpy_images bit for bit, and what it refuses it leaves unwritten;
+3. SRPipeline with trainer.FOLD_FINISH on == off, every tensor, eager and replayed from a captured graph;
+4. (host) G_SR_NET_low's deferral hands back the objects of the plain forward in its order.
+The C entry points run on operands in the guarded arena (tests/arena.py)."""
+import ctypes
+import functools
+
+import pytest
+import torch
+import torch.nn.functional as F
+
+from arena import Arena
+
+gpu = pytest.mark.gpu
+DEV = "cuda"
+OK, EINVAL, EUNSUPPORTED = 0, -1, -2
+ACT_NONE, ACT_TANH_AXPY = 0, 1
+ALPHA = 0.5
+TOL = 2e-5                     # atol = rtol of tests/test_hip_parity.py::test_conv_to3
+
+# (B, Cin, H, W) - the smallest shapes that select each tile form (B * ceil(W / 64) * ceil(H / th) >= 512)
+SHAPES_16 = [(8, 6, 128, 512), (8, 5, 125, 512), (16, 6, 256, 68)]      # odd height / channel count, ragged tiles, W % 64 != 0
+SHAPES_8 = [(4, 6, 128, 512), (4, 5, 123, 512)]
+SHAPES_4 = [(1, 9, 12, 64), (2, 3, 5, 8), (1, 2, 1, 4)]
+
+
+def _L():
+    from tgsr_amd import _lib
+    return _lib.lib()
+
+
+def _stream():
+    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
+@functools.lru_cache(maxsize=None)
+def _case(B, Cin, H, W, K):
+    """(x, w, addend, conv reference on the CPU), computed once per case and left unchanged."""
+    g = torch.Generator().manual_seed(1000 * K + 7 * H + W + Cin)
+    x = torch.randn(B, Cin, H, W, generator=g)
+    w = torch.randn(3, Cin, K, K, generator=g) / (K * Cin ** 0.5)
+    add = torch.randn(B, 3, H, W, generator=g)
+    return x, w, add, F.conv2d(x, w, None, 1, K // 2)
+
+
+def _ptrs(regions):
+    return (ctypes.c_void_p * len(regions))(*[None if r is None else r.address for r in regions])
+
+
+# ------------------------------------------------------------------------------------------------ 1. the streaming kernel
+@gpu
+@pytest.mark.parametrize("act", [ACT_NONE, ACT_TANH_AXPY], ids=["none", "tanh_addend"])
+@pytest.mark.parametrize("K", [3, 5])
+@pytest.mark.parametrize("shape", SHAPES_16 + SHAPES_8 + SHAPES_4, ids=lambda s: "x".join(map(str, s)))
+def test_streaming_head_equals_conv_to3_kernel_bit_for_bit(shape, K, act):
+    from tgsr_amd import ops
+    B, Cin, H, W = shape
+    x, w, add, conv = _case(B, Cin, H, W, K)
+    a = Arena(DEV)
+    xr = a.place_input(x, bstride=Cin * H * W + 8)             # samples apart, NaN in between
+    wr = a.place_input(w)
+    ar = a.place_input(add) if act else None
+    out = a.place_output((B, 3, H, W))
+    got = []
+    was = ops.conv_to3_set_pipe(True)
+    try:
+        for pipe in (True, False):
+            ops.conv_to3_set_pipe(pipe)
+            a.rearm()
+            rc = _L().tgsr_conv_to3_fwd(xr.ptr, Cin * H * W + 8, B, Cin, H, W, wr.ptr, K, act, ar.ptr if act else None, ALPHA,
+                                        out.ptr, _stream())
+            assert rc == OK
+            a.check()
+            got.append(out.read())
+    finally:
+        ops.conv_to3_set_pipe(was)
+    assert torch.equal(got[0], got[1])
+    ref = torch.tanh(conv) + ALPHA * add if act else conv
+    torch.testing.assert_close(got[0], ref, atol=TOL, rtol=TOL)
+
+
+# ------------------------------------------------------------------------------------------------ 2. the closing launch
+def _finish_operands(B, Cin, H, W, K, n, arena, x_bstride=None, skew=None, sizes=None, written=True):
+    """Places x, w, out and n triples (the others at half and quarter size, smallest first); returns the regions and host tensors."""
+    x, w, _, _ = _case(B, Cin, H, W, K)
+    g = torch.Generator().manual_seed(H + W + n)
+    shapes = sizes or [(B, 3, H >> k, W >> k) for k in range(n - 1, -1, -1)]
+    ts = [torch.randn(s, generator=g) for s in shapes]
+    ss = [torch.randn(s, generator=g) for s in shapes[:-1]]
+    skew = skew or {}
+    r = {"x": arena.place_input(x, bstride=x_bstride or Cin * H * W + 8, skew=skew.get("x", 0)), "w": arena.place_input(w),
+         "t": [arena.place_input(t, skew=skew.get("t%d" % k, 0)) for k, t in enumerate(ts)],
+         "s": [arena.place_input(s_, skew=skew.get("s%d" % k, 0)) for k, s_ in enumerate(ss)],
+         "out": arena.place_output((B, 3, H, W), skew=skew.get("out", 0), written=written),
+         "fine": [arena.place_output(s, skew=skew.get("fine%d" % k, 0), written=written) for k, s in enumerate(shapes)]}
+    return r, (x, w, ts, ss)
+
+
+def _finish_call(r, B, Cin, H, W, K, n=None, x_bstride=None, numel=None, null=()):
+    n = len(r["t"]) if n is None else n
+    m = len(r["t"])
+    ne = (ctypes.c_int64 * m)(*(numel or [int(torch.tensor(t.shape).prod()) for t in r["t"]]))
+    fine = None if "fine" in null else _ptrs(r["fine"])
+    t = None if "t" in null else _ptrs(r["t"])
+    s = _ptrs(r["s"] + [None] * (m - len(r["s"])))
+    return _L().tgsr_conv_to3_finish_fwd(r["x"].ptr, x_bstride or Cin * H * W + 8, B, Cin, H, W, r["w"].ptr, K, r["out"].ptr, n,
+                                         fine, t, s, ne, ALPHA, _stream())
+
+
+@gpu
+@pytest.mark.parametrize("n", [1, 2, 3])
+@pytest.mark.parametrize("shape,K", [((8, 6, 128, 512), 3), ((4, 6, 128, 512), 3), ((1, 9, 12, 64), 3), ((1, 9, 12, 64), 5)],
+                         ids=lambda v: "x".join(map(str, v)) if isinstance(v, tuple) else "K%d" % v)
+def test_closing_launch_equals_head_then_axpy_bit_for_bit(shape, K, n):
+    from tgsr_amd import ops
+    B, Cin, H, W = shape
+    a = Arena(DEV)
+    r, (x, w, ts, ss) = _finish_operands(B, Cin, H, W, K, n, a)
+    assert _finish_call(r, B, Cin, H, W, K) == OK
+    a.check()
+    img = ops.conv_to3(x.to(DEV), w.to(DEV))                                    # the two launches it replaces
+    fine = ops.axpy_images([t.to(DEV) for t in ts], [s_.to(DEV) for s_ in ss] + [img], ALPHA)
+    assert torch.equal(r["out"].read(), img.cpu())
+    for k in range(n):
+        assert torch.equal(r["fine"][k].read(), fine[k].cpu()), "fine[%d]" % k
+    torch.testing.assert_close(img.cpu(), _case(B, Cin, H, W, K)[3], atol=TOL, rtol=TOL)
+
+
+S = (1, 9, 12, 64)
+REFUSALS = [
+    # id, shape, K, n placed, operand overrides, call overrides, code
+    ("x_misaligned", S, 3, 2, dict(skew={"x": 1}), {}, EUNSUPPORTED),
+    ("out_misaligned", S, 3, 2, dict(skew={"out": 1}), {}, EUNSUPPORTED),
+    ("t_last_misaligned", S, 3, 2, dict(skew={"t1": 2}), {}, EUNSUPPORTED),
+    ("fine_misaligned", S, 3, 3, dict(skew={"fine0": 1}), {}, EUNSUPPORTED),
+    ("s_misaligned", S, 3, 3, dict(skew={"s1": 3}), {}, EUNSUPPORTED),
+    ("batch_stride_not_x4", (2, 3, 8, 8), 3, 1, dict(x_bstride=3 * 64 + 6), dict(x_bstride=3 * 64 + 6), EUNSUPPORTED),
+    ("numel_not_x4", S, 3, 2, dict(sizes=[(1, 3, 1, 2), (1, 3, 12, 64)]), {}, EUNSUPPORTED),
+    ("four_triples", S, 3, 4, dict(sizes=[(1, 3, 3, 16), (1, 3, 3, 16), (1, 3, 6, 32), (1, 3, 12, 64)]), {}, EUNSUPPORTED),
+    ("width_not_x4", (1, 9, 12, 62), 3, 1, {}, {}, EUNSUPPORTED),
+    ("filter_over_16KB", (1, 160, 4, 8), 3, 1, {}, {}, EUNSUPPORTED),
+    ("matrix_pipe_shape", (8, 16, 64, 512), 5, 1, {}, {}, EUNSUPPORTED),
+    ("pipe_off", S, 3, 2, {}, dict(pipe=False), EUNSUPPORTED),
+    ("kernel_size", (1, 9, 12, 64), 3, 1, {}, dict(K=7), EUNSUPPORTED),
+    ("no_triple", S, 3, 1, {}, dict(n=0), EINVAL),
+    ("last_of_another_size", S, 3, 2, {}, dict(numel=[3 * 6 * 32, 3 * 6 * 32]), EINVAL),
+    ("null_t", S, 3, 2, {}, dict(null=("t",)), EINVAL),
+    ("null_fine", S, 3, 2, {}, dict(null=("fine",)), EINVAL),
+]
+
+
+@gpu
+@pytest.mark.parametrize("row", REFUSALS, ids=[r[0] for r in REFUSALS])
+def test_closing_launch_refuses_and_writes_nothing(row):
+    from tgsr_amd import ops
+    _, (B, Cin, H, W), K, n, place, call, code = row
+    call = dict(call)
+    a = Arena(DEV)
+    r, _ = _finish_operands(B, Cin, H, W, K, n, a, written=False, **place)
+    pipe = call.pop("pipe", True)
+    K = call.pop("K", K)
+    was = ops.conv_to3_set_pipe(pipe)
+    try:
+        assert _finish_call(r, B, Cin, H, W, K, **call) == code
+    finally:
+        ops.conv_to3_set_pipe(was)
+    a.check()                                                                   # every output still holds its prefill
+
+
+# ------------------------------------------------------------------------------------------------ 3. SRPipeline
+@pytest.fixture()
+def cfg_small():
+    from tgsr_amd.miscc.config import cfg, cfg_reset
+    cfg_reset()
+    cfg.GAN.GF_DIM = 32
+    cfg.TEXT.EMBEDDING_DIM = 64
+    cfg.TREE.BRANCH_NUM = 4
+    yield cfg
+    cfg_reset()
+
+
+def _seeded_pipeline():
+    from tgsr_amd.synthetic import random_init_
+    from tgsr_amd.trainer import SRPipeline
+    torch.manual_seed(11)                                                       # the text encoder's own initialisation
+    p = SRPipeline(41, device=DEV, low="lr")
+    for k, m in enumerate((p.netGL, p.netGH)):
+        random_init_(m, seed=5 + k)
+    return p
+
+
+def _flat(out):
+    res = {}
+    for k, v in out.items():
+        for i, t in enumerate(v if isinstance(v, (list, tuple)) else [v]):
+            res["%s[%d]" % (k, i)] = t.detach().clone()
+    return res
+
+
+def _same(a, b):
+    assert a.keys() == b.keys()
+    for k in a:
+        assert torch.equal(a[k], b[k]), k
+
+
+def _batch(seed):
+    from tgsr_amd.synthetic import synthetic_batch
+    cap, lens, LR, LRb = synthetic_batch(2, seed=seed, lr=32)
+    return cap.to(DEV), lens.tolist(), LR.to(DEV), LRb.to(DEV)
+
+
+@gpu
+def test_pipeline_with_the_closing_launch_equals_the_two_launches(cfg_small, monkeypatch):
+    from tgsr_amd import custom_ops as C, trainer
+    assert trainer.SPLIT_HEADS
+    p = _seeded_pipeline()
+    one, other = _batch(3), _batch(8)
+    assert one[1] != other[1]                                                   # other caption lengths
+    calls = {"finish": 0, "axpy": 0}
+    fin, axpy = C.conv_to3_finish, C.axpy_images
+    monkeypatch.setattr(C, "conv_to3_finish", lambda *a: (calls.__setitem__("finish", calls["finish"] + 1), fin(*a))[1])
+    monkeypatch.setattr(C, "axpy_images", lambda *a: (calls.__setitem__("axpy", calls["axpy"] + 1), axpy(*a))[1])
+
+    monkeypatch.setattr(trainer, "FOLD_FINISH", False)
+    off = [_flat(p(*b)) for b in (one, other)]
+    assert calls == {"finish": 0, "axpy": 2}
+    monkeypatch.setattr(trainer, "FOLD_FINISH", True)
+    on = _flat(p(*one))
+    assert calls == {"finish": 1, "axpy": 2}
+    _same(on, off[0])
+    assert tuple(on["fake[2]"].shape) == (2, 3, 256, 256) and tuple(on["fine[2]"].shape) == (2, 3, 256, 256)
+
+    p.capture(*one)
+    assert calls["axpy"] == 2                                                   # the captured step is the folded one
+    _same(_flat(p.replay()), off[0])
+    _same(_flat(p.replay(*other)), off[1])                                      # a batch with other caption lengths
+
+    monkeypatch.setattr(trainer, "SPLIT_HEADS", False)                          # the reference's order: untouched by the switch
+    calls.update(finish=0, axpy=0)
+    plain_on = _flat(p(*one))
+    monkeypatch.setattr(trainer, "FOLD_FINISH", False)
+    _same(plain_on, _flat(p(*one)))
+    _same(plain_on, off[0])
+    assert calls == {"finish": 0, "axpy": 0}
+
+
+# ------------------------------------------------------------------------------------------------ 4. host only
+def test_deferral_returns_the_plain_forward_objects_in_order(monkeypatch):
+    from tgsr_amd import custom_ops as C, model
+    from tgsr_amd.miscc.config import cfg, cfg_reset
+    cfg_reset()
+    cfg.GAN.GF_DIM = 32
+    cfg.TEXT.EMBEDDING_DIM = 256
+    try:
+        gl = model.G_SR_NET_low().eval()
+    finally:
+        cfg_reset()
+    g = torch.Generator().manual_seed(0)
+    hs = [torch.randn(1, 32, 4 << k, 4 << k, generator=g) for k in range(3)]
+    atts = [torch.randn(1, 5, 2 << k, 2 << k, generator=g) for k in range(3)]
+
+    class Stage(torch.nn.Module):
+        def __init__(self, k):
+            super().__init__()
+            self.k = k
+
+        def forward(self, *a, **kw):
+            return hs[self.k], atts[self.k]
+
+    gl.h_net1, gl.h_net2, gl.h_net3 = Stage(0), Stage(1), Stage(2)
+    heads = []
+    monkeypatch.setattr(C, "conv_to3", lambda x, w, *a: (heads.append(x), F.conv2d(x, w, None, 1, 1))[1])
+    mu, logvar = torch.zeros(1, 4), torch.ones(1, 4)
+    args = (torch.zeros(1, 3, 2, 2), None, None, None)
+    with torch.no_grad():
+        fake, att, mu1, lv1 = gl(*args, ca=(None, mu, logvar), proj=[None] * 3)
+        res = gl(*args, ca=(None, mu, logvar), proj=[None] * 3, defer_last_head=True)
+    assert len(res) == 5 and len(fake) == 3 and len(heads) == 5               # three heads, then two
+    fake2, att2, mu2, lv2, (h3, w3) = res
+    assert len(fake2) == 2 and all(torch.equal(a, b) for a, b in zip(fake2, fake))
+    assert len(att2) == 3 and all(a is b for a, b in zip(att2, att)) and all(a is b for a, b in zip(att, atts))
+    assert mu2 is mu1 is mu and lv2 is lv1 is logvar
+    assert h3 is hs[2] and w3 is gl.img_net3.img[0].weight
+    assert torch.equal(F.conv2d(h3, w3, None, 1, 1), fake[2])                   # what the caller's launch has to produce
+    with pytest.raises(ValueError):
+        gl(*args, ca=(None, mu, logvar), proj=[None] * 3, defer_last_head=True, outmiddle=True)

@@ -228,9 +228,24 @@ __global__ __launch_bounds__(16 * TH * KS) void conv_to3_kernel(To3Args a) {
 // form) and a filter of <= 16 KB; everything else stays on the kernel above (TGSR_TO3_PIPE=0: everything).
 // Measured (batch 16, the six stand-alone heads of an inference step, same box): 0.206 -> 0.189 ms per step, 1.87 -> 2.04 TB/s -
 // 8 %, not the 2x the serialised copies suggested: four workgroups per CU already overlapped one another's round trips.
-template <int K, int ACT, int TH, int KS>
-__global__ __launch_bounds__(16 * TH * KS) void conv_to3_pipe_kernel(To3Args a) {
-  constexpr int P = K / 2, CK = 2, TW = 64, NG = 16 * TH, NW = NG / 64, NT = 16 * TH * KS;
+// FIN: the closing launch of the fp32 inference step (tgsr_conv_to3_finish_fwd).  The epilogue also writes
+// fine_last = fmaf(alpha, img, t_last) from the accumulators (t_last is fetched ahead of the channel loop), and the workgroups behind
+// the last tile evaluate fmaf(alpha, s_k, t_k) for the smaller scales - what axpy_images_kernel did in a launch of its own, reading
+// back an image this kernel has just held in registers.
+struct To3Fin {
+  const float* t_last;   // tanh(conv5x5) of this head's scale, [B][3][H][W]
+  float* fine_last;
+  const float* t[2];     // the smaller scales: fine[k] = fmaf(alpha, s[k], t[k]) over n4[k] float4s
+  const float* s[2];
+  float* fine[2];
+  uint32_t n4[2];
+  float alpha;
+  int conv_blocks;       // workgroups [0, conv_blocks) are tiles, the rest take the smaller scales
+};
+
+template <int K, int ACT, int TH, int KS, bool FIN>
+__global__ __launch_bounds__(16 * TH * KS) void conv_to3_pipe_kernel(To3Args a, To3Fin f) {
+  constexpr int P = K / 2, CK = 2, TW = 64, NG = 16 * TH, NW = NG / 64, NT = NG * KS;
   constexpr int TR = TH + K - 1;
   constexpr int PITCH = 72;
   constexpr int STAGE = CK * TR * PITCH;
@@ -239,8 +254,31 @@ __global__ __launch_bounds__(16 * TH * KS) void conv_to3_pipe_kernel(To3Args a) 
   constexpr int WPC = (3 * K * K + 3) & ~3;                        // filter floats per input channel ([co][ky][kx], padded)
   static_assert(NG % 64 == 0, "a channel group is a whole number of waves");
   static_assert((KS - 1) * 12 * NG <= KS * D * BUF, "reduction buffer fits the stage buffers");
+  static_assert(!FIN || ACT == TGSR_ACT_NONE, "the closing launch has no activation");
   __shared__ __attribute__((aligned(16))) float smem_all[KS * D * BUF];
   extern __shared__ __attribute__((aligned(16))) float w_s[];      // [Cin][WPC]
+
+  const int nconv = FIN ? f.conv_blocks : (int)gridDim.x;
+  if (FIN && (int)blockIdx.x >= nconv) {                           // (block-uniform, ahead of every barrier)
+    const uint32_t e = blockIdx.x - nconv, ne = gridDim.x - nconv;
+    const float al = f.alpha;
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+      const float4* __restrict__ t4 = reinterpret_cast<const float4*>(f.t[k]);
+      const float4* __restrict__ s4 = reinterpret_cast<const float4*>(f.s[k]);
+      float4* __restrict__ o4 = reinterpret_cast<float4*>(f.fine[k]);
+      for (uint32_t i = e * NT + threadIdx.x; i < f.n4[k]; i += ne * NT) {
+        const float4 tv = t4[i], sv = s4[i];
+        float4 r;
+        r.x = fmaf(al, sv.x, tv.x);
+        r.y = fmaf(al, sv.y, tv.y);
+        r.z = fmaf(al, sv.z, tv.z);
+        r.w = fmaf(al, sv.w, tv.w);
+        o4[i] = r;
+      }
+    }
+    return;
+  }
 
   const int grp = __builtin_amdgcn_readfirstlane(threadIdx.x / NG);
   const int tid = threadIdx.x - grp * NG, lane = tid & 63;
@@ -248,7 +286,7 @@ __global__ __launch_bounds__(16 * TH * KS) void conv_to3_pipe_kernel(To3Args a) 
   float* smem = smem_all + grp * D * BUF;
   const int lq = (lane >> 2) & 7;                                  // (the lane -> (row, quad) mapping of the kernel above)
   const int txi = (lq >> 1) * 4 + (lane & 3), tyi = 4 * wave + 2 * (lane >> 5) + ((0x96 >> lq) & 1);
-  int t = xcd_remap(blockIdx.x, gridDim.x);
+  int t = xcd_remap(blockIdx.x, nconv);
   const int tx = t % a.tiles_x;
   t /= a.tiles_x;
   const int ty = t % a.tiles_y;
@@ -292,6 +330,15 @@ __global__ __launch_bounds__(16 * TH * KS) void conv_to3_pipe_kernel(To3Args a) 
   for (int co = 0; co < 3; ++co)
 #pragma unroll
     for (int p = 0; p < 4; ++p) acc[co][p] = 0.f;
+
+  const int y = y0 + tyi, xx = x0 + 4 * txi;
+  float* __restrict__ outp = a.out;
+  const float* __restrict__ addp = a.addend;
+  float4 tl[3] = {};                                                  // FIN: this thread's t_last, under way while the channels run
+  if (FIN && grp == 0 && y < a.H && xx < a.W) {
+#pragma unroll
+    for (int co = 0; co < 3; ++co) tl[co] = *reinterpret_cast<const float4*>(f.t_last + ((int64_t)b * 3 + co) * HW + (int64_t)y * a.W + xx);
+  }
 
   const int nst = (a.Cin + CK - 1) / CK, per = (nst + KS - 1) / KS;
   const int s0 = grp * per, s1 = s0 + per < nst ? s0 + per : nst;
@@ -357,20 +404,21 @@ __global__ __launch_bounds__(16 * TH * KS) void conv_to3_pipe_kernel(To3Args a) 
         for (int p = 0; p < 4; ++p) acc[co][p] += red[((g - 1) * 12 + co * 4 + p) * NG + tid];
   }
 
-  const int y = y0 + tyi, xx = x0 + 4 * txi;
-  float* __restrict__ outp = a.out;
-  const float* __restrict__ addp = a.addend;
   if (y < a.H && xx < a.W) {                                       // (W % 4 == 0: a thread's four pixels are inside or outside together)
 #pragma unroll
     for (int co = 0; co < 3; ++co) {
       const int64_t o = ((int64_t)b * 3 + co) * HW + (int64_t)y * a.W + xx;
       float4 ad = make_float4(0.f, 0.f, 0.f, 0.f);
       if (ACT == TGSR_ACT_TANH_AXPY && addp) ad = *reinterpret_cast<const float4*>(addp + o);
+      if (FIN) ad = tl[co];
       const float adv[4] = {ad.x, ad.y, ad.z, ad.w};
-      float r[4];
+      float v[4];
 #pragma unroll
-      for (int p = 0; p < 4; ++p) r[p] = ACT == TGSR_ACT_TANH_AXPY ? fast_tanh(acc[co][p]) + a.alpha * adv[p] : acc[co][p];
-      *reinterpret_cast<float4*>(outp + o) = make_float4(r[0], r[1], r[2], r[3]);
+      for (int p = 0; p < 4; ++p) v[p] = ACT == TGSR_ACT_TANH_AXPY ? fast_tanh(acc[co][p]) + a.alpha * adv[p] : acc[co][p];
+      *reinterpret_cast<float4*>(outp + o) = make_float4(v[0], v[1], v[2], v[3]);
+      if (FIN)     // the fma of axpy_images_kernel, on the image while it is still in registers
+        *reinterpret_cast<float4*>(f.fine_last + o) = make_float4(fmaf(f.alpha, v[0], adv[0]), fmaf(f.alpha, v[1], adv[1]),
+                                                                  fmaf(f.alpha, v[2], adv[2]), fmaf(f.alpha, v[3], adv[3]));
     }
   }
 }
@@ -506,34 +554,55 @@ static int g_to3_pipe = [] {
 }();
 static bool to3_pipe() { return g_to3_pipe != 0; }
 
-template <int K, int ACT, int TH, int KS>
-static int launch_to3_th(To3Args a, hipStream_t s) {
-  a.tiles_x = (a.W + 63) / 64;
-  a.tiles_y = (a.H + TH - 1) / TH;
-  const dim3 grid((unsigned)(a.B * a.tiles_x * a.tiles_y));
+// Which kernel a head takes.  16-row tiles when they still give >= 2 workgroups per CU; smaller images take 8- or 4-row tiles (more
+// workgroups) and split the input channels over 2 / 4 thread groups (more waves per workgroup, fewer stages per wave).
+enum To3Form { TO3_MFMA, TO3_PIPE, TO3_VEC4, TO3_SCALAR };
+
+static int64_t to3_tiles(const To3Args& a, int th) { return (int64_t)a.B * ((a.W + 63) / 64) * ((a.H + th - 1) / th); }
+static int to3_th(const To3Args& a) { return to3_tiles(a, 16) >= 512 ? 16 : to3_tiles(a, 8) >= 512 ? 8 : 4; }
+
+static To3Form to3_form(const To3Args& a, int K) {
+  // large images of the 5x5 heads: the MFMA form (measured at B = 16: 256^2 116 -> 83 us, 128^2 34 -> 25 us); the 3x3
+  // heads fill 9 of 16 MFMA rows and gain nothing over the streaming kernel
+  if (K == 5 && a.Cin % 16 == 0 && a.W % 64 == 0 && a.H % 8 == 0 && to3_tiles(a, 8) >= 512 && a.xbs % 4 == 0 &&
+      (reinterpret_cast<uintptr_t>(a.x) & 15) == 0)
+    return TO3_MFMA;
   const bool vec4 = (a.W % 4 == 0) && (a.xbs % 4 == 0) && ((reinterpret_cast<uintptr_t>(a.x) & 15) == 0) &&
                     ((reinterpret_cast<uintptr_t>(a.out) & 15) == 0) &&
                     (!a.addend || (reinterpret_cast<uintptr_t>(a.addend) & 15) == 0);
-  constexpr int WPC = (3 * K * K + 3) & ~3;
-  const size_t wbytes = (size_t)a.Cin * WPC * sizeof(float);
-  if (vec4 && wbytes <= 16 * 1024 && to3_pipe())
-    hipLaunchKernelGGL((conv_to3_pipe_kernel<K, ACT, TH, KS>), grid, dim3(16 * TH * KS), wbytes, s, a);
-  else if (vec4)
-    hipLaunchKernelGGL((conv_to3_kernel<K, ACT, true, TH, KS>), grid, dim3(16 * TH * KS), 0, s, a);
-  else
-    hipLaunchKernelGGL((conv_to3_kernel<K, ACT, false, TH, KS>), grid, dim3(16 * TH * KS), 0, s, a);
+  const size_t wbytes = (size_t)a.Cin * ((3 * K * K + 3) & ~3) * sizeof(float);
+  if (vec4 && wbytes <= 16 * 1024 && to3_pipe()) return TO3_PIPE;
+  return vec4 ? TO3_VEC4 : TO3_SCALAR;
+}
+
+// The streaming forms of one tile height.  `fin` (the closing launch) is given only where to3_form() said TO3_PIPE.
+template <int K, int ACT, int TH, int KS>
+static int launch_to3_th(To3Args a, To3Form form, const To3Fin* fin, int extra_blocks, hipStream_t s) {
+  a.tiles_x = (a.W + 63) / 64;
+  a.tiles_y = (a.H + TH - 1) / TH;
+  const unsigned tiles = (unsigned)(a.B * a.tiles_x * a.tiles_y);
+  const size_t wbytes = (size_t)a.Cin * ((3 * K * K + 3) & ~3) * sizeof(float);
+  if (form == TO3_PIPE && fin) {
+    if constexpr (ACT == TGSR_ACT_NONE) {
+      To3Fin f = *fin;
+      f.conv_blocks = (int)tiles;
+      hipLaunchKernelGGL((conv_to3_pipe_kernel<K, ACT, TH, KS, true>), dim3(tiles + (unsigned)extra_blocks), dim3(16 * TH * KS),
+                         wbytes, s, a, f);
+    }
+  } else if (form == TO3_PIPE) {
+    hipLaunchKernelGGL((conv_to3_pipe_kernel<K, ACT, TH, KS, false>), dim3(tiles), dim3(16 * TH * KS), wbytes, s, a, To3Fin{});
+  } else if (form == TO3_VEC4) {
+    hipLaunchKernelGGL((conv_to3_kernel<K, ACT, true, TH, KS>), dim3(tiles), dim3(16 * TH * KS), 0, s, a);
+  } else {
+    hipLaunchKernelGGL((conv_to3_kernel<K, ACT, false, TH, KS>), dim3(tiles), dim3(16 * TH * KS), 0, s, a);
+  }
   return note_launch(hipGetLastError(), "conv_to3_kernel");
 }
 
 template <int K, int ACT>
-static int launch_to3(To3Args a, hipStream_t s) {
-  // 16-row tiles when they still give >= 2 workgroups per CU; smaller images take 8- or 4-row tiles (more workgroups)
-  // and split the input channels over 2 / 4 thread groups (more waves per workgroup, fewer stages per wave)
-  auto tiles = [&](int th) { return (int64_t)a.B * ((a.W + 63) / 64) * ((a.H + th - 1) / th); };
-  // large images of the 5x5 heads: the MFMA form (measured at B = 16: 256^2 116 -> 83 us, 128^2 34 -> 25 us); the 3x3
-  // heads fill 9 of 16 MFMA rows and gain nothing over the streaming kernel
-  if (K == 5 && a.Cin % 16 == 0 && a.W % 64 == 0 && a.H % 8 == 0 && tiles(8) >= 512 && a.xbs % 4 == 0 &&
-      (reinterpret_cast<uintptr_t>(a.x) & 15) == 0) {
+static int launch_to3(To3Args a, const To3Fin* fin, int extra_blocks, hipStream_t s) {
+  const To3Form form = to3_form(a, K);
+  if (form == TO3_MFMA) {
     a.tiles_x = a.W / 64;
     // 8-channel chunks (31 KB of LDS, 4 workgroups per CU): 83 us on the 256^2 head against 90 us with 16-channel chunks
     // (16-row tiles - 1.25x halo rows instead of 1.5x - measured 85 us: the re-read is not what bounds it)
@@ -541,9 +610,11 @@ static int launch_to3(To3Args a, hipStream_t s) {
     hipLaunchKernelGGL((conv_to3_mfma_kernel<K, ACT, 8, 8>), dim3((unsigned)(a.B * a.tiles_x * a.tiles_y)), dim3(256), 0, s, a);
     return note_launch(hipGetLastError(), "conv_to3_mfma_kernel");
   }
-  if (tiles(16) >= 512) return launch_to3_th<K, ACT, 16, 1>(a, s);
-  if (tiles(8) >= 512) return launch_to3_th<K, ACT, 8, 2>(a, s);
-  return launch_to3_th<K, ACT, 4, 4>(a, s);
+  switch (to3_th(a)) {
+    case 16: return launch_to3_th<K, ACT, 16, 1>(a, form, fin, extra_blocks, s);
+    case 8: return launch_to3_th<K, ACT, 8, 2>(a, form, fin, extra_blocks, s);
+    default: return launch_to3_th<K, ACT, 4, 4>(a, form, fin, extra_blocks, s);
+  }
 }
 
 }  // namespace tgsr
@@ -556,17 +627,54 @@ extern "C" int tgsr_conv_to3_set_pipe(int on) {
   return was;
 }
 
-extern "C" int tgsr_conv_to3_fwd(const float* x, int64_t x_bstride, int B, int Cin, int H, int W, const float* w,
-                                 int K, int act, const float* addend, float alpha, float* out, void* stream) {
+static int to3_args(To3Args& a, const float* x, int64_t x_bstride, int B, int Cin, int H, int W, const float* w, int K, float* out) {
   if (!x || !w || !out || B < 1 || Cin < 1 || H < 1 || W < 1) return TGSR_EINVAL;
   if (K != 3 && K != 5) return TGSR_EUNSUPPORTED;
+  if ((int64_t)H * W >= (1 << 28) || (int64_t)Cin * H * W >= (1ll << 32)) return TGSR_EUNSUPPORTED;
+  a.x = x; a.xbs = x_bstride; a.B = B; a.Cin = Cin; a.H = H; a.W = W; a.w = w;
+  a.addend = nullptr; a.alpha = 0.f; a.out = out; a.tiles_x = a.tiles_y = 0;
+  return TGSR_OK;
+}
+
+extern "C" int tgsr_conv_to3_fwd(const float* x, int64_t x_bstride, int B, int Cin, int H, int W, const float* w,
+                                 int K, int act, const float* addend, float alpha, float* out, void* stream) {
+  To3Args a;
+  if (const int rc = to3_args(a, x, x_bstride, B, Cin, H, W, w, K, out)) return rc;
   if (act != TGSR_ACT_NONE && act != TGSR_ACT_TANH_AXPY) return TGSR_EINVAL;
   if (act == TGSR_ACT_NONE && addend) return TGSR_EINVAL;
-  if ((int64_t)H * W >= (1 << 28) || (int64_t)Cin * H * W >= (1ll << 32)) return TGSR_EUNSUPPORTED;
-  To3Args a;
-  a.x = x; a.xbs = x_bstride; a.B = B; a.Cin = Cin; a.H = H; a.W = W; a.w = w;
-  a.addend = addend; a.alpha = alpha; a.out = out; a.tiles_x = a.tiles_y = 0;
+  a.addend = addend; a.alpha = alpha;
   hipStream_t s = as_stream(stream);
-  if (K == 3) return act == TGSR_ACT_NONE ? launch_to3<3, TGSR_ACT_NONE>(a, s) : launch_to3<3, TGSR_ACT_TANH_AXPY>(a, s);
-  return act == TGSR_ACT_NONE ? launch_to3<5, TGSR_ACT_NONE>(a, s) : launch_to3<5, TGSR_ACT_TANH_AXPY>(a, s);
+  if (K == 3) return act == TGSR_ACT_NONE ? launch_to3<3, TGSR_ACT_NONE>(a, nullptr, 0, s) : launch_to3<3, TGSR_ACT_TANH_AXPY>(a, nullptr, 0, s);
+  return act == TGSR_ACT_NONE ? launch_to3<5, TGSR_ACT_NONE>(a, nullptr, 0, s) : launch_to3<5, TGSR_ACT_TANH_AXPY>(a, nullptr, 0, s);
+}
+
+extern "C" int tgsr_conv_to3_finish_fwd(const float* x, int64_t x_bstride, int B, int Cin, int H, int W, const float* w, int K,
+                                        float* out, int n, float* const* fine, const float* const* t, const float* const* s,
+                                        const int64_t* numel, float alpha, void* stream) {
+  To3Args a;
+  if (const int rc = to3_args(a, x, x_bstride, B, Cin, H, W, w, K, out)) return rc;
+  if (n < 1 || !fine || !t || !s || !numel) return TGSR_EINVAL;
+  if (n > 3) return TGSR_EUNSUPPORTED;
+  To3Fin f{};
+  uint32_t most = 0;
+  for (int i = 0; i < n; ++i) {
+    const bool last = i == n - 1;                                  // the last triple is this head's scale: s = `out`, s[i] is not read
+    if (!fine[i] || !t[i] || (!last && !s[i]) || numel[i] < 1) return TGSR_EINVAL;
+    if (last && numel[i] != (int64_t)B * 3 * H * W) return TGSR_EINVAL;
+    if ((numel[i] & 3) || numel[i] > 0x7fffffff ||
+        ((reinterpret_cast<uintptr_t>(fine[i]) | reinterpret_cast<uintptr_t>(t[i]) | (last ? 0 : reinterpret_cast<uintptr_t>(s[i]))) & 15))
+      return TGSR_EUNSUPPORTED;
+    if (last) {
+      f.t_last = t[i]; f.fine_last = fine[i];
+    } else {
+      f.t[i] = t[i]; f.s[i] = s[i]; f.fine[i] = fine[i]; f.n4[i] = (uint32_t)(numel[i] >> 2);
+      most = f.n4[i] > most ? f.n4[i] : most;
+    }
+  }
+  f.alpha = alpha;
+  if (to3_form(a, K) != TO3_PIPE) return TGSR_EUNSUPPORTED;        // (W % 4, alignment, a filter over 16 KB, the MFMA shapes, pipe off)
+  // the smaller scales: one float4 per thread and trip, up to 256 workgroups behind the tiles (a workgroup has 256 threads)
+  const int extra = (int)((most + 255) / 256 < 256 ? (most + 255) / 256 : 256);
+  hipStream_t st = as_stream(stream);
+  return K == 3 ? launch_to3<3, TGSR_ACT_NONE>(a, &f, extra, st) : launch_to3<5, TGSR_ACT_NONE>(a, &f, extra, st);
 }

@@ -467,6 +467,11 @@ text_tail_lp = _define("text_tail_lp(Tensor words, Tensor[] w_ctxs, Tensor sent_
                         words.new_empty(len(ws) * words.shape[0] * 4096 + 4 * words.shape[0], dtype=torch.uint8)))
 axpy_images = _define("axpy_images(Tensor[] ts, Tensor[] ss, float alpha) -> Tensor[]",
                       lambda ts, ss, alpha: ops.axpy_images(list(ts), list(ss), alpha), lambda ts, ss, alpha: [torch.empty_like(t) for t in ts])
+# the last low-frequency head and every `+ a * SRb` in one launch (inference; ops.conv_to3_finish)
+conv_to3_finish = _define("conv_to3_finish(Tensor x, Tensor w, Tensor[] ts, Tensor[] ss, float alpha) -> (Tensor, Tensor[])",
+                          lambda x, w, ts, ss, alpha: ops.conv_to3_finish(x, w, list(ts), list(ss), alpha),
+                          lambda x, w, ts, ss, alpha: (x.new_empty(x.shape[0], 3, x.shape[2], x.shape[3]),
+                                                       [torch.empty_like(t) for t in ts]))
 # ------------------------------------------------------------------------------------------------ CNN_ENCODER's frozen trunk
 gconv_pack = _define("gconv_pack(Tensor w, Tensor? scale, bool dgrad) -> Tensor", lambda w, sc, dg: ops.gconv_pack(w, sc, dg),
                      lambda w, sc, dg: w.new_empty((w.shape[1], w.shape[0] * w.shape[2] * w.shape[3]) if dg else

@@ -54,10 +54,13 @@ class G_SR_NET_low(nn.Module):
         """The distinct GlobalAttentionGeneral modules in stage order: `proj` of forward() holds their word projections."""
         return [self.h_net1.att, self.h_net2.att, self.h_net3.att]
 
-    def forward(self, LR, sent_emb, word_embs, mask, outmiddle=False, ca=None, proj=None):
+    def forward(self, LR, sent_emb, word_embs, mask, outmiddle=False, ca=None, proj=None, defer_last_head=False):
         """ca: optional precomputed `self.ca_net(sent_emb)` (nothing downstream reads c_code, model.py:51-52, only mu /
         logvar are returned); proj: optional precomputed conv_context projections of `attention_modules()` (SRPipeline
-        computes both, and the mask, in one launch: ops.text_tail)."""
+        computes both, and the mask, in one launch: ops.text_tail).
+        defer_last_head=True (inference, SRPipeline): img_net3 is not run - fake_imgs holds the first two images and a fifth
+        result `(h_code3, img_net3's weight)` goes back, for the caller to finish in the launch that also closes
+        NetG_highweight's heads (NetG_highweight.finish_heads_with_last); the caller appends the image to fake_imgs."""
         fake_imgs, att_maps = [], []
         c_code, mu, logvar = self.ca_net(sent_emb) if ca is None else ca   # c_code unused downstream (model.py:51-52)
         srcs = [None, None, None]
@@ -73,8 +76,12 @@ class G_SR_NET_low(nn.Module):
         fake_imgs.append(self.img_net2(h_code2))
         att_maps.append(att1)
         h_code3, att2 = self.h_net3(h_code2, None, word_embs, mask, src=srcs[2])
-        fake_imgs.append(self.img_net3(h_code3))
         att_maps.append(att2)
+        if defer_last_head:
+            if outmiddle:
+                raise ValueError("G_SR_NET_low: outmiddle returns every image, defer_last_head leaves the last one out")
+            return fake_imgs, att_maps, mu, logvar, (h_code3, self.img_net3.img[0].weight)
+        fake_imgs.append(self.img_net3(h_code3))
         if outmiddle:
             return fake_imgs, att_maps, mu, logvar, [h_code1, h_code2, h_code3]
         return fake_imgs, att_maps, mu, logvar
@@ -165,6 +172,18 @@ class NetG_highweight(nn.Module):
         if self.weightmap:
             return [C.axpy_map(t, s.contiguous(), a.detach()) for t, s, a in zip(ts, SRb, self.maps())]
         return list(C.axpy_images(list(ts), [s.contiguous() for s in SRb[:len(ts)]], self._a))
+
+    def finish_heads_with_last(self, ts, SRb, last):
+        """finish_heads when G_SR_NET_low handed its last head back (`last` = (h_code3, weight), SRb = the images it did
+        compute): that head and the `+ a * SRb_k` of every scale are one launch (tgsr::conv_to3_finish) - the last image is
+        added while it is still in the head's registers.  Appends the image to SRb and returns the fine images; the same
+        bits as img_net3 followed by finish_heads.  Scalar `a` only (weightmap=False)."""
+        if self.weightmap:
+            raise ValueError("NetG_highweight(weightmap=True) has no folded closing launch; use finish_heads")
+        h_code, w = last
+        img, fine = C.conv_to3_finish(h_code, w.detach(), list(ts), [s.contiguous() for s in SRb], self._a)
+        SRb.append(img)
+        return list(fine)
 
     def forward(self, LR, SRb, LRb):
         ims = self.heads(self.trunk(LR, LRb), SRb[:3])

@@ -541,6 +541,46 @@ def conv_to3(x: torch.Tensor, w: torch.Tensor, tanh_axpy: bool = False, addend: 
     return out
 
 
+def conv_to3_finish(x: torch.Tensor, w: torch.Tensor, ts, ss, alpha: float):
+    """(img, fine): the closing launch of the fp32 inference step (tgsr_conv_to3_finish_fwd).  img = conv_to3(x, w), the last
+    low-frequency head; fine[k] = ts[k] + alpha * ss[k] for the smaller scales (len(ss) == len(ts) - 1) and
+    fine[-1] = ts[-1] + alpha * img - what axpy_images(ts, ss + [img], alpha) returns, bit for bit, without its launch and
+    without reading img back.  Only shapes of the streaming head with 16-byte copies (TgsrError otherwise)."""
+    import ctypes
+    ts, ss = list(ts), list(ss)
+    n = len(ts)
+    if n < 1 or n > 3 or len(ss) != n - 1:
+        raise TgsrError("conv_to3_finish: %d / %d images (1..3 scales, one low-frequency image fewer)" % (n, len(ss)))
+    _need_hip(x, w, *ts, *ss)
+    x, xbs = _nchw_bstride(_f32(x, "x"), "x")
+    w = _f32(w.detach(), "w").contiguous()
+    B, Cin, H, W = x.shape
+    if w.shape[0] != 3 or w.shape[1] != Cin or w.shape[2] != w.shape[3]:
+        raise TgsrError("conv_to3_finish: weight shape %s" % (tuple(w.shape),))
+    ts = [_f32(t, "t").contiguous() for t in ts]
+    ss = [_f32(s_, "s").contiguous() for s_ in ss]
+    if tuple(ts[-1].shape) != (B, 3, H, W):
+        raise TgsrError("conv_to3_finish: last scale %s against a %s head" % (tuple(ts[-1].shape), (B, 3, H, W)))
+    for t, s_ in zip(ts, ss):
+        if t.shape != s_.shape:
+            raise TgsrError("conv_to3_finish: %s + alpha * %s" % (tuple(t.shape), tuple(s_.shape)))
+    img = torch.empty(B, 3, H, W, dtype=torch.float32, device=x.device)
+    fine = [torch.empty_like(t) for t in ts]
+    tp = (ctypes.c_void_p * n)(*[t.data_ptr() for t in ts])
+    sp = (ctypes.c_void_p * n)(*([s_.data_ptr() for s_ in ss] + [None]))
+    fp = (ctypes.c_void_p * n)(*[o.data_ptr() for o in fine])
+    ne = (ctypes.c_int64 * n)(*[t.numel() for t in ts])
+    e0 = _ev() if profile is not None else None
+    rc = _lib.lib().tgsr_conv_to3_finish_fwd(_p(x), xbs, B, Cin, H, W, _p(w), int(w.shape[2]), _p(img), n, fp, tp, sp, ne,
+                                             float(alpha), _stream())
+    check(rc, "tgsr_conv_to3_finish_fwd")
+    if profile is not None:
+        K = int(w.shape[2])
+        nbytes = 4 * (B * Cin * H * W + B * 3 * H * W) + 4 * sum(3 * t.numel() for t in ts) - 4 * ts[-1].numel()
+        profile.append(("conv_to3_kernel", 2.0 * B * H * W * 3 * Cin * K * K, nbytes, e0, _ev()))
+    return img, fine
+
+
 # ----------------------------------------------------------------------------------------- attention
 _MASK_CACHE = [None, None, None]   # (tensor id/version key, source (kept alive), uint8 copy)
 
@@ -958,6 +998,14 @@ def linear(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None
 def conv_to3_set_pipe(on: bool) -> bool:
     """The image heads' streaming kernel with its copies two stages ahead (default) or the plain double buffer; returns the previous setting."""
     return bool(_lib.lib().tgsr_conv_to3_set_pipe(1 if on else 0))
+
+
+def conv_to3_pipe() -> bool:
+    """The current setting of conv_to3_set_pipe (the library has only the exchange: set it and put it back)."""
+    L = _lib.lib()
+    was = L.tgsr_conv_to3_set_pipe(1)
+    L.tgsr_conv_to3_set_pipe(was)
+    return bool(was)
 
 
 def bn_set_fuse_small(on: bool) -> bool:

@@ -45,6 +45,9 @@ GH_AFTER_TEXT = int(os.environ.get("TGSR_GH_AFTER_TEXT", "-1"))     # -1: by con
 # fp32 path: NetG_highweight's 5x5 + tanh convolutions on the side stream, only `+ a * SRb` behind G_SR_NET_low (0: the six
 # stand-alone heads in the reference's order)
 SPLIT_HEADS = os.environ.get("TGSR_SPLIT_HEADS", "1") != "0"
+# ... and G_SR_NET_low's last head takes that addition along (x8, scalar `a`): one closing launch behind the last upBlock instead
+# of the 256^2 head followed by the axpy over the three image pairs (0: the two launches)
+FOLD_FINISH = os.environ.get("TGSR_FOLD_FINISH", "1") != "0"
 
 
 def crop_words(out, num_words):
@@ -314,9 +317,15 @@ class SRPipeline:
             # G_SR_NET_low.  The convolutions (134 us at batch 16, 92 of them at 256^2) join the trunk on the side stream;
             # what is left behind G_SR_NET_low's last head on the step's critical path is one axpy launch over the three
             # images (~6 us) instead of the 256^2 head.
+            # FOLD_FINISH: G_SR_NET_low hands its last head back (`pend`), the side stream is joined in front of it, and the head
+            # and the additions are one launch - the axpy re-read the six images the heads had just written.
+            from . import model as _m8
+            fold = (FOLD_FINISH and LR.is_cuda and isinstance(self.netGL, _m8.G_SR_NET_low) and not self.netGL.training
+                    and not self.netGH.weightmap and not torch.is_grad_enabled() and LR.shape[3] % 4 == 0 and ops.conv_to3_pipe())
             trunk = lambda: self.netGH.tanh_heads(self.netGH.trunk(LR, LRb))                                 # noqa: E731
-            low = lambda sent, words, mask, ca, proj: self.netGL(LR, sent, words, mask, ca=ca, proj=proj)    # noqa: E731
-            heads = self.netGH.finish_heads
+            low = lambda sent, words, mask, ca, proj: self.netGL(LR, sent, words, mask, ca=ca, proj=proj,    # noqa: E731
+                                                                 **({"defer_last_head": True} if fold else {}))
+            heads = self.netGH.finish_heads_with_last if fold else self.netGH.finish_heads
         else:
             trunk = lambda: self.netGH.trunk(LR, LRb)                                                        # noqa: E731
             low = lambda sent, words, mask, ca, proj: self.netGL(LR, sent, words, mask, ca=ca, proj=proj)    # noqa: E731
