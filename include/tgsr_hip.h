@@ -76,18 +76,29 @@ int tgsr_bn_fold(const float* weight, const float* bias, const float* running_me
  * residual NULL or [B][Cout_out][Ho][Wo] (batch stride res_bstride) added after the affine; only with
  *          TGSR_EPI_AFFINE
  * out      [B][Cout_out][Ho][Wo], Ho = H*(upsample?2:1); Cout_out = Cout/2 with GLU else Cout
- * Supported: Cout % 32 == 0 (Cout % 64 == 0 with GLU); any B, Cin, H, W >= 1.
+ * Supported: Cout % 32 == 0 (Cout % 64 == 0 with GLU); any B, Cin, H, W >= 1 with H W < 2^28 and Cin H W < 2^32 (TGSR_EUNSUPPORTED
+ * beyond, as in every convolution below; the up-sample-aware Winograd forms stop at H W < 2^26).  No alignment is asked of x, out or
+ * residual and any batch stride will do; wpack is read 16 bytes at a time.  TGSR_EINVAL: a NULL x / wpack / out, a size < 1, scale
+ * without shift (or the reverse), an unknown epilogue, GLU with a residual.
  */
 int tgsr_conv3x3_fwd(const float* x, int64_t x_bstride, int B, int Cin, int H, int W, const float* wpack, int Cout,
                      const float* scale, const float* shift, const float* residual, int64_t res_bstride, float* out,
                      int64_t out_bstride, int epilogue, int upsample, void* stream);
+/*
+ * The tile tgsr_conv3x3_fwd takes at this shape: host arithmetic only (no launch, no device access), the very function the
+ * launcher calls.  The kernel instance is conv3x3_mfma_kernel<*nob, GLU, upsample != 0, *rows_per_wave, 4>: a workgroup = 4 waves
+ * x *rows_per_wave (4, 2 or 1) output rows x 32 columns x *nob (2 or 1) blocks of 32 (GLU: 64) filters; grid.y = *groups.
+ * Returns what tgsr_conv3x3_fwd returns for these sizes and selectors (TGSR_EINVAL: a size < 1 or an unknown epilogue;
+ * TGSR_EUNSUPPORTED: Cout % 32 (GLU: % 64) != 0 or H W >= 2^28); the outputs (any may be NULL) are written only with TGSR_OK.
+ */
+int tgsr_conv3x3_fwd_plan(int B, int H, int W, int Cout, int epilogue, int upsample, int* nob, int* rows_per_wave, int* groups);
 
 /*
  * upBlock (util.py:74-80) by sub-pixel decomposition: Upsample(x2, nearest) -> conv3x3 -> affine (BN eval) -> GLU
  * computed as four 2x2 convolutions on the PRE-upsample tensor with pre-summed taps: 4*Cin MACs per output instead
  * of 9*Cin, same result up to the rounding of the weight sums (tgsr_conv3x3_fwd(upsample=1) is the 9-tap form, kept
  * for the training path).  wpack from tgsr_pack_upconv_weight (tgsr_packed_upconv_weight_elems floats).
- * x [B][Cin][H][W] (batch stride), out [B][Cout/2][2H][2W] (batch stride, 8-byte aligned); Cout % 64 == 0.
+ * x [B][Cin][H][W] (batch stride), out [B][Cout/2][2H][2W] (8-byte aligned with an even batch stride); Cout % 64 == 0.
  */
 int64_t tgsr_packed_upconv_weight_elems(int Cout, int Cin);
 int tgsr_pack_upconv_weight(const float* w, float* wpack, int Cout, int Cin, void* stream);
@@ -188,10 +199,31 @@ int tgsr_conv_to3_set_pipe(int on);
  * Replaces GET_IMAGE_G_noAct.img (util.py:913-915; K=3, TGSR_ACT_NONE) and
  * conv_output = conv5x5 + Tanh followed by `one*. + a*SRb` (model.py:224, 280/288/297; K=5, TGSR_ACT_TANH_AXPY).
  * x [B][Cin][H][W] (batch stride x_bstride), w [3][Cin][K][K] (torch layout), addend NULL or [B][3][H][W] dense,
- * out [B][3][H][W] dense.
+ * out [B][3][H][W] dense.  No alignment is required (tgsr_conv_to3_plan names the kernel the operands get).  TGSR_EUNSUPPORTED: K
+ * other than 3 or 5; TGSR_EINVAL: a NULL x / w / out, a size < 1, an `act` other than the two above, an addend with TGSR_ACT_NONE.
  */
 int tgsr_conv_to3_fwd(const float* x, int64_t x_bstride, int B, int Cin, int H, int W, const float* w, int K,
                       int act, const float* addend, float alpha, float* out, void* stream);
+/*
+ * The kernel tgsr_conv_to3_fwd takes for these operands: host arithmetic only (no launch, no device access; the pointers are
+ * inspected for alignment, never dereferenced), the very function the launchers call.  *form:
+ *   TGSR_TO3_FORM_MFMA    conv_to3_mfma_kernel: K = 5, Cin % 16 == 0, W % 64 == 0, H % 8 == 0, >= 512 tiles of 8 x 64, x 16-byte
+ *                         aligned with x_bstride % 4 == 0
+ *   TGSR_TO3_FORM_PIPE    conv_to3_pipe_kernel: the 16-byte copy form below with the filter (<= 16 KB) in LDS, unless
+ *                         tgsr_conv_to3_set_pipe(0) is in force (the plan follows that setting)
+ *   TGSR_TO3_FORM_VEC4    conv_to3_kernel, 16-byte copies: W % 4 == 0, x_bstride % 4 == 0, x / out / addend 16-byte aligned
+ *   TGSR_TO3_FORM_SCALAR  conv_to3_kernel, 4-byte copies and stores: everything else
+ * *tile_rows = output rows per workgroup: 16 while B ceil(W / 64) ceil(H / 16) >= 512, else 8 while that count at 8 rows is >= 512,
+ * else 4 (the input channels split over 1 / 2 / 4 thread groups); 8 for the MFMA form.  Returns what tgsr_conv_to3_fwd returns
+ * for these arguments with a filter, a known `act` and an addend `act` permits; form / tile_rows (either may be NULL) are
+ * written only with TGSR_OK.
+ */
+#define TGSR_TO3_FORM_MFMA 0
+#define TGSR_TO3_FORM_PIPE 1
+#define TGSR_TO3_FORM_VEC4 2
+#define TGSR_TO3_FORM_SCALAR 3
+int tgsr_conv_to3_plan(const float* x, int64_t x_bstride, int B, int Cin, int H, int W, int K, const float* addend,
+                       const float* out, int* form, int* tile_rows);
 
 /*
  * The closing launch of the fp32 inference step: tgsr_conv_to3_fwd(act = TGSR_ACT_NONE) of the LAST low-frequency head and the

@@ -20,10 +20,12 @@ gpu = pytest.mark.gpu
 DEV = "cuda"
 OK, EINVAL, EUNSUPPORTED = 0, -1, -2
 ACT_NONE, ACT_TANH_AXPY = 0, 1
+FORM_PIPE, FORM_VEC4 = 1, 2     # TGSR_TO3_FORM_*
 ALPHA = 0.5
 TOL = 2e-5                     # atol = rtol of tests/test_hip_parity.py::test_conv_to3
 
-# (B, Cin, H, W) - the smallest shapes that select each tile form (B * ceil(W / 64) * ceil(H / th) >= 512)
+# (B, Cin, H, W) - the smallest shapes that select each tile form (B * ceil(W / 64) * ceil(H / th) >= 512; asserted from
+# tgsr_conv_to3_plan in the test)
 SHAPES_16 = [(8, 6, 128, 512), (8, 5, 125, 512), (16, 6, 256, 68)]      # odd height / channel count, ragged tiles, W % 64 != 0
 SHAPES_8 = [(4, 6, 128, 512), (4, 5, 123, 512)]
 SHAPES_4 = [(1, 9, 12, 64), (2, 3, 5, 8), (1, 2, 1, 4)]
@@ -72,6 +74,11 @@ def test_streaming_head_equals_conv_to3_kernel_bit_for_bit(shape, K, act):
         for pipe in (True, False):
             ops.conv_to3_set_pipe(pipe)
             a.rearm()
+            form, th = ctypes.c_int(), ctypes.c_int()              # the launcher's own plan: the form and tile height this call takes
+            assert _L().tgsr_conv_to3_plan(xr.ptr, Cin * H * W + 8, B, Cin, H, W, K, ar.ptr if act else None, out.ptr,
+                                           ctypes.byref(form), ctypes.byref(th)) == OK
+            assert form.value == (FORM_PIPE if pipe else FORM_VEC4)
+            assert th.value == (16 if shape in SHAPES_16 else 8 if shape in SHAPES_8 else 4)
             rc = _L().tgsr_conv_to3_fwd(xr.ptr, Cin * H * W + 8, B, Cin, H, W, wr.ptr, K, act, ar.ptr if act else None, ALPHA,
                                         out.ptr, _stream())
             assert rc == OK

@@ -15,6 +15,7 @@ ABI_VERSION = 2
 OK, EINVAL, EUNSUPPORTED, ELAUNCH = 0, -1, -2, -3
 EPI_AFFINE, EPI_AFFINE_GLU = 0, 1
 ACT_NONE, ACT_TANH_AXPY, ACT_IDENT_AXPY = 0, 1, 2
+TO3_FORM_MFMA, TO3_FORM_PIPE, TO3_FORM_VEC4, TO3_FORM_SCALAR = 0, 1, 2, 3
 DT_BF16, DT_F16 = 1, 2
 
 _vp, _i, _i64, _f, _d = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_float, ctypes.c_double
@@ -28,6 +29,7 @@ SIGNATURES = {
     "tgsr_pack_conv_weight_dgrad": (_i, [_vp, _vp, _i, _i, _i, _vp]),
     "tgsr_bn_fold": (_i, [_vp, _vp, _vp, _vp, _f, _vp, _vp, _i, _vp]),
     "tgsr_conv3x3_fwd": (_i, [_vp, _i64, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _i64, _vp, _i64, _i, _i, _vp]),
+    "tgsr_conv3x3_fwd_plan": (_i, [_i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     "tgsr_packed_upconv_weight_elems": (_i64, [_i, _i]),
     "tgsr_pack_upconv_weight": (_i, [_vp, _vp, _i, _i, _vp]),
     "tgsr_upconv3x3_glu_fwd": (_i, [_vp, _i64, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _i64, _vp]),
@@ -52,6 +54,7 @@ SIGNATURES = {
     "tgsr_wino4_wide_conv3x3_fwd": (_i, [_vp, _i64, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _i64, _vp, _i64, _i, _vp]),
     "tgsr_wino4_conv3x3_fwd": (_i, [_vp, _i64, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _i64, _vp, _i64, _i, _vp]),
     "tgsr_conv_to3_fwd": (_i, [_vp, _i64, _i, _i, _i, _i, _vp, _i, _i, _vp, _f, _vp, _vp]),
+    "tgsr_conv_to3_plan": (_i, [_vp, _i64, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "tgsr_word_attention_fwd": (_i, [_vp, _i64, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _i64, _vp, _vp]),
     "tgsr_word_project_fwd": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
     "tgsr_bilstm_fwd": (_i, [_vp, _i, _vp, _i, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp]),

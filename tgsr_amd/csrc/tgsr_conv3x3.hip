@@ -334,28 +334,21 @@ static int dispatch_up_r(const ConvArgs& a, int groups, bool up, int rows, hipSt
 
 using namespace tgsr;
 
-extern "C" int tgsr_conv3x3_fwd(const float* x, int64_t x_bstride, int B, int Cin, int H, int W, const float* wpack,
-                                int Cout, const float* scale, const float* shift, const float* residual,
-                                int64_t res_bstride, float* out, int64_t out_bstride, int epilogue, int upsample,
-                                void* stream) {
-  if (!x || !wpack || !out || B < 1 || Cin < 1 || H < 1 || W < 1 || Cout < 1) return TGSR_EINVAL;
-  if ((scale == nullptr) != (shift == nullptr)) return TGSR_EINVAL;
+// Tile choice of tgsr_conv3x3_fwd (host arithmetic only; also exported as tgsr_conv3x3_fwd_plan).  Candidates from most operand
+// reuse (2 output blocks per workgroup, 8 accumulators per wave) to least (1 block, 4 rows); take the first that gives >= 2
+// workgroups per CU, else the first with >= 1 per CU, else the smallest tile: at B = 16 an idle CU costs more than the lost
+// reuse.  (2-wave workgroups of 2 rows were measured: same MFMA chain per wave, no gain - the WV parameter stays for a K-split.)
+// As coded, a first pass that finds nothing ahead of the LAST candidate (1 block, 4 rows) leaves the choice to the second pass: a
+// taller tile with >= 256 workgroups then wins over the 4-row tile with >= 512 (B = 1, 96 filters, 17 x 1345: 16 rows, 258
+// workgroups).  The shipped shapes were tuned with it; tests/test_infer_abi_host.py restates it.
+// nob = output blocks per workgroup (the kernel's NOB), rows = output rows per workgroup (4 waves x R), groups = grid.y.
+static int conv3x3_fwd_plan(int B, int H, int W, int Cout, int epilogue, int upsample, int& nob, int& rows, int& groups) {
+  if (B < 1 || H < 1 || W < 1 || Cout < 1) return TGSR_EINVAL;
   const bool glu = epilogue == TGSR_EPI_AFFINE_GLU;
   if (!glu && epilogue != TGSR_EPI_AFFINE) return TGSR_EINVAL;
-  if (glu && residual) return TGSR_EINVAL;
   if (Cout % (glu ? 64 : 32) != 0) return TGSR_EUNSUPPORTED;
-  if ((int64_t)H * W >= (1 << 28) || (int64_t)Cin * H * W >= (1ll << 32)) return TGSR_EUNSUPPORTED;
-  ConvArgs a;
-  a.x = x; a.xbs = x_bstride; a.B = B; a.Cin = Cin; a.H = H; a.W = W;
-  a.wpack = wpack; a.Cout = Cout; a.scale = scale; a.shift = shift;
-  a.res = residual; a.rbs = res_bstride; a.out = out; a.obs = out_bstride;
-  a.Ho = upsample ? 2 * H : H; a.Wo = upsample ? 2 * W : W;
-  a.nchunks = (Cin + kConvCK - 1) / kConvCK;
-  a.tiles_x = a.tiles_y = 0;
-  // Tile choice.  Candidates from most operand reuse (2 output blocks per workgroup, 8 accumulators per wave) to
-  // least (1 block, 4 rows); take the first that gives >= 2 workgroups per CU, else the first
-  // with >= 1 per CU, else the smallest tile: at B = 16 an idle CU costs more than the lost reuse.  (2-wave
-  // workgroups of 2 rows were measured: same MFMA chain per wave, no gain - the WV parameter stays for a K-split.)
+  if ((int64_t)H * W >= (1 << 28)) return TGSR_EUNSUPPORTED;
+  const int Ho = upsample ? 2 * H : H, Wo = upsample ? 2 * W : W;
   const int unit = glu ? 64 : 32;          // couts consumed per output block
   const int nob_max = (Cout % (2 * unit) == 0) ? 2 : 1;
   struct Cand { int nob, rows; };
@@ -368,14 +361,46 @@ extern "C" int tgsr_conv3x3_fwd(const float* x, int64_t x_bstride, int B, int Ci
     cands[nc++] = {nb, 4};
   }
   auto ntiles = [&](const Cand& c) {
-    return (int64_t)B * ((a.Ho + c.rows - 1) / c.rows) * ((a.Wo + 31) / 32) * (Cout / (unit * c.nob));
+    return (int64_t)B * ((Ho + c.rows - 1) / c.rows) * ((Wo + 31) / 32) * (Cout / (unit * c.nob));
   };
   int pick = nc - 1;
   for (int pass = 0; pass < 2 && pick == nc - 1; ++pass)
     for (int i = 0; i < nc; ++i)
       if (ntiles(cands[i]) >= (pass == 0 ? 512 : 256)) { pick = i; break; }
-  const int nob = cands[pick].nob, rows = cands[pick].rows;
-  const int groups = Cout / (unit * nob);
+  nob = cands[pick].nob; rows = cands[pick].rows;
+  groups = Cout / (unit * nob);
+  return TGSR_OK;
+}
+
+extern "C" int tgsr_conv3x3_fwd_plan(int B, int H, int W, int Cout, int epilogue, int upsample, int* nob, int* rows_per_wave,
+                                     int* groups) {
+  int n = 0, rows = 0, g = 0;
+  const int rc = conv3x3_fwd_plan(B, H, W, Cout, epilogue, upsample, n, rows, g);
+  if (rc != TGSR_OK) return rc;
+  if (nob) *nob = n;
+  if (rows_per_wave) *rows_per_wave = rows / 4;
+  if (groups) *groups = g;
+  return TGSR_OK;
+}
+
+extern "C" int tgsr_conv3x3_fwd(const float* x, int64_t x_bstride, int B, int Cin, int H, int W, const float* wpack,
+                                int Cout, const float* scale, const float* shift, const float* residual,
+                                int64_t res_bstride, float* out, int64_t out_bstride, int epilogue, int upsample,
+                                void* stream) {
+  if (!x || !wpack || !out || Cin < 1) return TGSR_EINVAL;
+  if ((scale == nullptr) != (shift == nullptr)) return TGSR_EINVAL;
+  const bool glu = epilogue == TGSR_EPI_AFFINE_GLU;
+  if (glu && residual) return TGSR_EINVAL;
+  int nob = 0, rows = 0, groups = 0;   // (sizes, the epilogue selector, Cout % 32 | 64 and H W < 2^28 are the plan's to refuse)
+  if (const int rc = conv3x3_fwd_plan(B, H, W, Cout, epilogue, upsample, nob, rows, groups)) return rc;
+  if ((int64_t)Cin * H * W >= (1ll << 32)) return TGSR_EUNSUPPORTED;
+  ConvArgs a;
+  a.x = x; a.xbs = x_bstride; a.B = B; a.Cin = Cin; a.H = H; a.W = W;
+  a.wpack = wpack; a.Cout = Cout; a.scale = scale; a.shift = shift;
+  a.res = residual; a.rbs = res_bstride; a.out = out; a.obs = out_bstride;
+  a.Ho = upsample ? 2 * H : H; a.Wo = upsample ? 2 * W : W;
+  a.nchunks = (Cin + kConvCK - 1) / kConvCK;
+  a.tiles_x = a.tiles_y = 0;
   hipStream_t s = as_stream(stream);
   if (glu) return nob == 2 ? dispatch_up_r<2, true>(a, groups, upsample != 0, rows, s)
                            : dispatch_up_r<1, true>(a, groups, upsample != 0, rows, s);

@@ -556,7 +556,8 @@ static bool to3_pipe() { return g_to3_pipe != 0; }
 
 // Which kernel a head takes.  16-row tiles when they still give >= 2 workgroups per CU; smaller images take 8- or 4-row tiles (more
 // workgroups) and split the input channels over 2 / 4 thread groups (more waves per workgroup, fewer stages per wave).
-enum To3Form { TO3_MFMA, TO3_PIPE, TO3_VEC4, TO3_SCALAR };
+enum To3Form { TO3_MFMA = TGSR_TO3_FORM_MFMA, TO3_PIPE = TGSR_TO3_FORM_PIPE, TO3_VEC4 = TGSR_TO3_FORM_VEC4,
+               TO3_SCALAR = TGSR_TO3_FORM_SCALAR };
 
 static int64_t to3_tiles(const To3Args& a, int th) { return (int64_t)a.B * ((a.W + 63) / 64) * ((a.H + th - 1) / th); }
 static int to3_th(const To3Args& a) { return to3_tiles(a, 16) >= 512 ? 16 : to3_tiles(a, 8) >= 512 ? 8 : 4; }
@@ -573,6 +574,12 @@ static To3Form to3_form(const To3Args& a, int K) {
   const size_t wbytes = (size_t)a.Cin * ((3 * K * K + 3) & ~3) * sizeof(float);
   if (vec4 && wbytes <= 16 * 1024 && to3_pipe()) return TO3_PIPE;
   return vec4 ? TO3_VEC4 : TO3_SCALAR;
+}
+
+// The one plan of a head (host arithmetic; also exported as tgsr_conv_to3_plan): its form and the output rows per workgroup.
+static void to3_plan(const To3Args& a, int K, To3Form& form, int& th) {
+  form = to3_form(a, K);
+  th = form == TO3_MFMA ? 8 : to3_th(a);
 }
 
 // The streaming forms of one tile height.  `fin` (the closing launch) is given only where to3_form() said TO3_PIPE.
@@ -601,7 +608,9 @@ static int launch_to3_th(To3Args a, To3Form form, const To3Fin* fin, int extra_b
 
 template <int K, int ACT>
 static int launch_to3(To3Args a, const To3Fin* fin, int extra_blocks, hipStream_t s) {
-  const To3Form form = to3_form(a, K);
+  To3Form form;
+  int th;
+  to3_plan(a, K, form, th);
   if (form == TO3_MFMA) {
     a.tiles_x = a.W / 64;
     // 8-channel chunks (31 KB of LDS, 4 workgroups per CU): 83 us on the 256^2 head against 90 us with 16-channel chunks
@@ -610,7 +619,7 @@ static int launch_to3(To3Args a, const To3Fin* fin, int extra_blocks, hipStream_
     hipLaunchKernelGGL((conv_to3_mfma_kernel<K, ACT, 8, 8>), dim3((unsigned)(a.B * a.tiles_x * a.tiles_y)), dim3(256), 0, s, a);
     return note_launch(hipGetLastError(), "conv_to3_mfma_kernel");
   }
-  switch (to3_th(a)) {
+  switch (th) {
     case 16: return launch_to3_th<K, ACT, 16, 1>(a, form, fin, extra_blocks, s);
     case 8: return launch_to3_th<K, ACT, 8, 2>(a, form, fin, extra_blocks, s);
     default: return launch_to3_th<K, ACT, 4, 4>(a, form, fin, extra_blocks, s);
@@ -628,7 +637,7 @@ extern "C" int tgsr_conv_to3_set_pipe(int on) {
 }
 
 static int to3_args(To3Args& a, const float* x, int64_t x_bstride, int B, int Cin, int H, int W, const float* w, int K, float* out) {
-  if (!x || !w || !out || B < 1 || Cin < 1 || H < 1 || W < 1) return TGSR_EINVAL;
+  if (!x || !out || B < 1 || Cin < 1 || H < 1 || W < 1) return TGSR_EINVAL;
   if (K != 3 && K != 5) return TGSR_EUNSUPPORTED;
   if ((int64_t)H * W >= (1 << 28) || (int64_t)Cin * H * W >= (1ll << 32)) return TGSR_EUNSUPPORTED;
   a.x = x; a.xbs = x_bstride; a.B = B; a.Cin = Cin; a.H = H; a.W = W; a.w = w;
@@ -636,9 +645,23 @@ static int to3_args(To3Args& a, const float* x, int64_t x_bstride, int B, int Ci
   return TGSR_OK;
 }
 
+extern "C" int tgsr_conv_to3_plan(const float* x, int64_t x_bstride, int B, int Cin, int H, int W, int K, const float* addend,
+                                  const float* out, int* form, int* tile_rows) {
+  To3Args a;
+  if (const int rc = to3_args(a, x, x_bstride, B, Cin, H, W, nullptr, K, const_cast<float*>(out))) return rc;
+  a.addend = addend;
+  To3Form f;
+  int th;
+  to3_plan(a, K, f, th);
+  if (form) *form = (int)f;
+  if (tile_rows) *tile_rows = th;
+  return TGSR_OK;
+}
+
 extern "C" int tgsr_conv_to3_fwd(const float* x, int64_t x_bstride, int B, int Cin, int H, int W, const float* w,
                                  int K, int act, const float* addend, float alpha, float* out, void* stream) {
   To3Args a;
+  if (!w) return TGSR_EINVAL;
   if (const int rc = to3_args(a, x, x_bstride, B, Cin, H, W, w, K, out)) return rc;
   if (act != TGSR_ACT_NONE && act != TGSR_ACT_TANH_AXPY) return TGSR_EINVAL;
   if (act == TGSR_ACT_NONE && addend) return TGSR_EINVAL;
@@ -652,6 +675,7 @@ extern "C" int tgsr_conv_to3_finish_fwd(const float* x, int64_t x_bstride, int B
                                         float* out, int n, float* const* fine, const float* const* t, const float* const* s,
                                         const int64_t* numel, float alpha, void* stream) {
   To3Args a;
+  if (!w) return TGSR_EINVAL;
   if (const int rc = to3_args(a, x, x_bstride, B, Cin, H, W, w, K, out)) return rc;
   if (n < 1 || !fine || !t || !s || !numel) return TGSR_EINVAL;
   if (n > 3) return TGSR_EUNSUPPORTED;
