@@ -772,6 +772,34 @@ int tgsr_sr_metrics(const void* sr, int sr_f32, const void* hr, int hr_f32, int 
 int tgsr_rgb_to_y_u8(const uint8_t* rgb, int B, int H, int W, uint8_t* y, void* stream);
 
 /*
+ * Whole-image inference by overlapping tiles (SRPipeline.upscale; the reference's arbitrary-size example path,
+ * datasets.py:200-278, followed by the fully convolutional generators): the cut and the reassembly of a tile batch.
+ * table: int32 [Tb][6] = (y0, x0, oy0, oy1, ox0, ox1) in LR pixels, once in host memory (table_host, checked here) and once in
+ * device memory (table_dev, what the kernels read - they skip a row that fails the same checks, so no access leaves an
+ * image).  Window t is rows [y0, y0 + th) x columns [x0, x0 + tw) of the H x W image; the rectangle it OWNS is
+ * [oy0, oy1) x [ox0, ox1).  TGSR_EINVAL unless 1 <= th <= min(H, 4096), 1 <= tw <= min(W, 4096), H, W <= 2^20, Tb in [1, 65535]
+ * and for every row 0 <= y0 <= H - th, 0 <= x0 <= W - tw, y0 <= oy0 < oy1 <= y0 + th, x0 <= ox0 < ox1 <= x0 + tw.
+ *   tgsr_tile_gather  img (and img2 unless NULL; out2 is NULL exactly when img2 is): planar [3][H][W], both uint8 (is_u8 != 0:
+ *       normalised by tgsr_u8_normalize's arithmetic, (u8 / 255 - 0.5) / 0.5 in float32 division, subtraction, division) or both
+ *       float32 (a bit copy).  out / out2: float32 [Tb][3][th][tw].  One launch for both images.
+ *   tgsr_tile_stitch  n <= TGSR_STITCH_MAX outputs of the tile batch in one launch (host arrays of n entries): src[e] float32
+ *       [Tb][C[e]][s th][s tw] with s = scale[e] in [1, 64], a dense (C, s th, s tw) block per tile and src_stride[e] elements
+ *       between tiles (so a channel crop of a wider buffer is taken in place); dst[e]: [C[e]][s H][s W], float32 (out_u8[e] == 0:
+ *       a bit copy) or uint8 (tgsr_to_uint8's rule, the same bytes).  Only each tile's owned rectangle (times s) is written:
+ *       where the owned rectangles partition the image (tgsr_amd.tiles.plan_tiles) every output pixel has exactly one source -
+ *       no blending, no atomics, the same bits on every run.  Two rows may name the same window (a padded last batch): their
+ *       pixels are written twice with the same values.
+ * Rows move as 16-byte accesses where the bases, the row pitches and the rectangle's first column are multiples of 4
+ * elements, element by element otherwise (any H, W, offsets).  Plain loads and stores; capturable.
+ */
+#define TGSR_STITCH_MAX 12
+int tgsr_tile_gather(const void* img, const void* img2, int is_u8, int H, int W, const int32_t* table_host,
+                     const int32_t* table_dev, int Tb, int th, int tw, float* out, float* out2, void* stream);
+int tgsr_tile_stitch(int n, const float* const* src, const int64_t* src_stride, void* const* dst, const int* C,
+                     const int* scale, const int* out_u8, int H, int W, const int32_t* table_host, const int32_t* table_dev,
+                     int Tb, int th, int tw, void* stream);
+
+/*
  * Weight gradient of tgsr_conv3x3_fwd: dw[Cout][Cin][3][3] = sum over (b, y, x) of grad_out * shifted input
  * (upsample=1: the input is read through the folded nearest-x2, H/W are the PRE-upsample sizes).
  * grad_out [B][Cout][Ho][Wo] dense; x [B][Cin][H][W] with batch stride; Cout % 32 == 0.

@@ -581,6 +581,23 @@ rgb_to_y = _define("rgb_to_y(Tensor rgb) -> Tensor", lambda rgb: ops.rgb_to_y(rg
                    lambda rgb: rgb.new_empty(rgb.shape[0], rgb.shape[2], rgb.shape[3], dtype=torch.uint8))
 
 
+# whole images by overlapping tiles (SRPipeline.upscale): `table` is the host int32 [Tb, 6] window table, `table_dev` its device copy
+def _tile_gather(img, img2, table, table_dev, th, tw):
+    lr, lrb = ops.tile_gather(img, table, th, tw, img2=img2, table_dev=table_dev)
+    return lr, (lrb if lrb is not None else lr.new_empty(0))
+
+
+tile_gather = _define("tile_gather(Tensor img, Tensor? img2, Tensor table, Tensor table_dev, int th, int tw) -> (Tensor, Tensor)",
+                      _tile_gather,
+                      lambda img, img2, table, table_dev, th, tw: (
+                          img.new_empty(table.shape[0], 3, th, tw, dtype=torch.float32),
+                          img.new_empty((table.shape[0], 3, th, tw) if img2 is not None else (0,), dtype=torch.float32)))
+tile_stitch = _define("tile_stitch(Tensor[] tiles, Tensor(a!)[] outs, Tensor table, Tensor table_dev, int H, int W, int th, int tw) -> ()",
+                      lambda tiles, outs, table, table_dev, H, W, th, tw:
+                      ops.tile_stitch(list(tiles), list(outs), table, H, W, th, tw, table_dev=table_dev),
+                      lambda *a: None)
+
+
 # ================================================================================================ reduced-precision path
 # (lp images are mutable arguments: every kernel writes a channel slice of a caller-owned zero-bordered image)
 lp_conv3x3 = _define("lp_conv3x3(Tensor x, Tensor wpack, int cin, int cout, Tensor? scale, Tensor? shift, bool glu, bool upsample, "

@@ -5,6 +5,8 @@
     `transforms.Resize` and `ImageFilter.GaussianBlur` delegate to), restated in integer HIP kernels
     (tgsr_resize_bilinear_u8 / tgsr_gaussian_blur_u8 / tgsr_u8_normalize): byte-identical pyramids, so an end-to-end
     run is no longer bound by the CPU image library.
+  * `example_pyramid` - `get_imgsexampletestblur` (datasets.py:236-278) for one decoded image of any size: crop to a multiple of
+    the scale, the LR image, and the same four lists; what `SRPipeline.upscale` takes its LR image from.
   * `RaggedImages`, `DeviceAugment`, `SRBatcher` - what stands in front of that pyramid in the reference's loaders, for a
     batch of decoded images of different sizes: the CUB bounding-box crop (datasets.py:115-123, `crop_box`),
     `transforms.Resize` (`resized_size`), RandomCrop + RandomHorizontalFlip (test1.py:184-186) or CenterCrop
@@ -117,6 +119,45 @@ class GpuImagePyramid:
         if u8:
             return ret, bic, retb, bicb
         n = self.normalize
+        return [n(t) for t in ret], [n(t) for t in bic], [n(t) for t in retb], [n(t) for t in bicb]
+
+
+def example_pyramid(hr_u8: torch.Tensor, scale: int = 8, blur_radius: float = 2.0, u8: bool = False):
+    """`get_imgsexampletestblur` (datasets.py:236-278; without the blurred lists, `get_imgsexampletest`, :200-233) for ONE decoded
+    image of any size, planar uint8 [3, H, W] on the device: crop to a multiple of `scale` (the top-left corner stays),
+    `lrimg = Resize((h / scale, w / scale))`, then per power of two from there up to `scale` the HR image resized to that size
+    (the last one is the crop itself), the LR image re-grown to it, and their GaussianBlur(radius) versions.
+
+        ret, bic, retb, bicb = example_pyramid(hr_u8)              # each a list of float32 [3, h s / scale, w s / scale] in [-1, 1]
+        out = pipe.upscale(bic[0], caption, cap_len, lr_blur=bicb[0])   # bic[0] IS the LR image (a Resize to its own size returns it)
+
+    Byte-identical to the Pillow chain (resize_bilinear_u8, gaussian_blur_u8, u8_normalize); `u8=True` returns the uint8 lists."""
+    scale = int(scale)
+    if (not torch.is_tensor(hr_u8) or hr_u8.dtype != torch.uint8 or hr_u8.dim() != 3 or hr_u8.shape[0] != 3 or not hr_u8.is_cuda):
+        raise TgsrError("example_pyramid: expected a planar uint8 [3, H, W] device image")
+    if scale < 1 or scale & (scale - 1):
+        raise TgsrError("example_pyramid: scale %r is no power of two (the pyramid doubles from the LR size up)" % (scale,))
+    h, w = int(hr_u8.shape[1]) // scale * scale, int(hr_u8.shape[2]) // scale * scale
+    if h < scale or w < scale:
+        raise TgsrError("example_pyramid: a %d x %d image has no whole %d x %d block" % (hr_u8.shape[1], hr_u8.shape[2], scale, scale))
+    with torch.cuda.device(hr_u8.device):
+        pyr = GpuImagePyramid((1,), blur_radius, hr_u8.device)
+        img = hr_u8[:, :h, :w].contiguous()                                       # img.crop([0, 0, w, h]), :251
+        lr = pyr.resize(img, h // scale, w // scale)                              # `lrimg`, :255
+        ret, bic, retb, bicb = [], [], [], []
+        s = 1
+        while s <= scale:
+            hs, ws = h // scale * s, w // scale * s
+            re = pyr.resize(img, hs, ws) if s < scale else img                    # :261-265
+            bi = pyr.resize(lr, hs, ws)                                           # :272
+            ret.append(re)
+            retb.append(pyr.gaussian_blur(re))                                    # :267
+            bic.append(bi)
+            bicb.append(pyr.gaussian_blur(bi))                                    # :274
+            s *= 2
+        if u8:
+            return ret, bic, retb, bicb
+        n = pyr.normalize
         return [n(t) for t in ret], [n(t) for t in bic], [n(t) for t in retb], [n(t) for t in bicb]
 
 

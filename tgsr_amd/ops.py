@@ -1824,6 +1824,126 @@ def to_uint8(img: torch.Tensor) -> torch.Tensor:
     return out
 
 
+# ----------------------------------------------------------------------------------------- whole images by tiles
+TILE_DESC = 6            # int32 per window: y0, x0, oy0, oy1, ox0, ox1 (LR pixels; tgsr_amd.tiles.plan_tiles)
+TILE_MAX_SIDE = 1 << 20  # LR H, W
+TILE_MAX_TILE = 4096     # th, tw
+STITCH_MAX = 12          # outputs per tile_stitch launch (TGSR_STITCH_MAX)
+
+
+def _tile_table_host(table, H: int, W: int, th: int, tw: int) -> torch.Tensor:
+    """The checks that cost no tensor operation: the table is readable host memory of the stated shape, the sides are in range."""
+    t = torch.as_tensor(table)
+    if t.is_cuda or t.dtype != torch.int32 or t.dim() != 2 or t.shape[1] != TILE_DESC or not 1 <= t.shape[0] <= 65535:
+        raise TgsrError("tiles: the window table is a host int32 [Tb, %d] tensor with 1 <= Tb <= 65535, got %s %s on %s"
+                        % (TILE_DESC, t.dtype, tuple(t.shape), t.device))
+    H, W, th, tw = int(H), int(W), int(th), int(tw)
+    if not (1 <= H <= TILE_MAX_SIDE and 1 <= W <= TILE_MAX_SIDE):
+        raise TgsrError("tiles: an image of %d x %d (sides must lie in [1, %d])" % (H, W, TILE_MAX_SIDE))
+    if not (1 <= th <= min(H, TILE_MAX_TILE) and 1 <= tw <= min(W, TILE_MAX_TILE)):
+        raise TgsrError("tiles: a %d x %d window for a %d x %d image (1 <= window <= min(side, %d))" % (th, tw, H, W, TILE_MAX_TILE))
+    return t.contiguous()
+
+
+def check_tile_table(table, H: int, W: int, th: int, tw: int) -> torch.Tensor:
+    """The window checks of tgsr_tile_gather / tgsr_tile_stitch (include/tgsr_hip.h), on the host and with a message: returns
+    the table as a contiguous int32 [Tb, 6] host tensor or raises TgsrError.  Touches no device.  tile_gather / tile_stitch leave
+    the windows to the C entry's own pass over the host table and come here only for the message when it refuses."""
+    t = _tile_table_host(table, H, W, th, tw)
+    H, W, th, tw = int(H), int(W), int(th), int(tw)
+    y0, x0, oy0, oy1, ox0, ox1 = (c.to(torch.int64) for c in t.unbind(1))
+    rules = (
+        ("a window outside the image", (y0 < 0) | (x0 < 0) | (y0 > H - th) | (x0 > W - tw)),
+        ("owned rows that are empty or outside the window", (oy0 < y0) | (oy1 <= oy0) | (oy1 > y0 + th)),
+        ("owned columns that are empty or outside the window", (ox0 < x0) | (ox1 <= ox0) | (ox1 > x0 + tw)),
+    )
+    for what, bad in rules:
+        if bool(bad.any()):
+            b = int(bad.nonzero()[0])
+            raise TgsrError("tiles: window %d has %s (row %s, image %d x %d, window %d x %d)" % (b, what, t[b].tolist(), H, W, th, tw))
+    return t
+
+
+def _tile_table_dev(table_dev, t, device):
+    if table_dev is None:
+        return t.to(device)
+    if (not table_dev.is_cuda or table_dev.dtype != torch.int32 or tuple(table_dev.shape) != tuple(t.shape)
+            or not table_dev.is_contiguous()):
+        raise TgsrError("tiles: table_dev must be the dense int32 %s device copy of the table" % (tuple(t.shape),))
+    return table_dev
+
+
+def tile_gather(img: torch.Tensor, table, th: int, tw: int, img2: Optional[torch.Tensor] = None,
+                table_dev: Optional[torch.Tensor] = None):
+    """Windows of one planar image [3, H, W] (and of a second one of the same shape and dtype - the blurred LR - in the same
+    launch) as float32 [Tb, 3, th, tw] (tgsr_tile_gather): uint8 is normalised exactly like `u8_normalize`, float32 is a bit
+    copy.  table: host int32 [Tb, 6] (check_tile_table); table_dev: its device copy where the caller keeps one.  Returns
+    (LR, LRb) - LRb None without img2."""
+    for name, x in (("img", img), ("img2", img2)):
+        if x is None:
+            continue
+        if not torch.is_tensor(x) or x.dim() != 3 or x.shape[0] != 3 or x.dtype not in (torch.uint8, torch.float32):
+            raise TgsrError("tile_gather: %s must be a planar uint8 or float32 [3, H, W] image, got %s" % (
+                name, "%s %s" % (x.dtype, tuple(x.shape)) if torch.is_tensor(x) else type(x).__name__))
+    if img2 is not None and (img2.shape != img.shape or img2.dtype != img.dtype):
+        raise TgsrError("tile_gather: img2 is %s %s, img %s %s" % (img2.dtype, tuple(img2.shape), img.dtype, tuple(img.shape)))
+    H, W = int(img.shape[1]), int(img.shape[2])
+    t = _tile_table_host(table, H, W, th, tw)
+    _need_hip(img, img2, table_dev)
+    tdev = _tile_table_dev(table_dev, t, img.device)
+    img = img.contiguous()
+    img2 = None if img2 is None else img2.contiguous()
+    Tb = t.shape[0]
+    out = torch.empty(Tb, 3, th, tw, dtype=torch.float32, device=img.device)
+    out2 = torch.empty_like(out) if img2 is not None else None
+    rc = _lib.lib().tgsr_tile_gather(_p(img), _p(img2), int(img.dtype == torch.uint8), H, W, _p(t), _p(tdev), Tb, int(th), int(tw),
+                                     _p(out), _p(out2), _stream())
+    if rc:
+        check_tile_table(t, H, W, th, tw)                  # the window at fault, by name
+    check(rc, "tgsr_tile_gather")
+    return out, out2
+
+
+def tile_stitch(tiles, outs, table, H: int, W: int, th: int, tw: int, table_dev: Optional[torch.Tensor] = None) -> None:
+    """The owned rectangle of every tile of every tile output, into the whole-image outputs, in one launch (tgsr_tile_stitch).
+    tiles[e]: float32 [Tb, C, s th, s tw] with a dense (C, s th, s tw) block and any tile stride; outs[e]: dense [C, s H, s W],
+    float32 (a bit copy) or uint8 (`to_uint8`'s bytes); the scale s is read off the shapes.  Pixels no tile owns keep what `outs`
+    held."""
+    tiles, outs = list(tiles), list(outs)
+    n = len(tiles)
+    if n < 1 or n != len(outs) or n > STITCH_MAX:
+        raise TgsrError("tile_stitch: %d tile outputs for %d images (1 to %d per launch)" % (n, len(outs), STITCH_MAX))
+    t = _tile_table_host(table, H, W, th, tw)
+    Tb = t.shape[0]
+    _need_hip(*tiles, *outs, table_dev)
+    tdev = _tile_table_dev(table_dev, t, tiles[0].device)
+    Cs, ss, u8s, strides = [], [], [], []
+    for e, (x, o) in enumerate(zip(tiles, outs)):
+        if x.dtype != torch.float32 or x.dim() != 4 or x.shape[0] != Tb:
+            raise TgsrError("tile_stitch: tiles[%d] must be float32 [%d, C, s*%d, s*%d], got %s %s" % (e, Tb, th, tw, x.dtype, tuple(x.shape)))
+        C, s = int(x.shape[1]), int(x.shape[2]) // int(th)
+        if s < 1 or s > 64 or tuple(x.shape[2:]) != (s * th, s * tw) or C < 1 or C > 65535:
+            raise TgsrError("tile_stitch: tiles[%d] %s is no [%d, C, s*%d, s*%d] for an integer scale 1 <= s <= 64"
+                            % (e, tuple(x.shape), Tb, th, tw))
+        if (x.stride(3) != 1 or x.stride(2) != s * tw or (C > 1 and x.stride(1) != s * th * s * tw)
+                or (Tb > 1 and x.stride(0) < C * s * th * s * tw)):
+            raise TgsrError("tile_stitch: tiles[%d] needs a dense (C, H, W) block per tile (strides %s)" % (e, tuple(x.stride())))
+        if o.dtype not in (torch.float32, torch.uint8) or tuple(o.shape) != (C, s * H, s * W) or not o.is_contiguous():
+            raise TgsrError("tile_stitch: outs[%d] must be a dense float32 or uint8 [%d, %d, %d], got %s %s"
+                            % (e, C, s * H, s * W, o.dtype, tuple(o.shape)))
+        Cs.append(C)
+        ss.append(s)
+        u8s.append(int(o.dtype == torch.uint8))
+        strides.append(x.stride(0) if Tb > 1 else C * s * th * s * tw)
+    src = (ctypes.c_void_p * n)(*[x.data_ptr() for x in tiles])
+    dst = (ctypes.c_void_p * n)(*[o.data_ptr() for o in outs])
+    rc = _lib.lib().tgsr_tile_stitch(n, src, (ctypes.c_int64 * n)(*strides), dst, (ctypes.c_int * n)(*Cs), (ctypes.c_int * n)(*ss),
+                                     (ctypes.c_int * n)(*u8s), int(H), int(W), _p(t), _p(tdev), Tb, int(th), int(tw), _stream())
+    if rc:
+        check_tile_table(t, H, W, th, tw)                  # the window at fault, by name
+    check(rc, "tgsr_tile_stitch")
+
+
 # ----------------------------------------------------------------------------------------- image quality
 METRICS_WINDOW = 11      # the SSIM window; a shaved crop may not be smaller
 

@@ -1,0 +1,89 @@
+"""Whole-image inference by overlapping tiles: the host side of `SRPipeline.upscale`.
+
+The x8 generators are fully convolutional (3x3 and 5x5 convolutions with zero padding, eval-mode BatchNorm, nearest
+up-sampling, word attention that is a softmax over the words at each pixel separately), so an image of any size can be cut
+into overlapping windows, run as an ordinary fixed-shape batch and put back together WITHOUT changing a value - if every
+pixel a window owns is at least one receptive radius (`receptive_halo`) away from each window edge that is not an image
+edge, and a window edge on the image edge sees the zero padding the whole image would see there.  `plan_axis` /
+`plan_tiles` produce such windows; ops.tile_gather / ops.tile_stitch (tgsr_tiles.hip) cut and reassemble on the device.
+"""
+import math
+
+import torch
+import torch.nn as nn
+
+DEFAULT_TILE = 128      # SRPipeline.upscale's window side in LR pixels (measured: tools/upscale_timing.py)
+
+
+def plan_axis(n: int, tile: int, halo: int):
+    """Windows along one axis of n pixels: a list of (x0, own0, own1) - the window is [x0, x0 + tile), it owns [own0, own1).
+    n >= tile > 2 * halo.  The windows never leave [0, n): the last one is clamped back to end at n.  A window edge is either the
+    image edge or at least `halo` pixels away from every pixel the window owns; the owned intervals partition [0, n)."""
+    n, tile, halo = int(n), int(tile), int(halo)
+    if halo < 0 or tile <= 2 * halo or n < tile:
+        raise ValueError("plan_axis: need n >= tile > 2 * halo >= 0, got n = %d, tile = %d, halo = %d" % (n, tile, halo))
+    out, c0 = [], 0
+    while True:
+        x0 = min(max(c0 - halo, 0), n - tile)
+        own1 = n if x0 + tile == n else x0 + tile - halo
+        out.append((x0, c0, own1))
+        c0 = own1
+        if own1 == n:
+            return out
+
+
+def plan_tiles(H: int, W: int, tile, halo: int) -> torch.Tensor:
+    """The product of the two axes' plans: host int32 [T, 6] rows (y0, x0, oy0, oy1, ox0, ox1), row-major over the windows.
+    tile: one side, or (th, tw); an axis whose window is the whole side (th == H: an image shorter than the tile) has the one
+    window that owns everything, whatever the halo - both its edges are image edges."""
+    th, tw = (tile, tile) if isinstance(tile, int) else tile
+
+    def axis(n, t):
+        return [(0, 0, int(n))] if int(t) == int(n) else plan_axis(n, t, halo)
+    rows = [(y0, x0, oy0, oy1, ox0, ox1) for y0, oy0, oy1 in axis(H, th) for x0, ox0, ox1 in axis(W, tw)]
+    return torch.tensor(rows, dtype=torch.int32)
+
+
+def _chain(mods, radius: float, res: float):
+    """Receptive radius (in pixels of the chain's input) behind `mods` run one after the other, entered with `radius` at
+    `res` output pixels per input pixel: a k x k convolution adds (k - 1) / 2 pixels of its own resolution, nearest
+    up-sampling multiplies the resolution."""
+    for m in mods:
+        for leaf in m.modules():
+            if isinstance(leaf, nn.Upsample):
+                res *= float(leaf.scale_factor)
+            elif isinstance(leaf, nn.Conv2d):
+                k, s, d = leaf.kernel_size, leaf.stride, leaf.dilation
+                if k[0] != k[1] or s != (1, 1) or d != (1, 1) or k[0] % 2 != 1:
+                    raise ValueError("receptive_halo: %r is no stride-1 odd square convolution" % (leaf,))
+                radius += (k[0] - 1) / 2.0 / res
+    return radius, res
+
+
+def receptive_radius(netGL, netGH) -> float:
+    """The largest receptive radius, in LR pixels, of any output of the x8 generators (G_SR_NET_low's three images,
+    NetG_highweight's three heads), counted from the modules: 3x3 and 5x5 convolutions at their resolution.  The word
+    attention is per pixel (its 1x1 convolution runs over the words) and adds nothing."""
+    try:
+        stages = [([netGL.h_net1.im2f, netGL.h_net1.residual, netGL.h_net1.upsample], netGL.img_net1),
+                  ([netGL.h_net2.residual, netGL.h_net2.upsample], netGL.img_net2),
+                  ([netGL.h_net3.residual, netGL.h_net3.upsample], netGL.img_net3)]
+        high = [([netGH.convin, netGH.residual, netGH.upscale2x], netGH.conv_output),
+                ([netGH.residual24, netGH.upscale4x], netGH.conv_output),
+                ([netGH.residual48, netGH.upscale8x], netGH.conv_output)]
+    except AttributeError as e:
+        raise ValueError("receptive_halo walks the x8 generators of tgsr_amd.model (G_SR_NET_low, NetG_highweight): %s" % e)
+    worst = 0.0
+    for net in (stages, high):
+        r, res = 0.0, 1.0
+        for trunk, head in net:
+            r, res = _chain(trunk, r, res)
+            worst = max(worst, _chain([head], r, res)[0])
+    return worst
+
+
+def receptive_halo(netGL, netGH) -> int:
+    """The halo `upscale` needs: the ceiling of `receptive_radius` in LR pixels (16 for the shipped x8 networks:
+    NetG_highweight reaches 15.625 - 13 from convin and the 12 ResBlock convolutions at LR resolution, 1.5 at 2x, 0.75 at 4x,
+    0.125 + 0.25 at 8x; G_SR_NET_low 9)."""
+    return int(math.ceil(receptive_radius(netGL, netGH) - 1e-9))

@@ -134,6 +134,7 @@ class SRPipeline:
         # images): run it on a second HIP stream so the two networks' small layers and kernel tails overlap
         self.overlap = overlap
         self._side = None
+        self._tile_graphs, self._tile_graphs_sig = {}, None
         for m in (self.text_encoder, self.netGL, self.netGH):
             m.to(self.device)
             m.eval()
@@ -163,6 +164,7 @@ class SRPipeline:
         self.device = torch.device(device) if device is not None else next(netGL.parameters()).device
         self.overlap = overlap
         self._side = None
+        self._tile_graphs, self._tile_graphs_sig = {}, None
         if lp_dtype:
             from .lp_pipeline import LpExecutor
             self._lp = LpExecutor(self.netGL, self.netGH, dtype)
@@ -195,6 +197,7 @@ class SRPipeline:
             if self.branch_num == 4:
                 sd_GH = {k: v for k, v in sd_GH.items() if k != "a"}
             self.netGH.load_state_dict(sd_GH, strict=True)
+        self._tile_graphs, self._tile_graphs_sig = {}, None          # upscale(graph=True)'s captured steps hold the old weights
         return self
 
     # ------------------------------------------------------------------ throughput: stream lanes
@@ -248,6 +251,117 @@ class SRPipeline:
             invalidate_caches(m)
         if self._lp is not None:
             self._lp.key = None
+        self._tile_graphs, self._tile_graphs_sig = {}, None
+
+    # ------------------------------------------------------------------ whole images of any size, by tiles
+    def _tile_step(self, caps, lens, LR, LRb):
+        """The captured tile-batch step of upscale(graph=True) for this batch shape.  A captured graph holds raw pointers to the
+        weight packs and folded BatchNorm affines of its capture, so the steps are kept only as long as every parameter and
+        buffer of the three networks is the tensor, at the version, it was then (util._ver: what the packs themselves key on):
+        after load_state_dicts, an optimizer step or any other torch in-place write the old steps are dropped and one is
+        captured on the new weights.  A writer that bypasses the version counters calls invalidate_caches."""
+        from .util import _ver
+        sig = _ver(*(t for m in (self.text_encoder, self.netGL, self.netGH) for t in (*m.parameters(), *m.buffers())))
+        if sig != self._tile_graphs_sig:
+            self._tile_graphs, self._tile_graphs_sig = {}, sig
+        key = (LR.shape[0], LR.shape[2], LR.shape[3], caps.shape[1], LR.device)
+        step = self._tile_graphs.get(key)
+        if step is None:
+            step = self._tile_graphs[key] = GraphedStep(self, caps, lens, LR, LRb)
+        return step
+
+    @torch.no_grad()
+    def upscale(self, lr, caption, cap_len, lr_blur=None, tile=None, halo=None, tile_batch=4, out="f32", with_att=False,
+                graph=False):
+        """Super-resolve ONE image of any size (the reference's arbitrary-size example path, datasets.py:200-278
+        get_imgsexampletest*, + gen_exampleSRHL on the whole image): the image is cut into overlapping `tile` x `tile` LR windows
+        (ops.tile_gather), the windows run through this pipeline's own `__call__` in fixed-shape batches of `tile_batch`, and every
+        window's owned rectangle goes into the whole-image outputs (ops.tile_stitch).  With halo >= tiles.receptive_halo (16 for the
+        shipped x8 networks) the result is what one `__call__` on the whole image computes - not an approximation: each output
+        pixel sees its complete receptive field, and a window edge on the image edge sees the same zero padding.
+
+        lr: [3, H, W] device tensor, uint8 (normalised like the loader's ToTensor + Normalize) or float32 in [-1, 1].
+        caption [W] or [1, W] int64, cap_len: the image's one caption, replicated over the tile batch.
+        lr_blur: the GaussianBlur(radius=2) LR image, same shape and dtype as `lr`; None: computed from a uint8 `lr`
+        (datasets.gaussian_box_params + ops.gaussian_blur_u8, byte-identical to Pillow) when NetG_highweight's `low` reads it; a
+        float32 `lr` must bring it then.
+        tile: window side in LR pixels (default tiles.DEFAULT_TILE); a side of the image shorter than it shrinks the window to the
+        whole side.  halo: default and minimum tiles.receptive_halo(netGL, netGH).  The last batch is padded by repeating its last
+        window, so every batch has one shape.  graph=True: one tile-batch step is captured (GraphedStep, kept per shape
+        while the networks' weights stay what they were at the capture, `_tile_step`) and replayed per batch.
+        out: "f32" (float32, un-clamped, the bits `__call__` returns) or "u8" (`to_uint8`'s bytes, converted in the stitch).
+        Returns {"fine": [3 x [3, sH, sW]], "fake": [...]} for s = 2, 4, 8, + "att": [3 x [cap_len, sH, sW]] (s = 1, 2, 4; float32)
+        with with_att."""
+        from . import tiles as T
+        if self.branch_num != 4:
+            raise ValueError("upscale: the x16 generators (models16.py) are not tiled here - their receptive field and 16 x 16 "
+                             "design size are out of this method's scope; use the x8 pipeline (branch_num=4)")
+        if getattr(self.netGH, "weightmap", False):
+            raise ValueError("upscale: NetG_highweight(weightmap=True) cannot be tiled - its maps a1..a3 are sized for one 32 x 32 "
+                             "LR input (model.py:236-239), not for windows of another image")
+        if out not in ("f32", "u8"):
+            raise ValueError("upscale: out is 'f32' or 'u8', got %r" % (out,))
+        if not torch.is_tensor(lr) or lr.dim() != 3 or lr.shape[0] != 3 or lr.dtype not in (torch.uint8, torch.float32) or not lr.is_cuda:
+            raise ValueError("upscale: lr must be a uint8 or float32 [3, H, W] device tensor")
+        H, W = int(lr.shape[1]), int(lr.shape[2])
+        need = T.receptive_halo(self.netGL, self.netGH)
+        halo = need if halo is None else int(halo)
+        if halo < need:
+            raise ValueError("upscale: halo %d is below the networks' receptive radius of %d LR pixels (tiles.receptive_halo): the "
+                             "high-frequency network's output near a seam would be wrong, not merely less sharp" % (halo, need))
+        tile = T.DEFAULT_TILE if tile is None else int(tile)
+        if tile <= 2 * halo:
+            raise ValueError("upscale: a tile of %d cannot hold a halo of %d on both sides (tile > 2 * halo)" % (tile, halo))
+        th, tw = min(tile, H), min(tile, W)
+        if self._lp is not None and (th, tw) != (64, 64):
+            raise ValueError("upscale(dtype=%r): the reduced-precision path is tiled with 64 x 64 windows only (tile=64 on an image "
+                             "of at least 64 x 64) - the one window shape it is verified at; the window here is %d x %d (image "
+                             "%d x %d, tile %d)" % (self.dtype, th, tw, H, W, tile))
+        tb = int(tile_batch)
+        if tb < 1:
+            raise ValueError("upscale: tile_batch %r" % (tile_batch,))
+        low = self.netGH.low
+        with torch.cuda.device(lr.device):
+            if low != "lr" and lr_blur is None:
+                if lr.dtype != torch.uint8:
+                    raise ValueError("upscale: NetG_highweight(low=%r) reads the blurred LR image - pass lr_blur with a float32 lr" % low)
+                from .datasets import gaussian_box_params
+                lr_blur = ops.gaussian_blur_u8(lr, *gaussian_box_params(2.0, 3), 3)
+            if lr_blur is not None and (lr_blur.shape != lr.shape or lr_blur.dtype != lr.dtype):
+                raise ValueError("upscale: lr_blur is %s %s, lr %s %s" % (lr_blur.dtype, tuple(lr_blur.shape), lr.dtype, tuple(lr.shape)))
+            table = T.plan_tiles(H, W, (th, tw), halo)
+            nt = table.shape[0]
+            pad = (-nt) % tb
+            if pad:
+                table = torch.cat([table, table[-1:].expand(pad, -1)])             # repeat the last window: one batch shape
+            table = ops.check_tile_table(table, H, W, th, tw)
+            table_dev = table.to(lr.device)
+            caps = caption.reshape(1, -1).to(device=lr.device, dtype=torch.int64).expand(tb, -1).contiguous()
+            lens = [int(cap_len)] * tb
+            odt = torch.uint8 if out == "u8" else torch.float32
+            res = {k: [torch.empty(3, s * H, s * W, dtype=odt, device=lr.device) for s in (2, 4, 8)] for k in ("fine", "fake")}
+            if with_att:
+                res["att"] = [torch.empty(lens[0], s * H, s * W, dtype=torch.float32, device=lr.device) for s in (1, 2, 4)]
+            step = None
+            for b in range(0, table.shape[0], tb):
+                rows, rows_dev = table[b:b + tb], table_dev[b:b + tb]
+                LR, LRb = C.tile_gather(lr, lr_blur, rows, rows_dev, th, tw)
+                if lr_blur is None:
+                    LRb = LR                                                        # low == "lr": the blurred image is not read
+                if not graph:
+                    o = self(caps, lens, LR, LRb)
+                elif step is None:
+                    step = self._tile_step(caps, lens, LR, LRb)
+                    o = step.replay(caps, lens, LR, LRb)
+                else:
+                    o = step.replay(LR=LR, LRb=LRb)
+                srcs = list(o["fine"]) + list(o["fake"])
+                dsts = res["fine"] + res["fake"]
+                if with_att:
+                    srcs += list(o["att"])
+                    dsts = dsts + res["att"]
+                C.tile_stitch(srcs, dsts, rows, rows_dev, H, W, th, tw)
+        return res
 
     @torch.no_grad()
     def __call__(self, captions, cap_lens, LR, LRb, num_words=None):
