@@ -805,7 +805,32 @@ int tgsr_tile_stitch(int n, const float* const* src, const int64_t* src_stride, 
  * grad_out [B][Cout][Ho][Wo] dense; x [B][Cin][H][W] with batch stride; Cout % 32 == 0.
  * ws must hold tgsr_conv3x3_wgrad_ws_elems(...) floats (per-workgroup partial slabs, summed in a fixed order).
  * The data gradient is tgsr_conv3x3_fwd on the flipped / transposed weights (+ tgsr_sumpool2x2 for upsample=1).
+ *
+ * The planners of this and of the next two weight gradients.  Every launch is planned once, by one host function
+ * (csrc/tgsr_wgrad_plan.h); tgsr_conv3x3_wgrad_plan is that very function, for `kind` = TGSR_WGRAD_DIRECT (tgsr_conv3x3_wgrad),
+ * TGSR_WGRAD_WINO (tgsr_wino_wgrad; `upsample` is not read) or TGSR_WGRAD_UPWINO (tgsr_upwino_wgrad; likewise).  Host
+ * arithmetic only: grad_out and x are looked at for their alignment and never read through.  It returns what the launcher
+ * returns for these sizes and alignments (TGSR_EINVAL: a size < 1 or an unknown kind; TGSR_EUNSUPPORTED: the channel counts or
+ * an alignment the kernel does not take) and fills out[TGSR_WGRAD_PLAN_FIELDS] (may be NULL):
+ *     [0] the kernel family, TGSR_WGRAD_FAMILY_*     [1..3] its template integers, 0 where it has fewer:
+ *         DIRECT conv3x3_wgrad_kernel<NCOB, NCIB, UP>, WINO wino_wgrad_kernel<NCI, NCOB>, WINO_DMA wino_wgrad_dma_kernel<NCI>
+ *         (16-byte aligned operands, W % 4 == 0, x_bstride % 4 == 0 on a Cout % 64 == 0, Cin % 64 == 0 layer), UPWINO
+ *         upwino_wgrad_kernel<NCI>
+ *     [4] units: 2 x 32-pixel tiles (direct) or chunks of 8 tiles / 16 pixels (wino / upwino)     [5] units per workgroup
+ *     [6] nslots = partial slabs = grid.x     [7] channel groups = grid.y     [8] floats per slab     [9] ws_elems = [6] x [8]
+ * all 0 where the status is not TGSR_OK.  Each *_ws_elems below is "plan, then ws_elems" for operands of any alignment (the
+ * workspace does not depend on it): 0 for every shape its launcher refuses.
  */
+#define TGSR_WGRAD_DIRECT 0
+#define TGSR_WGRAD_WINO 1
+#define TGSR_WGRAD_UPWINO 2
+#define TGSR_WGRAD_FAMILY_DIRECT 0
+#define TGSR_WGRAD_FAMILY_WINO 1
+#define TGSR_WGRAD_FAMILY_WINO_DMA 2
+#define TGSR_WGRAD_FAMILY_UPWINO 3
+#define TGSR_WGRAD_PLAN_FIELDS 10
+int tgsr_conv3x3_wgrad_plan(int kind, const float* grad_out, const float* x, int64_t x_bstride, int B, int Cin, int H, int W,
+                            int Cout, int upsample, int64_t* out);
 int64_t tgsr_conv3x3_wgrad_ws_elems(int B, int Cin, int Cout, int H, int W, int upsample);
 int tgsr_conv3x3_wgrad(const float* grad_out, const float* x, int64_t x_bstride, int B, int Cin, int H, int W, int Cout,
                        int upsample, float* ws, float* dw, void* stream);
@@ -815,7 +840,7 @@ int tgsr_conv3x3_wgrad(const float* grad_out, const float* x, int64_t x_bstride,
  * form: dU'[p] = sum over LOW-resolution pixels of dM[p] (x) V[p] for the 9 positions, then dW = G'^T dU' G' - 4x fewer
  * multiplies than the direct form.  grad_out [B][Cout][2H][2W] dense (8-byte aligned), x [B][Cin][H][W] with batch
  * stride; Cout % 64 == 0, Cin % 32 == 0.  ws: tgsr_upwino_wgrad_ws_elems floats (per-workgroup partial slabs, summed
- * in a fixed order).  dw [Cout][Cin][3][3].
+ * in a fixed order; 0 for a shape the launcher refuses: plan, then ws_elems).  dw [Cout][Cin][3][3].
  */
 int64_t tgsr_upwino_wgrad_ws_elems(int B, int Cin, int Cout, int H, int W);
 int tgsr_upwino_wgrad(const float* grad_out, const float* x, int64_t x_bstride, int B, int Cin, int H, int W, int Cout,
@@ -824,8 +849,9 @@ int tgsr_upwino_wgrad(const float* grad_out, const float* x, int64_t x_bstride, 
 /*
  * Weight gradient of the plain conv3x3 (upsample = 0) in the Winograd F(2x2,3x3) domain: dU[p] = sum over 2x2 output
  * tiles of dM[p] (x) V[p] for the 16 positions, then dW = G^T dU G - 2.25x fewer multiplies than tgsr_conv3x3_wgrad.
- * grad_out [B][Cout][H][W] dense, x [B][Cin][H][W] with batch stride; Cout % 64 == 0, Cin % 32 == 0.
- * ws: tgsr_wino_wgrad_ws_elems floats (per-workgroup partial slabs, summed in a fixed order).  dw [Cout][Cin][3][3].
+ * grad_out [B][Cout][H][W] dense, x [B][Cin][H][W] with batch stride; Cout % 32 == 0, Cin % 32 == 0.
+ * ws: tgsr_wino_wgrad_ws_elems floats (per-workgroup partial slabs, summed in a fixed order; 0 for a shape the launcher
+ * refuses: plan, then ws_elems).  dw [Cout][Cin][3][3].
  */
 int64_t tgsr_wino_wgrad_ws_elems(int B, int Cin, int Cout, int H, int W);
 int tgsr_wino_wgrad(const float* grad_out, const float* x, int64_t x_bstride, int B, int Cin, int H, int W, int Cout,
@@ -845,7 +871,16 @@ int tgsr_word_attention_bwd(const float* h, int64_t h_bstride, const float* src,
  * Backward of tgsr_conv_to3_fwd.  g = dy * (1 - t^2), t = out - alpha*addend for act = TGSR_ACT_TANH_AXPY (out = the
  * forward output), g = dy otherwise.  dx (may be NULL) [B][Cin][H][W] dense needs w; dw (may be NULL) [3][Cin][K][K]
  * needs x and ws = tgsr_conv_to3_bwd_ws_elems(...) floats.  d(addend) = alpha * dy is left to the caller.
+ * TGSR_EUNSUPPORTED: K not in {3, 5}, Cin > 64.
+ * tgsr_conv_to3_bwd_plan is the function the launcher plans the weight gradient with (host arithmetic): it returns the
+ * launcher's status for these sizes and fills out[TGSR_TO3_BWD_PLAN_FIELDS] (may be NULL): [0] 1: conv_to3_wgrad_mfma_kernel<K,
+ * TANH, Cin / 16> (W % 16 == 0, Cin % 16 == 0), 0: conv_to3_wgrad_kernel<K, TANH>; [1] rows per wave of the MFMA tile (4 [1] x 64
+ * pixels per workgroup: the largest of 8, 4, 2, 1 that gives >= 1024 workgroups; 1 for the other kernel's 16 x 64 tile); [2] slabs
+ * = workgroups; [3] ws_elems = [2] x 3 Cin K K - all 0 where the status is not TGSR_OK.  tgsr_conv_to3_bwd_ws_elems is "plan,
+ * then ws_elems": 0 for every shape the launcher refuses.
  */
+#define TGSR_TO3_BWD_PLAN_FIELDS 4
+int tgsr_conv_to3_bwd_plan(int B, int Cin, int H, int W, int K, int64_t* out);
 int64_t tgsr_conv_to3_bwd_ws_elems(int B, int Cin, int H, int W, int K);
 int tgsr_conv_to3_bwd(const float* dy, const float* out, const float* addend, float alpha, const float* x,
                       int64_t x_bstride, const float* w, int B, int Cin, int H, int W, int K, int act, float* dx,

@@ -13,13 +13,14 @@ reference (F.conv2d / F.batch_norm in double under autograd, repeat_interleave f
 workspace holding a finite constant instead of NaN must give the same bits.
 
 TABLE below has one row per (entry point, kernel instance), the dispatch condition copied from the extern "C" launcher; a test
-re-evaluates that condition (plan_of / the public planners *_ws_elems, tgsr_bn_train_nsplit) and asserts the row's instance is the
+re-evaluates that condition (plan_of / the public planners *_ws_elems, tgsr_conv3x3_wgrad_plan, tgsr_bn_train_nsplit) and asserts the row's instance is the
 one its case reaches.  Shapes are the smallest at which the kernel can still go wrong: B = 1, odd H, W no multiple of the tile, Cin
 = 20, several tiles per workgroup with a short last one (asserted from the planner: 1 < nslots < units).
 
 Weight gradients additionally carry the project's ratio bound (tests/test_hip_parity_margin.py): the kernel's mean distance from
 fp64 against the distance of torch's CPU fp32 gradient from the same fp64, R_DIRECT / R_WINO below.
 """
+import ctypes
 import functools
 
 import numpy as np
@@ -61,8 +62,8 @@ def _b(B, C, H, W, act, res=False, run=True, nbt=True, oextra=0, rextra=0):
 
 DIRECT, WINO, UPWINO, TO3, BNF = ("tgsr_conv3x3_wgrad", "tgsr_wino_wgrad", "tgsr_upwino_wgrad", "tgsr_conv_to3_bwd",
                                   "tgsr_bn_train_fwd / tgsr_bn_train_bwd")
-_D = "conv3x3_wgrad_kernel<%s>"          # <NCOB, NCIB, UP>: cb = Cout / 32, ib = ceil(Cin / 32) (wgrad_plan)
-_M = "conv_to3_wgrad_mfma_kernel<%s>"    # <K, TANH, NCG = Cin / 16>: W % 16 == 0 and Cin in {16, 32, 48, 64} (to3_wgrad_mfma_ok)
+_D = "conv3x3_wgrad_kernel<%s>"          # <NCOB, NCIB, UP>: cb = Cout / 32, ib = ceil(Cin / 32) (wgrad_plan_direct)
+_M = "conv_to3_wgrad_mfma_kernel<%s>"    # <K, TANH, NCG = Cin / 16>: W % 16 == 0 and Cin in {16, 32, 48, 64} (wgrad_plan_to3)
 _F = "conv_to3_wgrad_kernel<%s>"         # <K, TANH>: otherwise
 TABLE = [
     # entry point, kernel instance, dispatch condition, case (None: not covered, the condition names the knob)
@@ -82,7 +83,7 @@ TABLE = [
     (DIRECT, _D % "1,1,false", "... Cin = 20 (CinPad = 32), Cout = 96 (cb = 3), odd x_bstride", _c(2, 20, 96, 5, 37, xextra=3)),
     (DIRECT, _D % "1,1,true", "... Cin = 20, Cout = 96, upsample = 1", _c(1, 20, 96, 3, 19, up=1)),
     (DIRECT, "every instance at another split", "TGSR_WGRAD_SPLIT_PCT (read once per process): not covered", None),
-    # wino_wgrad_kernel<NCI, NCOB>; nci = 2 where Cin % 64 == 0 and the plan did not choose the 64 x 32 tile (wwgrad_plan)
+    # wino_wgrad_kernel<NCI, NCOB>; nci = 2 where Cin % 64 == 0 and the plan did not choose the 64 x 32 tile (wgrad_plan_wino)
     (WINO, "wino_wgrad_kernel<1,1>", "Cin % 64 != 0, Cout % 64 != 0", _c(2, 32, 32, 5, 37, xextra=8)),
     (WINO, "wino_wgrad_kernel<1,1>", "... 68 workgroups of two chunks over 135", _c(3, 32, 32, 9, 138, multi=True)),
     (WINO, "wino_wgrad_kernel<1,2>", "Cin % 64 != 0, Cout % 64 == 0", _c(1, 32, 64, 5, 37)),
@@ -105,7 +106,7 @@ TABLE = [
     (UPWINO, "upwino_wgrad_kernel<2>", "Cin % 64 == 0", _c(1, 64, 64, 3, 19, up=1)),
     (UPWINO, "upwino_wgrad_kernel<2>", "Cin % 64 == 0, two co groups", _c(2, 64, 128, 5, 37, up=1, xextra=8)),
     (UPWINO, "every instance at another split", "TGSR_WGRAD_SPLIT_PCT: not covered", None),
-    # conv_to3: dgrad<K, TANH> whenever dx is asked for; the weight gradient on the matrix cores where to3_wgrad_mfma_ok
+    # conv_to3: dgrad<K, TANH> whenever dx is asked for; the weight gradient on the matrix cores where wgrad_plan_to3 says mfma
     (TO3, "conv_to3_dgrad_kernel<3,false> + " + _M % "3,false,1", "K = 3, act = 0, Cin = 16, W % 16 == 0", _t(2, 16, 7, 48, 3, 0)),
     (TO3, "conv_to3_dgrad_kernel<3,false> + " + _M % "3,false,2", "... Cin = 32", _t(1, 32, 7, 48, 3, 0, xextra=8)),
     (TO3, "conv_to3_dgrad_kernel<3,false> + " + _M % "3,false,3", "... Cin = 48, two column tiles", _t(1, 48, 5, 80, 3, 0)),
@@ -244,6 +245,38 @@ def to3_plan(c):
         slabs = B * tx * ((H + 3) // 4)
     if c["dw"]:
         inst.append(("conv_to3_wgrad_mfma_kernel<%s,%d>" % (kt, Cin // 16)) if mfma else "conv_to3_wgrad_kernel<%s>" % kt)
+    return " + ".join(inst), slabs
+
+
+# The same two answers from the library: tgsr_conv3x3_wgrad_plan / tgsr_conv_to3_bwd_plan are the functions the launchers plan with
+WGRAD_KIND = {DIRECT: 0, WINO: 1, UPWINO: 2}          # TGSR_WGRAD_DIRECT, _WINO, _UPWINO
+
+
+def exported_plan(entry, c, g_addr=0, x_addr=0, xbs=0):
+    """plan_of's fields as tgsr_conv3x3_wgrad_plan states them for operands at these addresses"""
+    M, L = _lib()
+    out = (ctypes.c_int64 * M.WGRAD_PLAN_FIELDS)()
+    rc = L.tgsr_conv3x3_wgrad_plan(WGRAD_KIND[entry], ctypes.c_void_p(g_addr), ctypes.c_void_p(x_addr), xbs, c["B"], c["Cin"],
+                                   c["H"], c["W"], c["Cout"], c["up"], out)
+    assert rc == M.OK, rc
+    fam, t0, t1, t2, units, per, nslots, _groups, slab, ws = out
+    fmt = M.WGRAD_FAMILIES[fam]
+    inst = fmt % ((t0, t1, "true" if t2 else "false") if "%s" in fmt else (t0, t1)[:fmt.count("%d")])
+    assert ws == nslots * slab
+    return dict(instance=inst, slab=slab, units=units, per=per, nslots=nslots)
+
+
+def exported_to3_plan(c):
+    """to3_plan's answers as tgsr_conv_to3_bwd_plan states them (rows per wave: 1 at every case of the table)"""
+    M, L = _lib()
+    out = (ctypes.c_int64 * M.TO3_BWD_PLAN_FIELDS)()
+    assert L.tgsr_conv_to3_bwd_plan(c["B"], c["Cin"], c["H"], c["W"], c["K"], out) == M.OK
+    mfma, rpw, slabs, ws = out
+    assert ws == slabs * 3 * c["Cin"] * c["K"] ** 2 and rpw == 1
+    kt = "%d,%s" % (c["K"], "true" if c["act"] else "false")
+    inst = ["conv_to3_dgrad_kernel<%s>" % kt] if c["dx"] else []
+    if c["dw"]:
+        inst.append(("conv_to3_wgrad_mfma_kernel<%s,%d>" % (kt, c["Cin"] // 16)) if mfma else "conv_to3_wgrad_kernel<%s>" % kt)
     return " + ".join(inst), slabs
 
 
@@ -456,6 +489,19 @@ def test_upwino_wgrad_refuses_a_grad_out_that_is_not_8_byte_aligned():
     assert gr.address % 8 == 4
     assert _call_wgrad(L, UPWINO, c, gr, xr, xbs, ws, dw) == M.EUNSUPPORTED
     a.check()          # neither the workspace nor dw was touched
+
+
+def test_ops_raise_on_a_shape_the_launchers_refuse():
+    """An empty batch on each of the three routes, and a 4x4 image head: TgsrError from check(), the process lives."""
+    from tgsr_amd import ops
+    M, _L = _lib()
+    for Cin, Cout, up in ((20, 32, False), (32, 32, False), (32, 64, True)):
+        s = 2 if up else 1
+        with pytest.raises(M.TgsrError):
+            ops.conv3x3_wgrad(torch.empty(0, Cout, 8 * s, 8 * s, device=DEV), torch.empty(0, Cin, 8, 8, device=DEV), up)
+    x, w, dy = torch.randn(2, 32, 8, 8, device=DEV), torch.randn(3, 32, 4, 4, device=DEV), torch.randn(2, 3, 8, 8, device=DEV)
+    with pytest.raises(M.TgsrError):
+        ops.conv_to3_bwd(dy, None, None, 0.0, x, w, False)
 
 
 # ----------------------------------------------------------------------------------------------------------------------------

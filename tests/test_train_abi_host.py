@@ -2,8 +2,9 @@
 
   * the arena's own arithmetic (tests/arena.py on a CPU buffer): offsets, alignment, gaps, and that check() trips on a written
     guard word, a written gap word, a written input and an unwritten output word;
-  * the instance table against the library's own planners (*_ws_elems and tgsr_bn_train_nsplit are host functions): every row's
-    case reaches the instance the row names, and the `multi` cases have 1 < nslots < units;
+  * the instance table against the library's own planners (*_ws_elems, tgsr_conv3x3_wgrad_plan, tgsr_conv_to3_bwd_plan and
+    tgsr_bn_train_nsplit are host functions): every row's case reaches the instance the row names, the exported plan equals the
+    restated one, and the `multi` cases have 1 < nslots < units;
   * tolerance discrimination, once per case: the fp64 reference gradient, built again with one border pixel (last row, last
     column - the pixel a ragged-tile bug would drop) of one sample's grad_out zeroed, must differ from the first by MORE than the
     test's tolerance in at least one element.  A tolerance that cannot tell a dropped pixel from rounding hides failures; a case
@@ -136,6 +137,26 @@ def test_weight_gradient_rows_reach_their_instance(row):
     assert x.shape[1] * dy.numel() * 9 <= 2e9, "the fp64 reference of a case stays within about 2e9 multiply-adds"
 
 
+@pytest.mark.parametrize("row", T._rows(T.DIRECT, T.WINO, T.UPWINO), ids=T.row_id)
+def test_the_exported_planner_names_what_the_restated_plan_names(row):
+    """tgsr_conv3x3_wgrad_plan - the function the launcher plans with - against plan_of: instance, units, units per workgroup, nslots
+    and slab; the Winograd rows at operand addresses 0, 4 and 8 bytes off 16-byte alignment, both sides of the DMA predicate."""
+    entry, instance, _cond, c = row
+    xbs = (c["Cin"] + c["xextra"]) * c["H"] * c["W"] + c["xpad"]
+    assert T.exported_plan(entry, c, 4096, 4096, xbs) == T.plan_of(entry, c, 4096, 4096, xbs)
+    assert T.exported_plan(entry, c, 4096, 4096, xbs)["instance"] == instance
+    if entry == T.WINO:
+        seen = set()
+        for g_off in (0, 4, 8):
+            for x_off in (0, 4, 8):
+                got = T.exported_plan(entry, c, 4096 + g_off, 4096 + x_off, xbs)
+                assert got == T.plan_of(entry, c, 4096 + g_off, 4096 + x_off, xbs), (g_off, x_off)
+                assert ("dma" not in got["instance"]) or (g_off, x_off) == (0, 0)
+                seen.add(got["instance"])
+        if "dma" in instance:
+            assert len(seen) == 2 and T.exported_plan(entry, c, 4096, 4096, xbs + 2)["instance"] in seen - {instance}
+
+
 def test_the_table_accounts_for_every_instance():
     inst = " ".join(r[1] for r in T.TABLE if r[3] is not None)
     for ncob in (4, 2, 1):
@@ -173,6 +194,7 @@ def test_conv_to3_rows_reach_their_instance(row):
     inst, slabs = T.to3_plan(c)
     assert inst == instance
     assert _L().tgsr_conv_to3_bwd_ws_elems(c["B"], c["Cin"], c["H"], c["W"], c["K"]) == slabs * 3 * c["Cin"] * c["K"] ** 2
+    assert T.exported_to3_plan(c) == (inst, slabs)                   # tgsr_conv_to3_bwd_plan: the function the launcher plans with
 
 
 @pytest.mark.parametrize("row", T._rows(T.BNF), ids=T.row_id)

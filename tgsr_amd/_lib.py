@@ -17,6 +17,11 @@ EPI_AFFINE, EPI_AFFINE_GLU = 0, 1
 ACT_NONE, ACT_TANH_AXPY, ACT_IDENT_AXPY = 0, 1, 2
 TO3_FORM_MFMA, TO3_FORM_PIPE, TO3_FORM_VEC4, TO3_FORM_SCALAR = 0, 1, 2, 3
 DT_BF16, DT_F16 = 1, 2
+WGRAD_DIRECT, WGRAD_WINO, WGRAD_UPWINO = 0, 1, 2                    # `kind` of tgsr_conv3x3_wgrad_plan
+# the kernel families its out[0] names (TGSR_WGRAD_FAMILY_*), each with the template integers of out[1..3] it takes
+WGRAD_FAMILIES = ("conv3x3_wgrad_kernel<%d,%d,%s>", "wino_wgrad_kernel<%d,%d>", "wino_wgrad_dma_kernel<%d>", "upwino_wgrad_kernel<%d>")
+WGRAD_PLAN_FIELDS, WGRAD_PLAN_WS = 10, 9                            # int64 fields of its `out`; the field that holds ws_elems
+TO3_BWD_PLAN_FIELDS, TO3_BWD_PLAN_WS = 4, 3                         # ... of tgsr_conv_to3_bwd_plan
 
 _vp, _i, _i64, _f, _d = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_float, ctypes.c_double
 
@@ -154,6 +159,7 @@ SIGNATURES = {
     "tgsr_rgb_to_y_u8": (_i, [_vp, _i, _i, _i, _vp, _vp]),
     "tgsr_tile_gather": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
     "tgsr_tile_stitch": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _i, _i, _i, _vp]),
+    "tgsr_conv3x3_wgrad_plan": (_i, [_i, _vp, _vp, _i64, _i, _i, _i, _i, _i, _i, _vp]),
     "tgsr_conv3x3_wgrad_ws_elems": (_i64, [_i, _i, _i, _i, _i, _i]),
     "tgsr_conv3x3_wgrad": (_i, [_vp, _vp, _i64, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     "tgsr_upwino_wgrad_ws_elems": (_i64, [_i, _i, _i, _i, _i]),
@@ -162,6 +168,7 @@ SIGNATURES = {
     "tgsr_wino_wgrad": (_i, [_vp, _vp, _i64, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     "tgsr_word_attention_bwd_chunks": (_i, [_i]),
     "tgsr_word_attention_bwd": (_i, [_vp, _i64, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "tgsr_conv_to3_bwd_plan": (_i, [_i, _i, _i, _i, _i, _vp]),
     "tgsr_conv_to3_bwd_ws_elems": (_i64, [_i, _i, _i, _i, _i]),
     "tgsr_conv_to3_bwd": (_i, [_vp, _vp, _vp, _f, _vp, _i64, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
     # reduced-precision inference path (lp images: zero-bordered channels-last bf16 / f16)

@@ -85,15 +85,4 @@ __device__ __forceinline__ void gemm_tile_stats(const f32x16 (&acc)[2][2], int m
   }
 }
 
-// Experiment knob: TGSR_WGRAD_SPLIT_PCT scales how many partial slabs the split weight-gradient kernels produce
-// (100 = the launchers' own choice).
-inline int wgrad_split_pct() {
-  static int pct = [] {
-    const char* e = getenv("TGSR_WGRAD_SPLIT_PCT");
-    const int v = e ? atoi(e) : 100;
-    return v < 1 ? 100 : v;
-  }();
-  return pct;
-}
-
 }  // namespace tgsr

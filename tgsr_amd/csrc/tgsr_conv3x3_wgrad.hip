@@ -11,7 +11,7 @@
 //   * each workgroup walks a contiguous run of 2x32-pixel tiles, keeps its accumulators in registers, and writes ONE
 //     partial slab [tap][co][ci] at the end; a second kernel sums the slabs in a fixed order (bitwise reproducible,
 //     no float atomics) into the torch layout [co][ci][3][3].
-#include "tgsr_common.h"
+#include "tgsr_wgrad_plan.h"
 
 namespace tgsr {
 
@@ -137,66 +137,47 @@ __global__ __launch_bounds__(256) void wgrad_reduce_kernel(const float* __restri
 }
 
 template <int NCOB, int NCIB>
-static int launch_wgrad(const WgradArgs& a, int nslots, int groups, bool up, hipStream_t s) {
-  dim3 grid(nslots, groups), block(64 * NCOB * NCIB);
-  if (up) hipLaunchKernelGGL((conv3x3_wgrad_kernel<NCOB, NCIB, true>), grid, block, 0, s, a);
-  else hipLaunchKernelGGL((conv3x3_wgrad_kernel<NCOB, NCIB, false>), grid, block, 0, s, a);
-  return note_launch(hipGetLastError(), "conv3x3_wgrad_kernel");
+static void launch_wgrad(const WgradArgs& a, const WgradPlan& p, hipStream_t s) {
+  if (p.t[2]) hipLaunchKernelGGL((conv3x3_wgrad_kernel<NCOB, NCIB, true>), p.grid, p.block, 0, s, a);
+  else hipLaunchKernelGGL((conv3x3_wgrad_kernel<NCOB, NCIB, false>), p.grid, p.block, 0, s, a);
 }
 
 }  // namespace tgsr
 
 using namespace tgsr;
 
-static void wgrad_plan(int B, int Cin, int Cout, int Ho, int Wo, int* ncob, int* ncib, int* groups, int* gi,
-                       int* nslots, int* tiles_per_wg, int* ntiles, int* cinpad) {
-  const int cb = (Cout + 31) / 32, ib = (Cin + 31) / 32;
-  *ncob = cb % 4 == 0 ? 4 : (cb % 2 == 0 ? 2 : 1);
-  *ncib = ib % 2 == 0 ? 2 : 1;
-  *gi = ib / *ncib;
-  *groups = (cb / *ncob) * *gi;
-  *cinpad = ib * 32;
-  *ntiles = B * ((Ho + 1) / 2) * ((Wo + 31) / 32);
-  // one partial slab per workgroup: ~256 CUs x 8 waves of workgroups in flight keeps the chip full while the slabs
-  // (nslots x |dW|) stay ~75 MB for every layer shape
-  int want = 2048 / (*ncob * *ncib) / *groups;
-  want = want * wgrad_split_pct() / 100;
-  if (want < 1) want = 1;
-  if (want > *ntiles) want = *ntiles;
-  *tiles_per_wg = (*ntiles + want - 1) / want;
-  *nslots = (*ntiles + *tiles_per_wg - 1) / *tiles_per_wg;
-}
+extern "C" int64_t tgsr_conv3x3_wgrad_ws_elems(int B, int Cin, int Cout, int H, int W, int upsample) { return wgrad_plan_direct(B, Cin, H, W, Cout, upsample).ws_elems; }
 
-extern "C" int64_t tgsr_conv3x3_wgrad_ws_elems(int B, int Cin, int Cout, int H, int W, int upsample) {
-  int ncob, ncib, groups, gi, nslots, tpw, ntiles, cinpad;
-  const int Ho = upsample ? 2 * H : H, Wo = upsample ? 2 * W : W;
-  wgrad_plan(B, Cin, Cout, Ho, Wo, &ncob, &ncib, &groups, &gi, &nslots, &tpw, &ntiles, &cinpad);
-  return (int64_t)nslots * 9 * Cout * cinpad;
+extern "C" int tgsr_conv3x3_wgrad_plan(int kind, const float* grad_out, const float* x, int64_t x_bstride, int B, int Cin, int H,
+                                       int W, int Cout, int upsample, int64_t* out) {
+  const WgradPlan p = kind == TGSR_WGRAD_WINO     ? wgrad_plan_wino(grad_out, x, x_bstride, B, Cin, H, W, Cout)
+                      : kind == TGSR_WGRAD_UPWINO ? wgrad_plan_upwino(grad_out, B, Cin, H, W, Cout)
+                      : kind == TGSR_WGRAD_DIRECT ? wgrad_plan_direct(B, Cin, H, W, Cout, upsample)
+                                                  : WgradPlan{TGSR_EINVAL};
+  const int64_t f[TGSR_WGRAD_PLAN_FIELDS] = {p.family, p.t[0], p.t[1], p.t[2], p.units, p.per_wg, p.nslots, p.groups, p.slab, p.ws_elems};
+  for (int i = 0; out && i < TGSR_WGRAD_PLAN_FIELDS; ++i) out[i] = f[i];
+  return p.status;
 }
 
 extern "C" int tgsr_conv3x3_wgrad(const float* grad_out, const float* x, int64_t x_bstride, int B, int Cin, int H,
                                   int W, int Cout, int upsample, float* ws, float* dw, void* stream) {
-  if (!grad_out || !x || !ws || !dw || B < 1 || Cin < 1 || Cout < 1 || H < 1 || W < 1) return TGSR_EINVAL;
-  if (Cout % 32 != 0) return TGSR_EUNSUPPORTED;
+  if (!grad_out || !x || !ws || !dw) return TGSR_EINVAL;
+  const WgradPlan p = wgrad_plan_direct(B, Cin, H, W, Cout, upsample);
+  if (p.status != TGSR_OK) return p.status;
   WgradArgs a;
-  a.g = grad_out; a.x = x; a.xbs = x_bstride; a.B = B; a.Cin = Cin; a.Cout = Cout; a.H = H; a.W = W;
-  a.Ho = upsample ? 2 * H : H; a.Wo = upsample ? 2 * W : W;
-  int ncob, ncib, groups, gi, nslots, tpw, ntiles, cinpad;
-  wgrad_plan(B, Cin, Cout, a.Ho, a.Wo, &ncob, &ncib, &groups, &gi, &nslots, &tpw, &ntiles, &cinpad);
-  a.tiles_x = (a.Wo + 31) / 32; a.tiles_y = (a.Ho + 1) / 2; a.ntiles = ntiles; a.tiles_per_wg = tpw;
-  a.cgroups_i = gi; a.partial = ws; a.CinPad = cinpad;
+  a.g = grad_out; a.x = x; a.xbs = x_bstride; a.B = B; a.Cin = Cin; a.Cout = Cout; a.H = H; a.W = W; a.Ho = H << p.t[2]; a.Wo = W << p.t[2];
+  a.tiles_x = p.tiles_x; a.tiles_y = p.tiles_y; a.ntiles = p.units; a.tiles_per_wg = p.per_wg; a.cgroups_i = p.cgroups_i; a.CinPad = p.CinPad;
+  a.partial = ws;
   hipStream_t s = as_stream(stream);
-  const bool up = upsample != 0;
-  int rc;
-  if (ncob == 4 && ncib == 2) rc = launch_wgrad<4, 2>(a, nslots, groups, up, s);
-  else if (ncob == 4) rc = launch_wgrad<4, 1>(a, nslots, groups, up, s);
-  else if (ncob == 2 && ncib == 2) rc = launch_wgrad<2, 2>(a, nslots, groups, up, s);
-  else if (ncob == 2) rc = launch_wgrad<2, 1>(a, nslots, groups, up, s);
-  else if (ncib == 2) rc = launch_wgrad<1, 2>(a, nslots, groups, up, s);
-  else rc = launch_wgrad<1, 1>(a, nslots, groups, up, s);
-  if (rc) return rc;
-  const int64_t n = (int64_t)9 * Cout * cinpad;
-  hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)((n + 31) / 32)), dim3(256), 0, s, ws, nslots, Cout, Cin,
-                     cinpad, dw);
+  switch (p.t[0] * 10 + p.t[1]) {           // <NCOB, NCIB>
+    case 42: launch_wgrad<4, 2>(a, p, s); break;
+    case 41: launch_wgrad<4, 1>(a, p, s); break;
+    case 22: launch_wgrad<2, 2>(a, p, s); break;
+    case 21: launch_wgrad<2, 1>(a, p, s); break;
+    case 12: launch_wgrad<1, 2>(a, p, s); break;
+    default: launch_wgrad<1, 1>(a, p, s); break;
+  }
+  if (const int rc = note_launch(hipGetLastError(), "conv3x3_wgrad_kernel")) return rc;
+  hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)((p.slab + 31) / 32)), dim3(256), 0, s, ws, p.nslots, Cout, Cin, p.CinPad, dw);
   return note_launch(hipGetLastError(), "wgrad_reduce_kernel");
 }

@@ -6,7 +6,7 @@
 // Both kernels tile 16 x 64 pixels like the forward.  dgrad: thread = 4 pixels x 16 input channels per pass, g tile
 // (3 channels + halo) in LDS, weights as scalar loads.  wgrad: thread = (channel, ky, group of 4 rows) with a sliding
 // 5-wide window along x, 15 accumulators (3 co x K kx); partial slabs per workgroup, summed in a fixed order.
-#include "tgsr_common.h"
+#include "tgsr_wgrad_plan.h"
 
 namespace tgsr {
 
@@ -315,15 +315,6 @@ __global__ __launch_bounds__(256) void conv_to3_wgrad_mfma_kernel(To3BwdArgs a, 
   }
 }
 
-// rows per wave of the MFMA weight-gradient tile: the largest of 8, 4, 2, 1 that still gives >= 1024 workgroups
-static int to3_wgrad_rpw(int B, int H, int W) {
-  const int tx = (W + 63) / 64;
-  for (int rpw = 8; rpw > 1; rpw >>= 1)
-    if ((int64_t)B * tx * ((H + 4 * rpw - 1) / (4 * rpw)) >= 1024) return rpw;
-  return 1;
-}
-static bool to3_wgrad_mfma_ok(int Cin, int W) { return W % 16 == 0 && (Cin == 16 || Cin == 32 || Cin == 48 || Cin == 64); }
-
 // out[i] = sum_slot part[slot][i]: block = 32 outputs x 32 slot lanes, combined in a fixed order (reproducible)
 __global__ __launch_bounds__(1024) void to3_wgrad_reduce_kernel(const float* __restrict__ part, int nslots, int n,
                                                                 float* __restrict__ dw) {
@@ -344,28 +335,18 @@ __global__ __launch_bounds__(1024) void to3_wgrad_reduce_kernel(const float* __r
 }
 
 template <int K, bool TANH>
-static int launch_to3_bwd(To3BwdArgs a, float* dw, hipStream_t s) {
-  a.tiles_x = (a.W + 63) / 64;
-  a.tiles_y = (a.H + 15) / 16;
-  const int nwg = a.B * a.tiles_x * a.tiles_y;
-  if (a.dx) hipLaunchKernelGGL((conv_to3_dgrad_kernel<K, TANH>), dim3(nwg), dim3(256), 0, s, a);
+static int launch_to3_bwd(To3BwdArgs a, const WgradPlan& p, float* dw, hipStream_t s) {
+  if (a.dx) hipLaunchKernelGGL((conv_to3_dgrad_kernel<K, TANH>), dim3(a.B * a.tiles_x * a.tiles_y), dim3(256), 0, s, a);
   if (dw) {
-    const int n = 3 * a.Cin * K * K;
-    int nslab = nwg;
-    if (to3_wgrad_mfma_ok(a.Cin, a.W)) {
-      const int rpw = to3_wgrad_rpw(a.B, a.H, a.W);
-      a.tiles_y = (a.H + 4 * rpw - 1) / (4 * rpw);
-      nslab = a.B * a.tiles_x * a.tiles_y;
-      switch (a.Cin / 16) {
-        case 1: hipLaunchKernelGGL((conv_to3_wgrad_mfma_kernel<K, TANH, 1>), dim3(nslab), dim3(256), 0, s, a, rpw); break;
-        case 2: hipLaunchKernelGGL((conv_to3_wgrad_mfma_kernel<K, TANH, 2>), dim3(nslab), dim3(256), 0, s, a, rpw); break;
-        case 3: hipLaunchKernelGGL((conv_to3_wgrad_mfma_kernel<K, TANH, 3>), dim3(nslab), dim3(256), 0, s, a, rpw); break;
-        default: hipLaunchKernelGGL((conv_to3_wgrad_mfma_kernel<K, TANH, 4>), dim3(nslab), dim3(256), 0, s, a, rpw); break;
-      }
-    } else {
-      hipLaunchKernelGGL((conv_to3_wgrad_kernel<K, TANH>), dim3(nwg), dim3(256), 0, s, a);
+    a.tiles_y = p.tiles_y;
+    switch (p.mfma ? a.Cin / 16 : 0) {        // <K, TANH, NCG> on the matrix cores
+      case 1: hipLaunchKernelGGL((conv_to3_wgrad_mfma_kernel<K, TANH, 1>), p.grid, p.block, 0, s, a, p.rpw); break;
+      case 2: hipLaunchKernelGGL((conv_to3_wgrad_mfma_kernel<K, TANH, 2>), p.grid, p.block, 0, s, a, p.rpw); break;
+      case 3: hipLaunchKernelGGL((conv_to3_wgrad_mfma_kernel<K, TANH, 3>), p.grid, p.block, 0, s, a, p.rpw); break;
+      case 4: hipLaunchKernelGGL((conv_to3_wgrad_mfma_kernel<K, TANH, 4>), p.grid, p.block, 0, s, a, p.rpw); break;
+      default: hipLaunchKernelGGL((conv_to3_wgrad_kernel<K, TANH>), p.grid, p.block, 0, s, a); break;
     }
-    hipLaunchKernelGGL(to3_wgrad_reduce_kernel, dim3((n + 31) / 32), dim3(1024), 0, s, a.part, nslab, n, dw);
+    hipLaunchKernelGGL(to3_wgrad_reduce_kernel, dim3(((int)p.slab + 31) / 32), dim3(1024), 0, s, a.part, p.nslots, (int)p.slab, dw);
   }
   return note_launch(hipGetLastError(), "conv_to3_bwd");
 }
@@ -374,28 +355,29 @@ static int launch_to3_bwd(To3BwdArgs a, float* dw, hipStream_t s) {
 
 using namespace tgsr;
 
-extern "C" int64_t tgsr_conv_to3_bwd_ws_elems(int B, int Cin, int H, int W, int K) {
-  int64_t slabs = (int64_t)B * ((W + 63) / 64) * ((H + 15) / 16);
-  if (to3_wgrad_mfma_ok(Cin, W)) {
-    const int rpw = to3_wgrad_rpw(B, H, W);
-    slabs = (int64_t)B * ((W + 63) / 64) * ((H + 4 * rpw - 1) / (4 * rpw));
-  }
-  return slabs * 3 * Cin * K * K;
+extern "C" int64_t tgsr_conv_to3_bwd_ws_elems(int B, int Cin, int H, int W, int K) { return wgrad_plan_to3(B, Cin, H, W, K).ws_elems; }
+
+extern "C" int tgsr_conv_to3_bwd_plan(int B, int Cin, int H, int W, int K, int64_t* out) {
+  const WgradPlan p = wgrad_plan_to3(B, Cin, H, W, K);
+  const int64_t f[TGSR_TO3_BWD_PLAN_FIELDS] = {p.mfma, p.rpw, p.nslots, p.ws_elems};
+  for (int i = 0; out && i < TGSR_TO3_BWD_PLAN_FIELDS; ++i) out[i] = f[i];
+  return p.status;
 }
 
 extern "C" int tgsr_conv_to3_bwd(const float* dy, const float* out, const float* addend, float alpha, const float* x,
                                  int64_t x_bstride, const float* w, int B, int Cin, int H, int W, int K, int act,
                                  float* dx, float* ws, float* dw, void* stream) {
-  if (!dy || B < 1 || Cin < 1 || H < 1 || W < 1) return TGSR_EINVAL;
-  if ((K != 3 && K != 5) || Cin > 64) return TGSR_EUNSUPPORTED;
+  if (!dy) return TGSR_EINVAL;
+  const WgradPlan p = wgrad_plan_to3(B, Cin, H, W, K);
+  if (p.status != TGSR_OK) return p.status;
   if (act == TGSR_ACT_TANH_AXPY && !out) return TGSR_EINVAL;
   if (dx && !w) return TGSR_EINVAL;
   if (dw && (!x || !ws)) return TGSR_EINVAL;
   To3BwdArgs a;
   a.dy = dy; a.out = out; a.addend = addend; a.alpha = alpha; a.x = x; a.xbs = x_bstride; a.w = w;
-  a.B = B; a.Cin = Cin; a.H = H; a.W = W; a.tiles_x = a.tiles_y = 0; a.dx = dx; a.part = ws;
+  a.B = B; a.Cin = Cin; a.H = H; a.W = W; a.tiles_x = p.tiles_x; a.tiles_y = p.dgrad_tiles_y; a.dx = dx; a.part = ws;
   hipStream_t s = as_stream(stream);
   const bool th = act == TGSR_ACT_TANH_AXPY;
-  if (K == 3) return th ? launch_to3_bwd<3, true>(a, dw, s) : launch_to3_bwd<3, false>(a, dw, s);
-  return th ? launch_to3_bwd<5, true>(a, dw, s) : launch_to3_bwd<5, false>(a, dw, s);
+  if (K == 3) return th ? launch_to3_bwd<3, true>(a, p, dw, s) : launch_to3_bwd<3, false>(a, p, dw, s);
+  return th ? launch_to3_bwd<5, true>(a, p, dw, s) : launch_to3_bwd<5, false>(a, p, dw, s);
 }

@@ -12,7 +12,7 @@
 // [p][channel][16 px] (pitch 17: lanes = channels hit distinct banks), then 9 x 8 MFMAs per wave consume the chunk.
 // One partial slab [9][Cout][Cin] per workgroup, summed in a fixed order by upwino_wgrad_reduce_kernel, which also
 // applies G'^T . G' and writes the torch layout [Cout][Cin][3][3] (bitwise reproducible, no float atomics).
-#include "tgsr_common.h"
+#include "tgsr_wgrad_plan.h"
 
 namespace tgsr {
 
@@ -25,7 +25,7 @@ struct UpWgradArgs {
   float* partial;     // [nslots][9][Cout][Cin]
 };
 
-constexpr int kUWT = 16, kUWP = kUWT + 1;   // pixels per chunk, LDS pitch
+constexpr int kUWP = kUWT + 1;   // LDS pitch of a chunk of kUWT pixels
 
 template <int NCI>
 __global__ __launch_bounds__(128 * NCI) void upwino_wgrad_kernel(UpWgradArgs a) {
@@ -231,46 +231,20 @@ __global__ __launch_bounds__(256) void upwino_wgrad_reduce_kernel(const float* _
 
 using namespace tgsr;
 
-static void upwgrad_plan(int B, int Cin, int Cout, int H, int W, int* nci, int* groups, int* gi, int* nslots, int* cpw,
-                         int* nchunks) {
-  *nci = (Cin % 64 == 0) ? 2 : 1;
-  *gi = Cin / (32 * *nci);
-  *groups = (Cout / 64) * *gi;
-  *nchunks = B * H * ((W + kUWT - 1) / kUWT);
-  int want = 512 / *groups;                  // two workgroups per CU in flight; fewer, longer K walks keep the slabs small
-  if (*nchunks <= 1024 && want >= 64) want /= 2;   // the 32 x 32 upBlocks are slab-bound (tools/exp_wgrad.py: 54 -> 41 us, 46 -> 42)
-  want = want * wgrad_split_pct() / 100;
-  if (want < 1) want = 1;
-  if (want > *nchunks) want = *nchunks;
-  *cpw = (*nchunks + want - 1) / want;
-  *nslots = (*nchunks + *cpw - 1) / *cpw;
-}
-
-extern "C" int64_t tgsr_upwino_wgrad_ws_elems(int B, int Cin, int Cout, int H, int W) {
-  if (B < 1 || H < 1 || W < 1 || Cout < 64 || Cout % 64 != 0 || Cin < 32 || Cin % 32 != 0) return 0;   // shapes tgsr_upwino_wgrad refuses
-  int nci, groups, gi, nslots, cpw, nchunks;
-  upwgrad_plan(B, Cin, Cout, H, W, &nci, &groups, &gi, &nslots, &cpw, &nchunks);
-  return (int64_t)nslots * 9 * Cout * Cin;
-}
+extern "C" int64_t tgsr_upwino_wgrad_ws_elems(int B, int Cin, int Cout, int H, int W) { return wgrad_plan_upwino(nullptr, B, Cin, H, W, Cout).ws_elems; }
 
 extern "C" int tgsr_upwino_wgrad(const float* grad_out, const float* x, int64_t x_bstride, int B, int Cin, int H, int W,
                                  int Cout, float* ws, float* dw, void* stream) {
-  if (!grad_out || !x || !ws || !dw || B < 1 || Cin < 1 || Cout < 1 || H < 1 || W < 1) return TGSR_EINVAL;
-  if (Cout % 64 != 0 || Cin % 32 != 0) return TGSR_EUNSUPPORTED;
-  if ((reinterpret_cast<uintptr_t>(grad_out) & 7) != 0) return TGSR_EUNSUPPORTED;
+  if (!grad_out || !x || !ws || !dw) return TGSR_EINVAL;
+  const WgradPlan p = wgrad_plan_upwino(grad_out, B, Cin, H, W, Cout);
+  if (p.status != TGSR_OK) return p.status;
   UpWgradArgs a;
   a.g = grad_out; a.x = x; a.xbs = x_bstride; a.B = B; a.Cin = Cin; a.Cout = Cout; a.H = H; a.W = W;
-  int nci, groups, gi, nslots, cpw, nchunks;
-  upwgrad_plan(B, Cin, Cout, H, W, &nci, &groups, &gi, &nslots, &cpw, &nchunks);
-  a.chunks_x = (W + kUWT - 1) / kUWT; a.nchunks = nchunks; a.chunks_per_wg = cpw; a.cgroups_i = gi; a.partial = ws;
+  a.chunks_x = p.chunks_x; a.nchunks = p.units; a.chunks_per_wg = p.per_wg; a.cgroups_i = p.cgroups_i; a.partial = ws;
   hipStream_t s = as_stream(stream);
-  dim3 grid(nslots, groups);
-  if (nci == 2) hipLaunchKernelGGL(upwino_wgrad_kernel<2>, grid, dim3(256), 0, s, a);
-  else hipLaunchKernelGGL(upwino_wgrad_kernel<1>, grid, dim3(128), 0, s, a);
-  int rc = note_launch(hipGetLastError(), "upwino_wgrad_kernel");
-  if (rc) return rc;
-  const int64_t n = (int64_t)Cout * Cin;
-  hipLaunchKernelGGL(upwino_wgrad_reduce_kernel, dim3((unsigned)((n + 31) / 32)), dim3(256), 0, s, ws, nslots, Cout, Cin,
-                     dw);
+  if (p.t[0] == 2) hipLaunchKernelGGL(upwino_wgrad_kernel<2>, p.grid, p.block, 0, s, a);      // <NCI>
+  else hipLaunchKernelGGL(upwino_wgrad_kernel<1>, p.grid, p.block, 0, s, a);
+  if (const int rc = note_launch(hipGetLastError(), "upwino_wgrad_kernel")) return rc;
+  hipLaunchKernelGGL(upwino_wgrad_reduce_kernel, dim3((unsigned)((p.slab / 9 + 31) / 32)), dim3(256), 0, s, ws, p.nslots, Cout, Cin, dw);
   return note_launch(hipGetLastError(), "upwino_wgrad_reduce_kernel");
 }

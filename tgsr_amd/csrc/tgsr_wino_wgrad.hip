@@ -11,7 +11,7 @@
 // straight from global memory into LDS images [p][channel][8 tiles] (pitch 9), then 8 x 4 MFMAs per wave consume the
 // chunk.  One partial slab [16][Cout][Cin] per workgroup; wino_wgrad_reduce_kernel sums the slabs in a fixed order,
 // applies G^T . G and writes the torch layout [Cout][Cin][3][3] (bitwise reproducible, no float atomics).
-#include "tgsr_common.h"
+#include "tgsr_wgrad_plan.h"
 
 namespace tgsr {
 
@@ -24,7 +24,7 @@ struct WinoWgradArgs {
   float* partial;     // [nslots][16][Cout][Cin]
 };
 
-constexpr int kWWT = 8, kWWP = kWWT + 1;    // tiles per chunk, LDS pitch
+constexpr int kWWP = kWWT + 1;    // LDS pitch of a chunk of kWWT tiles
 
 // NCOB = 32-channel co blocks per workgroup (2: Cout % 64 == 0; 1: the 32-channel layers of NetG_highweight - model.py:258-262
 // ResBlock(32), residual24 / 48 - which the direct-form kernel of tgsr_conv3x3_wgrad.hip served at 9 TFLOP/s), NCI = ci blocks.
@@ -462,73 +462,26 @@ __global__ __launch_bounds__(256) void wino_wgrad_reduce_kernel(const float* __r
 
 using namespace tgsr;
 
-// TGSR_WGRAD_TILE = 32 | 64: force the DMA-staged kernel's 64 co x 32 ci (two workgroups per CU) or 64 x 64 form on the
-// Cout % 64 == 0, Cin % 64 == 0 layers (0 / unset: by layer size, see wwgrad_plan)
-static int wgrad_tile() {
-  static const int v = [] { const char* e = getenv("TGSR_WGRAD_TILE"); return e ? atoi(e) : 0; }();
-  return v;
-}
-
-static void wwgrad_plan(int B, int Cin, int Cout, int H, int W, int* nci, int* groups, int* gi, int* nslots, int* cpw,
-                        int* nchunks, int* tiles_y, int* chunks_x) {
-  *tiles_y = (H + 1) / 2;
-  *chunks_x = ((W + 1) / 2 + kWWT - 1) / kWWT;
-  *nchunks = B * *tiles_y * *chunks_x;
-  // The 64 x 32 tile (two 4-wave workgroups per CU) measured 3-20 % faster than the 64 x 64 one on the 32^2 and 64^2 layers
-  // (<= 2 048 chunks at batch 16: 47 -> 37, 35 -> 31, 83 -> 79, 57 -> 54 us) and 3 % slower on the 128^2 ones
-  // (tools/exp_wgrad.py; TGSR_WGRAD_TILE=32 | 64 forces one of them).
-  const bool can32 = Cin % 64 == 0 && Cout % 64 == 0 && W % 4 == 0;
-  const int force = wgrad_tile();
-  const bool use32 = can32 && (force == 32 || (force == 0 && *nchunks <= 2048));
-  *nci = (Cin % 64 == 0 && !use32) ? 2 : 1;
-  *gi = Cin / (32 * *nci);
-  const int ncob = (Cout % 64 == 0) ? 2 : 1;
-  *groups = (Cout / (32 * ncob)) * *gi;
-  int want = 256 / *groups;                  // one 8-wave workgroup per CU: fewer, longer K walks keep the slabs small
-  if (use32) want = 512 / *groups;           // two 4-wave workgroups per CU
-  // the 32 x 32 layers (<= 512 chunks at batch 16) are slab-bound - 2-4 chunks of work per workgroup against a 64-KB..512-KB
-  // slab written and re-read: half the split measured 5-20 % faster there, slower everywhere else (tools/exp_wgrad.py)
-  if (*nchunks <= 512 && want >= 64) want /= 2;
-  want = want * wgrad_split_pct() / 100;
-  if (want < 1) want = 1;
-  if (want > *nchunks) want = *nchunks;
-  *cpw = (*nchunks + want - 1) / want;
-  *nslots = (*nchunks + *cpw - 1) / *cpw;
-}
-
-extern "C" int64_t tgsr_wino_wgrad_ws_elems(int B, int Cin, int Cout, int H, int W) {
-  int nci, groups, gi, nslots, cpw, nchunks, ty, cx;
-  wwgrad_plan(B, Cin, Cout, H, W, &nci, &groups, &gi, &nslots, &cpw, &nchunks, &ty, &cx);
-  return (int64_t)nslots * 16 * Cout * Cin;
-}
+extern "C" int64_t tgsr_wino_wgrad_ws_elems(int B, int Cin, int Cout, int H, int W) { return wgrad_plan_wino(nullptr, nullptr, 0, B, Cin, H, W, Cout).ws_elems; }
 
 extern "C" int tgsr_wino_wgrad(const float* grad_out, const float* x, int64_t x_bstride, int B, int Cin, int H, int W,
                                int Cout, float* ws, float* dw, void* stream) {
-  if (!grad_out || !x || !ws || !dw || B < 1 || Cin < 1 || Cout < 1 || H < 1 || W < 1) return TGSR_EINVAL;
-  if (Cout % 32 != 0 || Cin % 32 != 0) return TGSR_EUNSUPPORTED;
+  if (!grad_out || !x || !ws || !dw) return TGSR_EINVAL;
+  const WgradPlan p = wgrad_plan_wino(grad_out, x, x_bstride, B, Cin, H, W, Cout);
+  if (p.status != TGSR_OK) return p.status;
   WinoWgradArgs a;
   a.g = grad_out; a.x = x; a.xbs = x_bstride; a.B = B; a.Cin = Cin; a.Cout = Cout; a.H = H; a.W = W;
-  int nci, groups, gi, nslots, cpw, nchunks;
-  wwgrad_plan(B, Cin, Cout, H, W, &nci, &groups, &gi, &nslots, &cpw, &nchunks, &a.tiles_y, &a.chunks_x);
-  a.nchunks = nchunks; a.chunks_per_wg = cpw; a.cgroups_i = gi; a.partial = ws;
+  a.tiles_y = p.tiles_y; a.chunks_x = p.chunks_x; a.nchunks = p.units; a.chunks_per_wg = p.per_wg; a.cgroups_i = p.cgroups_i; a.partial = ws;
   hipStream_t s = as_stream(stream);
-  dim3 grid(nslots, groups);
-  const bool co64 = Cout % 64 == 0;
-  // the DMA-staged instance: aligned planes and rows (TGSR_WGRAD_DMA=0 keeps the register-fetch kernel for A/B runs)
-  static const bool dma_on = [] { const char* e = getenv("TGSR_WGRAD_DMA"); return !(e && e[0] == '0'); }();
-  const bool dma_ok = dma_on && W % 4 == 0 && ((reinterpret_cast<uintptr_t>(grad_out) | reinterpret_cast<uintptr_t>(x)) & 15) == 0 &&
-                      x_bstride % 4 == 0;
-  if (nci == 2 && co64 && dma_ok) hipLaunchKernelGGL(wino_wgrad_dma_kernel<2>, grid, dim3(512), 0, s, a);
-  else if (nci == 1 && co64 && dma_ok && Cin % 64 == 0)      // the plan chose the 64 x 32 tile for a 64-ci-multiple layer
-    hipLaunchKernelGGL(wino_wgrad_dma_kernel<1>, grid, dim3(256), 0, s, a);
-  else if (nci == 2 && co64) hipLaunchKernelGGL((wino_wgrad_kernel<2, 2>), grid, dim3(512), 0, s, a);
-  else if (nci == 2) hipLaunchKernelGGL((wino_wgrad_kernel<2, 1>), grid, dim3(256), 0, s, a);
-  else if (co64) hipLaunchKernelGGL((wino_wgrad_kernel<1, 2>), grid, dim3(256), 0, s, a);
-  else hipLaunchKernelGGL((wino_wgrad_kernel<1, 1>), grid, dim3(128), 0, s, a);
-  int rc = note_launch(hipGetLastError(), "wino_wgrad_kernel");
-  if (rc) return rc;
-  const int64_t n = (int64_t)Cout * Cin;
-  hipLaunchKernelGGL(wino_wgrad_reduce_kernel, dim3((unsigned)((n + 31) / 32)), dim3(256), 0, s, ws, nslots, Cout, Cin,
-                     dw);
+  switch (p.family * 100 + p.t[0] * 10 + p.t[1]) {      // wino_wgrad_dma_kernel<NCI> | wino_wgrad_kernel<NCI, NCOB>
+    case TGSR_WGRAD_FAMILY_WINO_DMA * 100 + 20: hipLaunchKernelGGL(wino_wgrad_dma_kernel<2>, p.grid, p.block, 0, s, a); break;
+    case TGSR_WGRAD_FAMILY_WINO_DMA * 100 + 10: hipLaunchKernelGGL(wino_wgrad_dma_kernel<1>, p.grid, p.block, 0, s, a); break;
+    case TGSR_WGRAD_FAMILY_WINO * 100 + 22: hipLaunchKernelGGL((wino_wgrad_kernel<2, 2>), p.grid, p.block, 0, s, a); break;
+    case TGSR_WGRAD_FAMILY_WINO * 100 + 21: hipLaunchKernelGGL((wino_wgrad_kernel<2, 1>), p.grid, p.block, 0, s, a); break;
+    case TGSR_WGRAD_FAMILY_WINO * 100 + 12: hipLaunchKernelGGL((wino_wgrad_kernel<1, 2>), p.grid, p.block, 0, s, a); break;
+    default: hipLaunchKernelGGL((wino_wgrad_kernel<1, 1>), p.grid, p.block, 0, s, a); break;
+  }
+  if (const int rc = note_launch(hipGetLastError(), "wino_wgrad_kernel")) return rc;
+  hipLaunchKernelGGL(wino_wgrad_reduce_kernel, dim3((unsigned)((p.slab / 16 + 31) / 32)), dim3(256), 0, s, ws, p.nslots, Cout, Cin, dw);
   return note_launch(hipGetLastError(), "wino_wgrad_reduce_kernel");
 }

@@ -1103,11 +1103,16 @@ def conv3x3_wgrad_kind(Cin: int, Cout: int, upsample: bool, winograd: bool = Tru
     return "direct"
 
 
+# conv3x3_wgrad_kind -> (the launcher - its planner is <launcher>_ws_elems, 0 for what the launcher refuses; the profile row's name)
+_WGRAD = {"direct": ("tgsr_conv3x3_wgrad", "conv3x3_wgrad_kernel"), "wino": ("tgsr_wino_wgrad", "wino_wgrad_kernel"),
+          "upwino": ("tgsr_upwino_wgrad", "upwino_wgrad_kernel")}
+
+
 def conv3x3_wgrad(draw: torch.Tensor, x: torch.Tensor, upsample: bool = False, winograd: bool = True,
                   out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Weight gradient [Cout,Cin,3,3] of conv3x3(upsample ? nearest_x2(x) : x): draw [B,Cout,Ho,Wo] (gradient at the raw
     conv output), x [B,Cin,H,W]; per-workgroup partial slabs summed in a fixed order (reproducible).  `out`: where to
-    write it (a gradient slot)."""
+    write it (a gradient slot).  A shape the kernel refuses (an empty batch) raises TgsrError."""
     _need_hip(draw, x, out)
     L = _lib.lib()
     draw = _f32(draw, "draw").contiguous()
@@ -1116,20 +1121,13 @@ def conv3x3_wgrad(draw: torch.Tensor, x: torch.Tensor, upsample: bool = False, w
     Cout, HW, dev = draw.shape[1], draw.shape[2] * draw.shape[3], x.device
     dw = out if out is not None else torch.empty(Cout, Cin, 3, 3, dtype=torch.float32, device=dev)
     kind = conv3x3_wgrad_kind(Cin, Cout, upsample, winograd)
+    entry, name = _WGRAD[kind]
+    up = (1 if upsample else 0,) if kind == "direct" else ()         # the one argument only tgsr_conv3x3_wgrad takes
     e0 = _ev() if profile is not None else None
-    if kind == "upwino":
-        ws = torch.empty(L.tgsr_upwino_wgrad_ws_elems(B, Cin, Cout, H, W), dtype=torch.float32, device=dev)
-        check(L.tgsr_upwino_wgrad(_p(draw), _p(x), Cin * H * W, B, Cin, H, W, Cout, _p(ws), _p(dw), _stream()), "tgsr_upwino_wgrad")
-    elif kind == "wino":
-        ws = torch.empty(L.tgsr_wino_wgrad_ws_elems(B, Cin, Cout, H, W), dtype=torch.float32, device=dev)
-        check(L.tgsr_wino_wgrad(_p(draw), _p(x), Cin * H * W, B, Cin, H, W, Cout, _p(ws), _p(dw), _stream()), "tgsr_wino_wgrad")
-    else:
-        ws = torch.empty(L.tgsr_conv3x3_wgrad_ws_elems(B, Cin, Cout, H, W, 1 if upsample else 0), dtype=torch.float32, device=dev)
-        check(L.tgsr_conv3x3_wgrad(_p(draw), _p(x), Cin * H * W, B, Cin, H, W, Cout, 1 if upsample else 0, _p(ws), _p(dw),
-                                   _stream()), "tgsr_conv3x3_wgrad")
+    ws = torch.empty(getattr(L, entry + "_ws_elems")(B, Cin, Cout, H, W, *up), dtype=torch.float32, device=dev)
+    check(getattr(L, entry)(_p(draw), _p(x), Cin * H * W, B, Cin, H, W, Cout, *up, _p(ws), _p(dw), _stream()), entry)
     if profile is not None:      # direct-form FLOPs of the weight gradient: one MAC per (output pixel, tap, ci, co)
-        profile.append(({"upwino": "upwino_wgrad_kernel", "wino": "wino_wgrad_kernel", "direct": "conv3x3_wgrad_kernel"}[kind],
-                        2.0 * B * HW * Cout * Cin * 9, 4.0 * (B * Cin * H * W + B * Cout * HW + Cout * Cin * 9), e0, _ev()))
+        profile.append((name, 2.0 * B * HW * Cout * Cin * 9, 4.0 * (B * Cin * H * W + B * Cout * HW + Cout * Cin * 9), e0, _ev()))
     return dw
 
 
