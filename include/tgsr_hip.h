@@ -482,11 +482,17 @@ int tgsr_axpy_images(int n, float* const* out, const float* const* t, const floa
  *   mask (nullable; laid out like `out`, same batch stride): the contribution is kept where mask > 0 and dropped elsewhere - the
  *              ReLU of the tensor whose gradient is being written (a 0 / 1 factor distributes over the sum of a tensor's consumers,
  *              so every consumer applies it to its own contribution and no separate mask pass runs).  Also on the pool backwards.
- *   ws: tgsr_gconv_ws_elems(B, M, PH, PW, K) floats (0 when the shape is not split over K).  Deterministic (slabs summed in order).
+ *   ws: tgsr_gconv_ws_elems(B, M, PH, PW, K) floats (0 when the shape is not split over K: NULL is accepted).  Deterministic (slabs
+ *              summed in order).
+ *   Alignment: every operand - A, S, bias, mask, out, ws, and tgsr_gconv_pack's w, scale, out - needs 4 bytes.  The three-piece form
+ *              (tgsr_gconv_set_form) loads A 16 bytes at a time: an A off 16 bytes is served by the fp32 MFMA (dword loads); S, mask and
+ *              out are read and written by dwords in both forms, so a channel slice and an odd batch stride need no more.
  * tgsr_maxpool3s2_*: F.max_pool2d(x, 3, stride 2); the backward routes dy to the FIRST maximum of a window (torch's rule).
  * tgsr_avgpool3: F.avg_pool2d(x, 3, 1, 1) (count_include_pad); symmetric, so it is also its own backward (accumulate = 1).
  * tgsr_plane_mean(_bwd): the 8 x 8 global average (F.avg_pool2d(x, 8) on an 8 x 8 map).  tgsr_relu_mask: out = dy * (y > 0).
  * tgsr_bilinear_*: nn.Upsample(size = (OH, OW), mode = 'bilinear') (align_corners = False), util.py:310, on dense planes.
+ * Alignment: the pools, tgsr_relu_mask, tgsr_interleave2x2, tgsr_plane_mean(_bwd) and tgsr_bilinear_* read and write by dwords: every
+ * pointer needs 4 bytes, every batch stride may be odd.  (tgsr_sum_stack: 16 bytes, below.)
  */
 /*
  * tgsr_gconv_set_form: 1 (default; TGSR_GCONV_SPLIT=0 in the environment turns it off): tgsr_gconv / tgsr_gconv_stats run on the bf16
@@ -531,7 +537,9 @@ int tgsr_gconv_pack(const float* w, const float* scale, float* out, int Cout, in
  *   y = relu((y - mean) * scale + beta) with the batch statistics combined from stat_partial (Chan's formula, double precision, a
  *   fixed order); writes stats [4][C] (mean,
  *   invstd, scale, shift), updates running_mean / running_var (momentum, unbiased variance; both NULL: none) and
- *   num_batches_tracked (nullable) once.
+ *   num_batches_tracked (nullable) once.  Alignment: stat_partial (read a (sum, M2) pair at a time) and num_batches_tracked 8 bytes,
+ *   else TGSR_EUNSUPPORTED; y, gamma, beta, the running statistics and stats 4 bytes.  tgsr_gconv_stats itself writes stat_partial by
+ *   dwords.
  */
 int tgsr_gconv_stats_nslots(int B, int M, int PH, int PW, int K);
 int tgsr_gconv_stats_slot_pixels(int B, int M, int PH, int PW, int K);
@@ -659,9 +667,15 @@ int tgsr_bn_train_bwd(const float* dout, const float* raw, int B, int C, int HW,
  *   *_fwd   out = conv(x, w)              *_dgrad  dx = conv_transpose(dy, w)          *_wgrad  dw = sum_pixels dy x_gather
  * ws: *_ws_elems(op, ...) floats with op = 0 forward, 1 data gradient, 2 weight gradient (slabs; for the 4x4 data
  * gradient also the per-parity-class weight regrouping, rebuilt by every call: weights change per step).
+ * Alignment: every operand - x, w, dy, ws, out / dx / dw - needs 4 bytes; no call is refused for an address.  The three-piece form
+ * (tgsr_dconv_set_split) loads its A operand 16 bytes at a time - w and the head of ws (forward, 4x4 data gradient), dy (weight
+ * gradients); the 3x3 data gradient reads w by dwords - and a call whose A is off 16 bytes is served by the fp32 MFMA, all dword
+ * accesses, with the bits of tgsr_dconv_set_split(0); the 4x4 data gradient then also regroups the weight one float at a time (the
+ * same packed bits).  The gathered tensor and the output are dword accesses in both forms.  The image layer's data gradient
+ * (Cin <= 4) stores dx in pairs where dx is 8-byte aligned and one float at a time where not: the same bits.
  * The generator's 3x3 convolutions (32 ... 128 channels on 32^2 ... 256^2 pixels) are tgsr_wino_conv3x3_fwd /
  * tgsr_conv3x3_fwd, not these.
- * tgsr_leaky_relu: out = x > 0 ? x : 0.2 x, or with y_for_bwd != NULL the backward out = x * (y > 0 ? 1 : 0.2).
+ * tgsr_leaky_relu: out = x > 0 ? x : 0.2 x, or with y_for_bwd != NULL the backward out = x * (y > 0 ? 1 : 0.2); dword accesses.
  * tgsr_dconv_set_split(on): on != 0 (the default; TGSR_DCONV_SPLIT=0 in the environment turns it off) lets the GEMMs of both
  * forms run on the bf16 matrix pipe with every fp32 operand split exactly into three bf16 pieces and six of the nine piece
  * products accumulated in fp32 (what is left out is <= 2^-26 of a product; measured error against fp64: below the fp32 MFMA's) -
@@ -672,8 +686,9 @@ int tgsr_bn_train_bwd(const float* dout, const float* raw, int B, int C, int HW,
 int tgsr_dconv_set_split(int on);
 /* 1 when tgsr_conv4x4s2_{fwd (op 0), dgrad (1), wgrad (2)} takes the split form for this shape under the current setting: what a
  * caller's bookkeeping needs to price a launch.  These and *_ws_elems read the launchers' own plan, evaluated for 16-byte aligned
- * operands (the calls themselves test w and ws - forward, 4x4 data gradient - or dy - weight gradient - and fall back to the fp32
- * MFMA otherwise) and bounding the convolution's tensors, not the kernel's operands, by 4 GB. */
+ * operands (the calls themselves test w and ws - forward, 4x4 data gradient - or dy - weight gradient - and serve an operand off 16
+ * bytes on the fp32 MFMA: see "Alignment" above) and bounding the convolution's tensors, not the kernel's operands, by 4 GB.
+ * An op outside 0..2 or a shape the calls refuse: split_form 0, ws_elems 0. */
 int tgsr_conv4x4s2_split_form(int op, int B, int Cin, int H, int W, int Cout);
 int tgsr_conv3x3_gemm_split_form(int op, int B, int Cin, int H, int W, int Cout);
 int64_t tgsr_conv4x4s2_ws_elems(int op, int B, int Cin, int H, int W, int Cout);

@@ -7,6 +7,7 @@ outside the process's memory.
     x = a.place_input(x_host, bstride=(Cin + 8) * H * W)      # samples `bstride` floats apart, NaN in between
     ws = a.place_ws(n)                                         # exactly n floats, NaN-prefilled
     dw = a.place_output((Cout, Cin, 3, 3))
+    dx = a.place_inout(base, bstride=(Cin + 2) * H * W + 1)   # what an accumulating call adds to: read and written, gaps guarded
     rc = L.tgsr_...(x.ptr, ..., ws.ptr, dw.ptr, ...)           # the first .ptr allocates the buffer
     a.check()
     got = dw.read()
@@ -110,20 +111,22 @@ class Arena:
         shape, nb, per = self._split(t.shape, t.dtype, bstride is not None)
         return self._place(_INPUT, shape, nb, per, bstride, align, skew, t.dtype, t.reshape(-1).view(torch.int32).clone())
 
-    def place_inout(self, t, align=16):
-        """An operand the call updates in place (running statistics, a step counter): initial values from `t`, must end finite."""
+    def place_inout(self, t, bstride=None, align=16, skew=0):
+        """An operand the call updates in place (running statistics, a step counter, the destination of an accumulating call):
+        initial values from `t`, must end finite.  With `bstride` its samples (dim 0) lie that many words apart, PATTERN in between -
+        gap words that must hold their bits like any other."""
         t = t.detach().cpu().contiguous()
-        shape, nb, per = self._split(t.shape, t.dtype, False)
-        return self._place(_INOUT, shape, nb, per, None, align, 0, t.dtype, t.reshape(-1).view(torch.int32).clone())
+        shape, nb, per = self._split(t.shape, t.dtype, bstride is not None)
+        return self._place(_INOUT, shape, nb, per, bstride, align, skew, t.dtype, t.reshape(-1).view(torch.int32).clone())
 
     def place_output(self, shape, bstride=None, align=16, skew=0, written=True, dtype=torch.float32):
         """An output, PATTERN-prefilled.  written=False: the call is given NULL (or refuses) - the region must stay untouched."""
         shape, nb, per = self._split(shape, dtype, bstride is not None)
         return self._place(_OUTPUT if written else _ABSENT, shape, nb, per, bstride, align, skew, dtype, None)
 
-    def place_ws(self, n, align=16):
+    def place_ws(self, n, align=16, skew=0):
         """A workspace of exactly `n` floats, PATTERN-prefilled (a NaN: whatever is read before it is written poisons the result)."""
-        return self._place(_WS, (int(n),), 1, int(n), None, align, 0, torch.float32, None)
+        return self._place(_WS, (int(n),), 1, int(n), None, align, skew, torch.float32, None)
 
     # ---- the buffer ----
     def _commit(self):

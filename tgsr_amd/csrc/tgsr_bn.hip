@@ -633,6 +633,8 @@ extern "C" int tgsr_bn_train_relu_slice_from_stats(float* y, int64_t bstride, in
   if ((int64_t)(nslots - 1) * slot_px >= (int64_t)B * HW || (int64_t)nslots * slot_px < (int64_t)B * HW) return TGSR_EINVAL;
   if ((running_mean == nullptr) != (running_var == nullptr)) return TGSR_EINVAL;
   if ((int64_t)B * HW >= (1ll << 31) - kBnThreads || bstride < (int64_t)C * HW) return TGSR_EUNSUPPORTED;
+  // the kernel reads a slot's (sum, M2) pair as one 8-byte load and num_batches_tracked as one 64-bit word
+  if ((reinterpret_cast<uintptr_t>(stat_partial) | reinterpret_cast<uintptr_t>(num_batches_tracked)) & 7) return TGSR_EUNSUPPORTED;
   const int nsplit = tgsr_bn_train_nsplit(B, C, HW);
   hipLaunchKernelGGL(bn_relu_slice_kernel, dim3(C, nsplit), dim3(kBnThreads), 0, as_stream(stream), y, bstride, B, C, HW,
                      stat_partial, nslots, slot_px, gamma, beta, eps, momentum, running_mean, running_var, stats,

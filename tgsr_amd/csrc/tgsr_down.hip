@@ -837,30 +837,52 @@ __global__ __launch_bounds__(256) void dconv_dgrad4_image_kernel(const float* __
   }
   const int W = 2 * W2;
   float* ob = dx + (int64_t)b * CIN * 4 * plane + (int64_t)(2 * yq) * W + 2 * xq;
+  // every offset above is even: the pairs are float2 stores where dx is 8-byte aligned, and two float stores of the same bits where not
+  // (no 8-byte alignment promised to the compiler there)
+  const bool pair = (reinterpret_cast<uintptr_t>(dx) & 7) == 0;
 #pragma unroll
   for (int c = 0; c < CIN; ++c) {
     float* o = ob + (int64_t)c * 4 * plane;
-    *reinterpret_cast<float2*>(o) = make_float2(acc[c][0][0], acc[c][0][1]);
-    *reinterpret_cast<float2*>(o + W) = make_float2(acc[c][1][0], acc[c][1][1]);
+    if (pair) {
+      *reinterpret_cast<float2*>(o) = make_float2(acc[c][0][0], acc[c][0][1]);
+      *reinterpret_cast<float2*>(o + W) = make_float2(acc[c][1][0], acc[c][1][1]);
+    } else {
+      o[0] = acc[c][0][0]; o[1] = acc[c][0][1];
+      o[W] = acc[c][1][0]; o[W + 1] = acc[c][1][1];
+    }
   }
 }
 
 // packed[cls = 2p + q][ci][co * 4 + 2a + c] = w[co][ci][p + 2a][q + 2c].  One thread per (ci, co) filter: its 16 taps are one
 // 64-byte read, and the four taps of a parity class are one 16-byte store that is contiguous with the neighbouring thread's
 // (co runs fastest over the lanes) - the per-element form of rounds 3-4 gathered 4 bytes at a time and took 0.49 ms per G/D step.
+// VEC4 = false: w or out is not 16-byte aligned (the launcher's fp32-MFMA fallback for exactly that case): the same regrouping one
+// float at a time - a pure copy, so the packed bits are the same.  What this form takes back is the float4 casts' PROMISE of 16-byte
+// alignment; hipcc may merge the dword accesses again (it does on gfx950: global multi-dword accesses need dword alignment only).
+template <bool VEC4>
 __global__ __launch_bounds__(256) void conv4x4s2_pack_dgrad_kernel(const float* __restrict__ w, float* __restrict__ out, int Cout,
                                                                    int Cin, int64_t total) {
   const int64_t nf = (int64_t)Cin * Cout;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nf; i += (int64_t)gridDim.x * blockDim.x) {
     const int co = (int)(i % Cout), ci = (int)(i / Cout);
-    const float4* src = reinterpret_cast<const float4*>(w + ((int64_t)co * Cin + ci) * 16);
-    const float4 r0 = src[0], r1 = src[1], r2 = src[2], r3 = src[3];            // kernel rows ky = 0 .. 3
-    float4* dst = reinterpret_cast<float4*>(out + ((int64_t)ci * Cout + co) * 4);
-    const int64_t cls4 = nf;                                                      // float4s per parity class
-    dst[0 * cls4] = make_float4(r0.x, r0.z, r2.x, r2.z);                          // p = 0, q = 0: (ky, kx) = (0|2, 0|2)
-    dst[1 * cls4] = make_float4(r0.y, r0.w, r2.y, r2.w);                          // p = 0, q = 1
-    dst[2 * cls4] = make_float4(r1.x, r1.z, r3.x, r3.z);                          // p = 1, q = 0
-    dst[3 * cls4] = make_float4(r1.y, r1.w, r3.y, r3.w);                          // p = 1, q = 1
+    if constexpr (VEC4) {
+      const float4* src = reinterpret_cast<const float4*>(w + ((int64_t)co * Cin + ci) * 16);
+      const float4 r0 = src[0], r1 = src[1], r2 = src[2], r3 = src[3];            // kernel rows ky = 0 .. 3
+      float4* dst = reinterpret_cast<float4*>(out + ((int64_t)ci * Cout + co) * 4);
+      const int64_t cls4 = nf;                                                      // float4s per parity class
+      dst[0 * cls4] = make_float4(r0.x, r0.z, r2.x, r2.z);                          // p = 0, q = 0: (ky, kx) = (0|2, 0|2)
+      dst[1 * cls4] = make_float4(r0.y, r0.w, r2.y, r2.w);                          // p = 0, q = 1
+      dst[2 * cls4] = make_float4(r1.x, r1.z, r3.x, r3.z);                          // p = 1, q = 0
+      dst[3 * cls4] = make_float4(r1.y, r1.w, r3.y, r3.w);                          // p = 1, q = 1
+    } else {
+      const float* src = w + ((int64_t)co * Cin + ci) * 16;
+      float* dst = out + ((int64_t)ci * Cout + co) * 4;
+#pragma unroll
+      for (int cls = 0; cls < 4; ++cls)
+#pragma unroll
+        for (int e = 0; e < 4; ++e)                                                 // e = 2a + c: tap (p + 2a, q + 2c) of class cls = 2p + q
+          dst[cls * 4 * nf + e] = src[((cls >> 1) + 2 * (e >> 1)) * 4 + (cls & 1) + 2 * (e & 1)];
+    }
   }
 }
 
@@ -1033,7 +1055,10 @@ static int dconv_dgrad(int kind, const float* dy, int B, int Cin, int H, int W, 
     const int64_t total = 16ll * Cin * Cout;
     const int64_t nf = (int64_t)Cin * Cout;
     const int pb = (int)((nf + 255) / 256 < 4096 ? (nf + 255) / 256 : 4096);
-    hipLaunchKernelGGL(conv4x4s2_pack_dgrad_kernel, dim3(pb), dim3(256), 0, s, w, ws, Cout, Cin, total);
+    // (unaligned w or ws: the plan has fallen back to the fp32 MFMA, which reads the pack by dwords - so must the pack be written)
+    if ((reinterpret_cast<uintptr_t>(ws) | reinterpret_cast<uintptr_t>(w)) & 15)
+      hipLaunchKernelGGL(conv4x4s2_pack_dgrad_kernel<false>, dim3(pb), dim3(256), 0, s, w, ws, Cout, Cin, total);
+    else hipLaunchKernelGGL(conv4x4s2_pack_dgrad_kernel<true>, dim3(pb), dim3(256), 0, s, w, ws, Cout, Cin, total);
     rc = note_launch(hipGetLastError(), "conv4x4s2_pack_dgrad_kernel");
   }
   if (rc) return rc;
