@@ -142,8 +142,8 @@ int tgsr_upwino4_fwd(const float* x, int64_t x_bstride, int B, int Cin, int H, i
  * outputs instead of 36.  fp32 throughout; the transforms only use {0, +-1, +-1/2} (end-to-end error on the shipped
  * checkpoint indistinguishable from the direct fp32 form).  upack from tgsr_pack_wino_weight
  * (tgsr_packed_wino_weight_elems floats; `glu` != 0 groups each value channel block with its gate block and must
- * match the epilogue the pack is used with).  Cout % 32 == 0 (64-channel groups when Cout % 64 == 0, else 32), Cin % 4 == 0, W % 4 == 0, x 16-byte aligned, out / residual 8-byte
- * aligned with even batch strides; same epilogue selectors and residual rule as tgsr_conv3x3_fwd.
+ * match the epilogue the pack is used with).  Cout % 32 == 0 (64-channel groups when Cout % 64 == 0, else 32), Cin % 4 == 0, W % 4 == 0, x 16-byte
+ * aligned (batch stride % 4 == 0), out / residual 8-byte aligned with even batch strides; same epilogue selectors and residual rule as tgsr_conv3x3_fwd.
  */
 int64_t tgsr_packed_wino_weight_elems(int Cout, int Cin);
 int tgsr_pack_wino_weight(const float* w, float* upack, int Cout, int Cin, int glu, void* stream);
@@ -179,13 +179,46 @@ int tgsr_wino4_conv3x3_fwd(const float* x, int64_t x_bstride, int B, int Cin, in
 int tgsr_pack_wino4_wide_weight(const float* w, float* upack, int Cout, int Cin, int glu, void* stream);
 /* ... of the data-gradient convolution, from the forward weight [Cin][Cout][3][3] (see tgsr_pack_conv_weight_dgrad) */
 int tgsr_pack_wino4_wide_weight_dgrad(const float* w, float* upack, int Cout, int Cin, void* stream);
-/* ... with the statistics epilogue of tgsr_wino4_conv3x3_stats_fwd (training forward): one pair per channel and 4 x 64 wave tile */
+/* ... with the statistics epilogue of tgsr_wino4_conv3x3_stats_fwd (training forward): one pair per channel and workgroup (4 x 64
+ * outputs).  Like the other two *_stats_nslots: the plan's nslots, 0 for sizes the launcher refuses (a size < 1, Cout % 64, H W >= 2^28). */
 int tgsr_wino4_wide_stats_nslots(int B, int H, int W, int Cout);
 int tgsr_wino4_wide_conv3x3_stats_fwd(const float* x, int64_t x_bstride, int B, int Cin, int H, int W, const float* upack,
                                       int Cout, float* out, int64_t out_bstride, float* stat_partial, void* stream);
 int tgsr_wino4_wide_conv3x3_fwd(const float* x, int64_t x_bstride, int B, int Cin, int H, int W, const float* upack, int Cout,
                                 const float* scale, const float* shift, const float* residual, int64_t res_bstride,
                                 float* out, int64_t out_bstride, int epilogue, void* stream);
+
+/*
+ * The planner of the seven forms above.  Every launch of theirs is planned once, by one host function (csrc/tgsr_conv_plan.h, which
+ * also holds the table of what the forms ask of their operands); tgsr_conv3x3_form_plan is that very function.  Host arithmetic
+ * only: the pointers are looked at for NULL and for their alignment and never read through.  `form` = TGSR_CONV_FORM_*, the rest as
+ * the form's entry point takes it: `pack` its wpack / upack, `epilogue` TGSR_EPI_AFFINE_GLU for tgsr_upconv3x3_glu_fwd,
+ * tgsr_upwino_glu_fwd and tgsr_upwino4_fwd(glu != 0), `residual` NULL for the entries that take none, `upsample` read by
+ * TGSR_CONV_FORM_DIRECT only, `stats` != 0 for the *_stats_fwd entries (which pass no scale / shift / residual and TGSR_EPI_AFFINE).
+ * It returns what the entry point returns for these operands ahead of its launch (TGSR_EINVAL: an unknown form, a NULL x / pack /
+ * out, a size < 1, scale without shift, an unknown epilogue, a residual with GLU or for a form without one, an epilogue or `stats`
+ * the form has no kernel for; TGSR_EUNSUPPORTED: channel counts, image sizes, alignments or a grid beyond 2^31 - 1 workgroups) and,
+ * with TGSR_OK only, fills plan[TGSR_CONV_PLAN_FIELDS] (may be NULL):
+ *     [0] the kernel family = form     [1..4] its template integers, 0 where it has fewer:
+ *         DIRECT conv3x3_mfma_kernel<NOB, GLU, UP, R, 4>, UPCONV upconv_glu_mfma_kernel, UPWINO upwino_kernel<GLU>, UPWINO4
+ *         upwino4_kernel<GLU>, WINO wino_conv3x3_kernel<GLU, NH, STATS>, WINO4 wino4_conv3x3_kernel<GLU, STATS>, WINO4W
+ *         wino4w_conv3x3_kernel<GLU, NB, STATS>
+ *     [5] grid.x     [6] grid.y     [7] block.x     [8] tiles_x     [9] tiles_y: workgroup tiles of an image
+ *     [10] [11] rows and columns of a workgroup tile in OUTPUT pixels     [12] K stages of 4 input channels     [13] channel groups
+ *     [14] nslots: statistics slots per channel (the forms with a *_stats_fwd entry; what their *_stats_nslots answer)
+ */
+#define TGSR_CONV_FORM_DIRECT 0
+#define TGSR_CONV_FORM_UPCONV 1
+#define TGSR_CONV_FORM_UPWINO 2
+#define TGSR_CONV_FORM_UPWINO4 3
+#define TGSR_CONV_FORM_WINO 4
+#define TGSR_CONV_FORM_WINO4 5
+#define TGSR_CONV_FORM_WINO4W 6
+#define TGSR_CONV_FORMS 7
+#define TGSR_CONV_PLAN_FIELDS 15
+int tgsr_conv3x3_form_plan(int form, const float* x, int64_t x_bstride, int B, int Cin, int H, int W, const float* pack, int Cout,
+                           const float* scale, const float* shift, const float* residual, int64_t res_bstride, const float* out,
+                           int64_t out_bstride, int epilogue, int upsample, int stats, int* plan);
 
 /*
  * tgsr_conv_to3_set_pipe(on): the streaming form of tgsr_conv_to3_fwd with its LDS copies two stages ahead in a ring of three buffers

@@ -14,10 +14,11 @@ hold their bits, every output word is written and finite, a second call gives th
 project's caps of the same operation in fp64 on the CPU (F.conv2d on the repeat_interleave'd input for the up forms, the affine,
 GLU with torch.sigmoid).
 
-TABLE has one row per (entry point, kernel instance) with the dispatch condition copied from the launcher; a test asserts from
-the library's own planners (tgsr_conv3x3_fwd_plan, tgsr_conv_to3_plan, *_stats_nslots) that its case reaches the instance the
-row names.  Shapes are the smallest that reach the instance with a ragged last tile in both directions and, where the tile-count
-thresholds leave room, two tile rows and two tile columns.
+TABLE has one row per (entry point, kernel instance) with the dispatch condition in words; a test asserts from the library's own
+planners that its case reaches the instance the row names - tgsr_conv3x3_form_plan, the one place the fp32 forward launches are
+planned (csrc/tgsr_conv_plan.h: the function the launchers call), and tgsr_conv_to3_plan for the image heads.  Shapes are the
+smallest that reach the instance with a ragged last tile in both directions and, where the tile-count thresholds leave room, two
+tile rows and two tile columns.
 
 Besides the caps every convolution carries the ratio bound of tests/test_hip_parity_margin.py: its mean distance from fp64 against
 the distance of torch's CPU fp32 evaluation of the same operation from the same fp64 (R_DIRECT / R_F22 / R_F44 below).
@@ -173,7 +174,7 @@ def row_id(r):
 
 
 # ----------------------------------------------------------------------------------------------------------------------------
-# What a case reaches, from the library's planners and the launchers' conditions
+# What a case reaches, from the library's planners
 # ----------------------------------------------------------------------------------------------------------------------------
 def _b(v):
     return "true" if v else "false"
@@ -189,31 +190,56 @@ def fn_of(entry, c):
     return entry
 
 
-def conv_plan(L, entry, c):
-    """(instance, tile rows, tile columns) in output pixels of a convolution case."""
-    B, Cout, H, W, glu = c["B"], c["Cout"], c["H"], c["W"], c["glu"]
-    if entry == DIRECT:
-        nob, rpw, groups = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
-        rc = L.tgsr_conv3x3_fwd_plan(B, H, W, Cout, glu, c["up"], ctypes.byref(nob), ctypes.byref(rpw), ctypes.byref(groups))
-        assert rc == 0 and groups.value == Cout // ((64 if glu else 32) * nob.value)
-        return _D % ("%d,%s,%s,%d" % (nob.value, _b(glu), _b(c["up"]), rpw.value)), 4 * rpw.value, 32
-    if entry == UPCONV:
-        return "upconv_glu_mfma_kernel", 8, 64
-    if entry == UPWINO:
-        return "upwino_kernel<%s>" % _b(glu), 4, 32
-    if entry == UPWINO4:
-        return "upwino4_kernel<%s>" % _b(glu), 4, 64
-    if entry == WINO:
-        nh = 2 if Cout % 64 == 0 else 1
-        rows = 4 if nh == 2 else 8
-        assert L.tgsr_wino_stats_nslots(B, H, W, Cout) == B * -(-H // rows) * -(-W // 32) * (rows // 2)      # one slot per wave
-        return "wino_conv3x3_kernel<%s,%d,%s>" % (_b(glu), nh, _b(c["stats"])), rows, 32
-    if entry == WINO4:
-        assert L.tgsr_wino4_stats_nslots(B, H, W, Cout) == B * -(-H // 8) * -(-W // 64) * 2
-        return "wino4_conv3x3_kernel<%s,%s>" % (_b(glu), _b(c["stats"])), 8, 64
-    assert entry == WIDE
-    assert L.tgsr_wino4_wide_stats_nslots(B, H, W, Cout) == B * -(-H // 4) * -(-W // 64)
-    return "wino4w_conv3x3_kernel<%s,%d,%s>" % (_b(glu), 8 if Cout % 128 == 0 else 4, _b(c["stats"])), 4, 64
+FORM_OF = {DIRECT: "direct", UPCONV: "upconv", UPWINO: "upwino", UPWINO4: "upwino4", WINO: "wino", WINO4: "wino4", WIDE: "wino4w"}
+
+
+def form_plan(L, form, kw, stats=0):
+    """tgsr_conv3x3_form_plan - the function the launchers plan with - on the named arguments of a call (place_conv's or fake_conv's):
+    (status, plan[TGSR_CONV_PLAN_FIELDS], prefilled with -7)."""
+    from tgsr_amd import _lib as M
+    buf = (ctypes.c_int * M.CONV_PLAN_FIELDS)(*([-7] * M.CONV_PLAN_FIELDS))
+    rc = L.tgsr_conv3x3_form_plan(M.CONV_FORMS.index(form), kw["x"], kw["xbs"], kw["B"], kw["Cin"], kw["H"], kw["W"], kw["pack"], kw["Cout"],
+                                  kw["scale"], kw["shift"], kw["res"], kw["rbs"], kw["out"], kw["obs"], kw["epilogue"], kw["upsample"],
+                                  int(stats), buf)
+    return rc, list(buf)
+
+
+def instance_of(plan):
+    """The kernel instance a plan names: its family with the template integers it takes."""
+    from tgsr_amd import _lib as M
+    fam = M.CONV_FAMILIES[plan[M.CONV_PLAN_FAMILY]]
+    specs = [fam[i + 1] for i in range(len(fam) - 1) if fam[i] == "%"]
+    return fam % tuple(t if k == "d" else _b(t) for k, t in zip(specs, plan[M.CONV_PLAN_T:]))
+
+
+def fake_conv(c, skew=None):
+    """place_conv's named arguments with the operands at made-up addresses, 16-byte aligned plus their skew in words: all the planner,
+    which reads through no pointer, needs."""
+    skew = skew or {}
+    xbs, obs, rbs = conv_strides(c)
+
+    def at(i, name):
+        return (i << 24) + 4 * skew.get(name, 0)
+    return dict(x=at(1, "x"), xbs=xbs, B=c["B"], Cin=c["Cin"], H=c["H"], W=c["W"], pack=at(2, "pack"), Cout=c["Cout"],
+                scale=at(3, "scale") if c["aff"] else None, shift=at(4, "shift") if c["aff"] else None,
+                res=at(5, "res") if c["res"] else None, rbs=rbs if c["res"] else 0, out=at(6, "out"), obs=obs, epilogue=c["glu"],
+                upsample=c["up"], glu=c["glu"], stat=at(7, "stat") if c["stats"] else None)
+
+
+def conv_plan(L, entry, c, kw=None):
+    """(instance, tile rows, tile columns) in output pixels of a convolution case, as the library's planner states them for the call
+    `kw` (default: the case's operands at aligned made-up addresses)."""
+    from tgsr_amd import _lib as M
+    rc, plan = form_plan(L, FORM_OF[entry], kw or fake_conv(c), c["stats"])
+    assert rc == 0, "the planner refuses the case with %d" % rc
+    if entry in (WINO, WINO4, WIDE):
+        assert nslots_of(L, entry, c) == plan[M.CONV_PLAN_NSLOTS]
+    return instance_of(plan), plan[M.CONV_PLAN_TILE_H], plan[M.CONV_PLAN_TILE_W]
+
+
+def ops_forms():
+    from tgsr_amd import ops
+    return ops.FORMS
 
 
 def nslots_of(L, entry, c):

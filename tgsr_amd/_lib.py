@@ -22,6 +22,14 @@ WGRAD_DIRECT, WGRAD_WINO, WGRAD_UPWINO = 0, 1, 2                    # `kind` of 
 WGRAD_FAMILIES = ("conv3x3_wgrad_kernel<%d,%d,%s>", "wino_wgrad_kernel<%d,%d>", "wino_wgrad_dma_kernel<%d>", "upwino_wgrad_kernel<%d>")
 WGRAD_PLAN_FIELDS, WGRAD_PLAN_WS = 10, 9                            # int64 fields of its `out`; the field that holds ws_elems
 TO3_BWD_PLAN_FIELDS, TO3_BWD_PLAN_WS = 4, 3                         # ... of tgsr_conv_to3_bwd_plan
+# `form` of tgsr_conv3x3_form_plan (TGSR_CONV_FORM_*) = the kernel family its plan[0] names, in the order of ops.FORMS' names below
+CONV_FORMS = ("direct", "upconv", "upwino", "upwino4", "wino", "wino4", "wino4w")
+# ... each with the template integers of plan[1..4] it takes (%d an integer, %s a bool)
+CONV_FAMILIES = ("conv3x3_mfma_kernel<%d,%s,%s,%d,4>", "upconv_glu_mfma_kernel", "upwino_kernel<%s>", "upwino4_kernel<%s>",
+                 "wino_conv3x3_kernel<%s,%d,%s>", "wino4_conv3x3_kernel<%s,%s>", "wino4w_conv3x3_kernel<%s,%d,%s>")
+CONV_PLAN_FIELDS = 15                                               # int fields of its `plan`, and where they are:
+(CONV_PLAN_FAMILY, CONV_PLAN_T, CONV_PLAN_GRID_X, CONV_PLAN_GRID_Y, CONV_PLAN_BLOCK, CONV_PLAN_TILES_X, CONV_PLAN_TILES_Y,
+ CONV_PLAN_TILE_H, CONV_PLAN_TILE_W, CONV_PLAN_STAGES, CONV_PLAN_GROUPS, CONV_PLAN_NSLOTS) = (0, 1, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14)
 
 _vp, _i, _i64, _f, _d = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_float, ctypes.c_double
 
@@ -58,6 +66,7 @@ SIGNATURES = {
     "tgsr_wino4_wide_conv3x3_stats_fwd": (_i, [_vp, _i64, _i, _i, _i, _i, _vp, _i, _vp, _i64, _vp, _vp]),
     "tgsr_wino4_wide_conv3x3_fwd": (_i, [_vp, _i64, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _i64, _vp, _i64, _i, _vp]),
     "tgsr_wino4_conv3x3_fwd": (_i, [_vp, _i64, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _i64, _vp, _i64, _i, _vp]),
+    "tgsr_conv3x3_form_plan": (_i, [_i, _vp, _i64, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _i64, _vp, _i64, _i, _i, _i, _vp]),
     "tgsr_conv_to3_fwd": (_i, [_vp, _i64, _i, _i, _i, _i, _vp, _i, _i, _vp, _f, _vp, _vp]),
     "tgsr_conv_to3_plan": (_i, [_vp, _i64, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "tgsr_word_attention_fwd": (_i, [_vp, _i64, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _i64, _vp, _vp]),

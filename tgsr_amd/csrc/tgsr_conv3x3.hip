@@ -16,6 +16,7 @@
 //     copy of stage c+1 runs under the 9.2k MFMA cycles of stage c: one barrier per stage, no staging VGPRs.
 //   * <= 48 KB LDS and ~128 accumulator VGPRs per workgroup -> 2-3 workgroups per CU.
 #include "tgsr_common.h"
+#include "tgsr_conv_plan.h"
 
 namespace tgsr {
 
@@ -304,82 +305,51 @@ __global__ __launch_bounds__(64 * WV, 2) void conv3x3_mfma_kernel(ConvArgs a) {
 }
 
 template <int NOB, bool GLU, bool UP, int R, int WV>
-static int launch_conv(const ConvArgs& a, int groups, hipStream_t s) {
-  using C = ConvCfg<NOB, GLU, UP, R, WV>;
-  ConvArgs k = a;
-  k.tiles_x = (a.Wo + 31) / 32;
-  k.tiles_y = (a.Ho + C::TH - 1) / C::TH;
-  dim3 grid((unsigned)(a.B * k.tiles_x * k.tiles_y), (unsigned)groups);
-  hipLaunchKernelGGL((conv3x3_mfma_kernel<NOB, GLU, UP, R, WV>), grid, dim3(64 * WV), 0, s, k);
+static int launch_conv(const ConvArgs& a, const ConvPlan& p, hipStream_t s) {
+  static_assert(WV == kConvDirectWaves && ConvCfg<NOB, GLU, UP, R, WV>::TH == kConvDirectWaves * R, "the plan's rows are the kernel's");
+  hipLaunchKernelGGL((conv3x3_mfma_kernel<NOB, GLU, UP, R, WV>), p.grid, p.block, 0, s, a);
   return note_launch(hipGetLastError(), "conv3x3_mfma_kernel");
 }
 
-// rows per workgroup = WV * R: (4,4) 16 rows, (4,2) 8, (4,1) 4
+// R = the plan's rows per wave: (4,4) 16 rows per workgroup, (4,2) 8, (4,1) 4; 16 rows only with <= 2 accumulator blocks
 template <int NOB, bool GLU, bool UP>
-static int dispatch_r(const ConvArgs& a, int groups, int rows, hipStream_t s) {
+static int dispatch_r(const ConvArgs& a, const ConvPlan& p, hipStream_t s) {
   constexpr int NCB = NOB * (GLU ? 2 : 1);
   if constexpr (NCB <= 2) {
-    if (rows == 16) return launch_conv<NOB, GLU, UP, 4, 4>(a, groups, s);
+    if (p.t[3] == 4) return launch_conv<NOB, GLU, UP, 4, 4>(a, p, s);
   }
-  if (rows >= 8) return launch_conv<NOB, GLU, UP, 2, 4>(a, groups, s);
-  return launch_conv<NOB, GLU, UP, 1, 4>(a, groups, s);
+  if (p.t[3] >= 2) return launch_conv<NOB, GLU, UP, 2, 4>(a, p, s);
+  return launch_conv<NOB, GLU, UP, 1, 4>(a, p, s);
 }
 
 template <int NOB, bool GLU>
-static int dispatch_up_r(const ConvArgs& a, int groups, bool up, int rows, hipStream_t s) {
-  return up ? dispatch_r<NOB, GLU, true>(a, groups, rows, s) : dispatch_r<NOB, GLU, false>(a, groups, rows, s);
+static int dispatch_up_r(const ConvArgs& a, const ConvPlan& p, hipStream_t s) {
+  return p.t[2] ? dispatch_r<NOB, GLU, true>(a, p, s) : dispatch_r<NOB, GLU, false>(a, p, s);
 }
 
 }  // namespace tgsr
 
 using namespace tgsr;
 
-// Tile choice of tgsr_conv3x3_fwd (host arithmetic only; also exported as tgsr_conv3x3_fwd_plan).  Candidates from most operand
-// reuse (2 output blocks per workgroup, 8 accumulators per wave) to least (1 block, 4 rows); take the first that gives >= 2
-// workgroups per CU, else the first with >= 1 per CU, else the smallest tile: at B = 16 an idle CU costs more than the lost
-// reuse.  (2-wave workgroups of 2 rows were measured: same MFMA chain per wave, no gain - the WV parameter stays for a K-split.)
-// As coded, a first pass that finds nothing ahead of the LAST candidate (1 block, 4 rows) leaves the choice to the second pass: a
-// taller tile with >= 256 workgroups then wins over the 4-row tile with >= 512 (B = 1, 96 filters, 17 x 1345: 16 rows, 258
-// workgroups).  The shipped shapes were tuned with it; tests/test_infer_abi_host.py restates it.
-// nob = output blocks per workgroup (the kernel's NOB), rows = output rows per workgroup (4 waves x R), groups = grid.y.
-static int conv3x3_fwd_plan(int B, int H, int W, int Cout, int epilogue, int upsample, int& nob, int& rows, int& groups) {
-  if (B < 1 || H < 1 || W < 1 || Cout < 1) return TGSR_EINVAL;
-  const bool glu = epilogue == TGSR_EPI_AFFINE_GLU;
-  if (!glu && epilogue != TGSR_EPI_AFFINE) return TGSR_EINVAL;
-  if (Cout % (glu ? 64 : 32) != 0) return TGSR_EUNSUPPORTED;
-  if ((int64_t)H * W >= (1 << 28)) return TGSR_EUNSUPPORTED;
-  const int Ho = upsample ? 2 * H : H, Wo = upsample ? 2 * W : W;
-  const int unit = glu ? 64 : 32;          // couts consumed per output block
-  const int nob_max = (Cout % (2 * unit) == 0) ? 2 : 1;
-  struct Cand { int nob, rows; };
-  Cand cands[8];
-  int nc = 0;
-  for (int nb = nob_max; nb >= 1; --nb) {
-    const int ncb = nb * (glu ? 2 : 1);
-    if (ncb <= 2) cands[nc++] = {nb, 16};
-    cands[nc++] = {nb, 8};
-    cands[nc++] = {nb, 4};
-  }
-  auto ntiles = [&](const Cand& c) {
-    return (int64_t)B * ((Ho + c.rows - 1) / c.rows) * ((Wo + 31) / 32) * (Cout / (unit * c.nob));
-  };
-  int pick = nc - 1;
-  for (int pass = 0; pass < 2 && pick == nc - 1; ++pass)
-    for (int i = 0; i < nc; ++i)
-      if (ntiles(cands[i]) >= (pass == 0 ? 512 : 256)) { pick = i; break; }
-  nob = cands[pick].nob; rows = cands[pick].rows;
-  groups = Cout / (unit * nob);
+extern "C" int tgsr_conv3x3_fwd_plan(int B, int H, int W, int Cout, int epilogue, int upsample, int* nob, int* rows_per_wave,
+                                     int* groups) {
+  const ConvPlan p = conv_tiles(TGSR_CONV_FORM_DIRECT, B, H, W, Cout, epilogue, upsample, 0);
+  if (p.status != TGSR_OK) return p.status;
+  if (nob) *nob = p.t[0];
+  if (rows_per_wave) *rows_per_wave = p.t[3];
+  if (groups) *groups = p.groups;
   return TGSR_OK;
 }
 
-extern "C" int tgsr_conv3x3_fwd_plan(int B, int H, int W, int Cout, int epilogue, int upsample, int* nob, int* rows_per_wave,
-                                     int* groups) {
-  int n = 0, rows = 0, g = 0;
-  const int rc = conv3x3_fwd_plan(B, H, W, Cout, epilogue, upsample, n, rows, g);
-  if (rc != TGSR_OK) return rc;
-  if (nob) *nob = n;
-  if (rows_per_wave) *rows_per_wave = rows / 4;
-  if (groups) *groups = g;
+extern "C" int tgsr_conv3x3_form_plan(int form, const float* x, int64_t x_bstride, int B, int Cin, int H, int W, const float* pack,
+                                      int Cout, const float* scale, const float* shift, const float* residual, int64_t res_bstride,
+                                      const float* out, int64_t out_bstride, int epilogue, int upsample, int stats, int* plan) {
+  const ConvPlan p = conv_plan(form, ConvCall{x, x_bstride, B, Cin, H, W, pack, Cout, scale, shift, residual, res_bstride,
+                                              const_cast<float*>(out), out_bstride, epilogue, upsample, stats});
+  if (p.status != TGSR_OK) return p.status;
+  const int f[TGSR_CONV_PLAN_FIELDS] = {p.family, p.t[0], p.t[1], p.t[2], p.t[3], (int)p.grid.x, (int)p.grid.y, (int)p.block.x,
+                                        p.tiles_x, p.tiles_y, p.tile_h, p.tile_w, p.stages, p.groups, p.nslots};
+  for (int i = 0; plan && i < TGSR_CONV_PLAN_FIELDS; ++i) plan[i] = f[i];
   return TGSR_OK;
 }
 
@@ -387,25 +357,15 @@ extern "C" int tgsr_conv3x3_fwd(const float* x, int64_t x_bstride, int B, int Ci
                                 int Cout, const float* scale, const float* shift, const float* residual,
                                 int64_t res_bstride, float* out, int64_t out_bstride, int epilogue, int upsample,
                                 void* stream) {
-  if (!x || !wpack || !out || Cin < 1) return TGSR_EINVAL;
-  if ((scale == nullptr) != (shift == nullptr)) return TGSR_EINVAL;
-  const bool glu = epilogue == TGSR_EPI_AFFINE_GLU;
-  if (glu && residual) return TGSR_EINVAL;
-  int nob = 0, rows = 0, groups = 0;   // (sizes, the epilogue selector, Cout % 32 | 64 and H W < 2^28 are the plan's to refuse)
-  if (const int rc = conv3x3_fwd_plan(B, H, W, Cout, epilogue, upsample, nob, rows, groups)) return rc;
-  if ((int64_t)Cin * H * W >= (1ll << 32)) return TGSR_EUNSUPPORTED;
+  const ConvCall c{x, x_bstride, B, Cin, H, W, wpack, Cout, scale, shift, residual, res_bstride, out, out_bstride, epilogue, upsample, 0};
+  const ConvPlan p = conv_plan(TGSR_CONV_FORM_DIRECT, c);
+  if (p.status != TGSR_OK) return p.status;
   ConvArgs a;
-  a.x = x; a.xbs = x_bstride; a.B = B; a.Cin = Cin; a.H = H; a.W = W;
-  a.wpack = wpack; a.Cout = Cout; a.scale = scale; a.shift = shift;
-  a.res = residual; a.rbs = res_bstride; a.out = out; a.obs = out_bstride;
-  a.Ho = upsample ? 2 * H : H; a.Wo = upsample ? 2 * W : W;
-  a.nchunks = (Cin + kConvCK - 1) / kConvCK;
-  a.tiles_x = a.tiles_y = 0;
+  conv_fill(a, c, p);
+  a.wpack = wpack; a.res = residual; a.rbs = res_bstride; a.Ho = upsample ? 2 * H : H; a.Wo = upsample ? 2 * W : W; a.nchunks = p.stages;
   hipStream_t s = as_stream(stream);
-  if (glu) return nob == 2 ? dispatch_up_r<2, true>(a, groups, upsample != 0, rows, s)
-                           : dispatch_up_r<1, true>(a, groups, upsample != 0, rows, s);
-  return nob == 2 ? dispatch_up_r<2, false>(a, groups, upsample != 0, rows, s)
-                  : dispatch_up_r<1, false>(a, groups, upsample != 0, rows, s);
+  if (p.t[1]) return p.t[0] == 2 ? dispatch_up_r<2, true>(a, p, s) : dispatch_up_r<1, true>(a, p, s);
+  return p.t[0] == 2 ? dispatch_up_r<2, false>(a, p, s) : dispatch_up_r<1, false>(a, p, s);
 }
 
 #ifdef TGSR_CONV_STAMPS

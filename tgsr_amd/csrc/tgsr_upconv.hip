@@ -16,6 +16,7 @@
 // channels are double buffered in LDS by LDS-DMA exactly like tgsr_conv3x3.hip; the two column phases of a lane are
 // stored together as one 8-byte store (fully coalesced rows of the NCHW output plane).
 #include "tgsr_common.h"
+#include "tgsr_conv_plan.h"
 
 namespace tgsr {
 
@@ -241,27 +242,20 @@ extern "C" int64_t tgsr_packed_upconv_weight_elems(int Cout, int Cin) {
 }
 
 extern "C" int tgsr_pack_upconv_weight(const float* w, float* wpack, int Cout, int Cin, void* stream) {
-  if (!w || !wpack || Cout < 1 || Cin < 1) return TGSR_EINVAL;
-  const int64_t total = tgsr_packed_upconv_weight_elems(Cout, Cin);
-  const int blocks = (int)((total + 255) / 256 < 1024 ? (total + 255) / 256 : 1024);
-  hipLaunchKernelGGL(pack_upconv_weight_kernel, dim3(blocks), dim3(256), 0, as_stream(stream), w, wpack, Cout, Cin,
-                     total);
-  return note_launch(hipGetLastError(), "pack_upconv_weight_kernel");
+  return launch_pack(pack_upconv_weight_kernel, "pack_upconv_weight_kernel", 1, 1024, tgsr_packed_upconv_weight_elems(Cout, Cin), stream, w,
+                     wpack, Cout, Cin);
 }
 
 extern "C" int tgsr_upconv3x3_glu_fwd(const float* x, int64_t x_bstride, int B, int Cin, int H, int W,
                                       const float* wpack, int Cout, const float* scale, const float* shift, float* out,
                                       int64_t out_bstride, void* stream) {
-  if (!x || !wpack || !out || B < 1 || Cin < 1 || H < 1 || W < 1 || Cout < 1) return TGSR_EINVAL;
-  if ((scale == nullptr) != (shift == nullptr)) return TGSR_EINVAL;
-  if (Cout % 64 != 0) return TGSR_EUNSUPPORTED;
-  if ((int64_t)H * W >= (1 << 28) || (int64_t)Cin * H * W >= (1ll << 32)) return TGSR_EUNSUPPORTED;
-  if ((reinterpret_cast<uintptr_t>(out) & 7) != 0 || (out_bstride & 1) != 0) return TGSR_EUNSUPPORTED;
+  static_assert(kUpWV == 4 && kConvCK == kConvStage, "the plan's tile (4 source rows) and stage are the kernel's");
+  const ConvCall c{x, x_bstride, B, Cin, H, W, wpack, Cout, scale, shift, nullptr, 0, out, out_bstride, TGSR_EPI_AFFINE_GLU, 1, 0};
+  const ConvPlan p = conv_plan(TGSR_CONV_FORM_UPCONV, c);
+  if (p.status != TGSR_OK) return p.status;
   UpArgs a;
-  a.x = x; a.xbs = x_bstride; a.B = B; a.Cin = Cin; a.H = H; a.W = W; a.wpack = wpack; a.Cout = Cout;
-  a.scale = scale; a.shift = shift; a.out = out; a.obs = out_bstride;
-  a.tiles_x = (W + 31) / 32; a.tiles_y = (H + kUpWV - 1) / kUpWV; a.nchunks = (Cin + kConvCK - 1) / kConvCK;
-  dim3 grid((unsigned)(B * a.tiles_x * a.tiles_y), (unsigned)(Cout / 64));
-  hipLaunchKernelGGL(upconv_glu_mfma_kernel, grid, dim3(64 * kUpWV), 0, as_stream(stream), a);
+  conv_fill(a, c, p);
+  a.wpack = wpack; a.nchunks = p.stages;
+  hipLaunchKernelGGL(upconv_glu_mfma_kernel, p.grid, p.block, 0, as_stream(stream), a);
   return note_launch(hipGetLastError(), "upconv_glu_mfma_kernel");
 }

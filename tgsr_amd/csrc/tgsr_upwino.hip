@@ -21,6 +21,7 @@
 // LDS-DMA issued from inline asm (see tgsr_winograd.hip); V [3 rows i][4 ci][16 tiles][4] is computed one stage
 // ahead by the two cout-half waves of a row (h = 0: rows i = 0, 1; h = 1: row i = 2) and shared through LDS.
 #include "tgsr_common.h"
+#include "tgsr_conv_plan.h"
 
 #include <type_traits>
 
@@ -361,44 +362,30 @@ extern "C" int64_t tgsr_packed_upwino_weight_elems(int Cout, int Cin) {
 }
 
 extern "C" int tgsr_pack_upwino_weight(const float* w, float* upack, int Cout, int Cin, int glu, void* stream) {
-  if (!w || !upack || Cout < 1 || Cin < 1) return TGSR_EINVAL;
-  if (Cout % 64 != 0) return TGSR_EUNSUPPORTED;
-  const int64_t total = tgsr_packed_upwino_weight_elems(Cout, Cin);
-  const int blocks = (int)((total + 255) / 256 < 2048 ? (total + 255) / 256 : 2048);
-  hipLaunchKernelGGL(pack_upwino_weight_kernel, dim3(blocks), dim3(256), 0, as_stream(stream), w, upack, Cout, Cin,
-                     glu ? 1 : 0, total);
-  return note_launch(hipGetLastError(), "pack_upwino_weight_kernel");
+  return launch_pack(pack_upwino_weight_kernel, "pack_upwino_weight_kernel", 64, 2048, tgsr_packed_upwino_weight_elems(Cout, Cin), stream, w,
+                     upack, Cout, Cin, glu ? 1 : 0);
 }
 
-static int upwino_launch(const float* x, int64_t x_bstride, int B, int Cin, int H, int W, const float* upack, int Cout,
-                         const float* scale, const float* shift, float* out, int64_t out_bstride, bool glu,
-                         void* stream) {
-  if (!x || !upack || !out || B < 1 || Cin < 1 || H < 1 || W < 1 || Cout < 1) return TGSR_EINVAL;
-  if ((scale == nullptr) != (shift == nullptr)) return TGSR_EINVAL;
-  if (Cout % 64 != 0 || Cin % kUCK != 0) return TGSR_EUNSUPPORTED;
-  if ((int64_t)H * W >= (1 << 26) || (int64_t)Cin * H * W >= (1ll << 32)) return TGSR_EUNSUPPORTED;
-  if ((W & 3) || (x_bstride & 3) || (reinterpret_cast<uintptr_t>(x) & 15) || (reinterpret_cast<uintptr_t>(out) & 7) ||
-      (out_bstride & 1))
-    return TGSR_EUNSUPPORTED;
+static int upwino_launch(const ConvCall& c, void* stream) {
+  static_assert(kUCK == kConvStage, "the plan's stage is the kernel's");
+  const ConvPlan p = conv_plan(TGSR_CONV_FORM_UPWINO, c);
+  if (p.status != TGSR_OK) return p.status;
   UpwArgs a;
-  a.x = x; a.xbs = x_bstride; a.B = B; a.Cin = Cin; a.H = H; a.W = W; a.upack = upack; a.Cout = Cout;
-  a.scale = scale; a.shift = shift; a.out = out; a.obs = out_bstride;
-  a.tiles_x = (W + 15) / 16; a.tiles_y = (H + 1) / 2; a.nstages = (Cin + kUCK - 1) / kUCK;
-  a.ngroups = Cout / 64;
-  dim3 grid((unsigned)(B * a.tiles_x * a.tiles_y * a.ngroups));
-  if (glu) hipLaunchKernelGGL(upwino_kernel<true>, grid, dim3(256), 0, as_stream(stream), a);
-  else hipLaunchKernelGGL(upwino_kernel<false>, grid, dim3(256), 0, as_stream(stream), a);
+  conv_fill(a, c, p);
+  a.upack = c.pack; a.nstages = p.stages; a.ngroups = p.groups;
+  if (p.t[0]) hipLaunchKernelGGL(upwino_kernel<true>, p.grid, p.block, 0, as_stream(stream), a);
+  else hipLaunchKernelGGL(upwino_kernel<false>, p.grid, p.block, 0, as_stream(stream), a);
   return note_launch(hipGetLastError(), "upwino_kernel");
 }
 
 extern "C" int tgsr_upwino_glu_fwd(const float* x, int64_t x_bstride, int B, int Cin, int H, int W, const float* upack,
                                    int Cout, const float* scale, const float* shift, float* out, int64_t out_bstride,
                                    void* stream) {
-  return upwino_launch(x, x_bstride, B, Cin, H, W, upack, Cout, scale, shift, out, out_bstride, true, stream);
+  return upwino_launch({x, x_bstride, B, Cin, H, W, upack, Cout, scale, shift, nullptr, 0, out, out_bstride, TGSR_EPI_AFFINE_GLU, 1, 0}, stream);
 }
 
 extern "C" int tgsr_upwino_fwd(const float* x, int64_t x_bstride, int B, int Cin, int H, int W, const float* upack,
                                int Cout, const float* scale, const float* shift, float* out, int64_t out_bstride,
                                void* stream) {
-  return upwino_launch(x, x_bstride, B, Cin, H, W, upack, Cout, scale, shift, out, out_bstride, false, stream);
+  return upwino_launch({x, x_bstride, B, Cin, H, W, upack, Cout, scale, shift, nullptr, 0, out, out_bstride, TGSR_EPI_AFFINE, 1, 0}, stream);
 }

@@ -33,6 +33,7 @@
 //   S   [4 rows of S = quads][4 ci][16 tiles][4] (4 KB, double buffered): wave cb computes row cb.
 // LDS 15 KB.  GLU channel blocks as in tgsr_winograd4.hip (value, value, gate, gate per lane).
 #include "tgsr_common.h"
+#include "tgsr_conv_plan.h"
 
 #include <type_traits>
 
@@ -340,30 +341,21 @@ extern "C" int64_t tgsr_packed_upwino4_weight_elems(int Cout, int Cin) {
 }
 
 extern "C" int tgsr_pack_upwino4_weight(const float* w, float* upack, int Cout, int Cin, int glu, void* stream) {
-  if (!w || !upack || Cout < 1 || Cin < 1) return TGSR_EINVAL;
-  if (Cout % 64 != 0) return TGSR_EUNSUPPORTED;
-  const int64_t total = tgsr_packed_upwino4_weight_elems(Cout, Cin);
-  const int blocks = (int)((total + 255) / 256 < 2048 ? (total + 255) / 256 : 2048);
-  hipLaunchKernelGGL(pack_upwino4_weight_kernel, dim3(blocks), dim3(256), 0, as_stream(stream), w, upack, Cout, Cin, glu ? 1 : 0,
-                     total);
-  return note_launch(hipGetLastError(), "pack_upwino4_weight_kernel");
+  return launch_pack(pack_upwino4_weight_kernel, "pack_upwino4_weight_kernel", 64, 2048, tgsr_packed_upwino4_weight_elems(Cout, Cin), stream,
+                     w, upack, Cout, Cin, glu ? 1 : 0);
 }
 
 extern "C" int tgsr_upwino4_fwd(const float* x, int64_t x_bstride, int B, int Cin, int H, int W, const float* upack, int Cout,
                                 const float* scale, const float* shift, float* out, int64_t out_bstride, int glu, void* stream) {
-  if (!x || !upack || !out || B < 1 || Cin < 1 || H < 1 || W < 1 || Cout < 1) return TGSR_EINVAL;
-  if ((scale == nullptr) != (shift == nullptr)) return TGSR_EINVAL;
-  if (Cout % 64 != 0 || Cin % (2 * ku4CK) != 0) return TGSR_EUNSUPPORTED;          // an even number of 4-channel stages
-  if ((int64_t)H * W >= (1 << 26) || (int64_t)Cin * H * W >= (1ll << 32)) return TGSR_EUNSUPPORTED;
-  if ((W & 3) || (x_bstride & 3) || (reinterpret_cast<uintptr_t>(x) & 15) || (reinterpret_cast<uintptr_t>(out) & 15) ||
-      (reinterpret_cast<uintptr_t>(upack) & 15) || (out_bstride & 3))
-    return TGSR_EUNSUPPORTED;
+  static_assert(ku4CK == kConvStage, "the plan's stage is the kernel's");
+  const ConvCall c{x, x_bstride, B, Cin, H, W, upack, Cout, scale, shift, nullptr, 0, out, out_bstride,
+                   glu ? TGSR_EPI_AFFINE_GLU : TGSR_EPI_AFFINE, 1, 0};
+  const ConvPlan p = conv_plan(TGSR_CONV_FORM_UPWINO4, c);
+  if (p.status != TGSR_OK) return p.status;
   Upw4Args a;
-  a.x = x; a.xbs = x_bstride; a.B = B; a.Cin = Cin; a.H = H; a.W = W; a.upack = upack; a.Cout = Cout;
-  a.scale = scale; a.shift = shift; a.out = out; a.obs = out_bstride;
-  a.tiles_x = (2 * W + 63) / 64; a.tiles_y = (2 * H + 3) / 4; a.nstages = Cin / ku4CK; a.ngroups = Cout / 64;
-  const dim3 grid((unsigned)(B * a.tiles_x * a.tiles_y * a.ngroups));
-  if (glu) hipLaunchKernelGGL((upwino4_kernel<true>), grid, dim3(256), 0, as_stream(stream), a);
-  else hipLaunchKernelGGL((upwino4_kernel<false>), grid, dim3(256), 0, as_stream(stream), a);
+  conv_fill(a, c, p);
+  a.upack = upack; a.nstages = p.stages; a.ngroups = p.groups;
+  if (p.t[0]) hipLaunchKernelGGL((upwino4_kernel<true>), p.grid, p.block, 0, as_stream(stream), a);
+  else hipLaunchKernelGGL((upwino4_kernel<false>), p.grid, p.block, 0, as_stream(stream), a);
   return note_launch(hipGetLastError(), "upwino4_kernel");
 }

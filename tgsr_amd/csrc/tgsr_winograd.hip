@@ -9,6 +9,7 @@
 //
 // Mapping: see the geometry comment above the kernel.
 #include "tgsr_common.h"
+#include "tgsr_conv_plan.h"
 
 #include <cstdlib>
 #include <type_traits>
@@ -478,13 +479,8 @@ extern "C" int64_t tgsr_packed_wino_weight_elems(int Cout, int Cin) {
 }
 
 static int pack_wino_weight(const float* w, float* upack, int Cout, int Cin, int glu, int tr, void* stream) {
-  if (!w || !upack || Cout < 1 || Cin < 1) return TGSR_EINVAL;
-  if (Cout % 32 != 0) return TGSR_EUNSUPPORTED;
-  const int64_t total = tgsr_packed_wino_weight_elems(Cout, Cin);
-  const int blocks = (int)((total + 255) / 256 < 2048 ? (total + 255) / 256 : 2048);
-  hipLaunchKernelGGL(pack_wino_weight_kernel, dim3(blocks), dim3(256), 0, as_stream(stream), w, upack, Cout, Cin,
-                     glu ? 1 : 0, Cout % 64 == 0 ? 2 : 1, tr, total);
-  return note_launch(hipGetLastError(), "pack_wino_weight_kernel");
+  return launch_pack(pack_wino_weight_kernel, "pack_wino_weight_kernel", 32, 2048, tgsr_packed_wino_weight_elems(Cout, Cin), stream, w, upack,
+                     Cout, Cin, glu ? 1 : 0, Cout % 64 == 0 ? 2 : 1, tr);
 }
 
 extern "C" int tgsr_pack_wino_weight(const float* w, float* upack, int Cout, int Cin, int glu, void* stream) {
@@ -495,53 +491,31 @@ extern "C" int tgsr_pack_wino_weight_dgrad(const float* w, float* upack, int Cou
   return pack_wino_weight(w, upack, Cout, Cin, 0, 1, stream);
 }
 
-static void wino_geometry(int B, int Cin, int H, int W, int Cout, WinoArgs& a) {
-  const int nh = Cout % 64 == 0 ? 2 : 1;                 // cout halves per workgroup: 64- or 32-channel groups
-  a.tiles_x = (W + 31) / 32; a.tiles_y = nh == 2 ? (H + 3) / 4 : (H + 7) / 8; a.nstages = (Cin + kWCK - 1) / kWCK;
-  a.ngroups = Cout / (32 * nh);
-  a.nslots = B * a.tiles_y * a.tiles_x * (nh == 2 ? 2 : 4);
-}
-
 extern "C" int tgsr_wino_stats_nslots(int B, int H, int W, int Cout) {
-  if (B < 1 || H < 1 || W < 1 || Cout < 1 || Cout % 32 != 0) return 0;
-  WinoArgs a;
-  wino_geometry(B, 4, H, W, Cout, a);
-  return a.nslots;
+  return conv_tiles(TGSR_CONV_FORM_WINO, B, H, W, Cout, TGSR_EPI_AFFINE, 0, 1).nslots;
 }
 
-static int wino_conv3x3(const float* x, int64_t x_bstride, int B, int Cin, int H, int W, const float* upack, int Cout,
-                        const float* scale, const float* shift, const float* residual, int64_t res_bstride, float* out,
-                        int64_t out_bstride, int epilogue, float* stat, void* stream) {
-  if (!x || !upack || !out || B < 1 || Cin < 1 || H < 1 || W < 1 || Cout < 1) return TGSR_EINVAL;
-  if ((scale == nullptr) != (shift == nullptr)) return TGSR_EINVAL;
-  const bool glu = epilogue == TGSR_EPI_AFFINE_GLU;
-  if (!glu && epilogue != TGSR_EPI_AFFINE) return TGSR_EINVAL;
-  if (glu && residual) return TGSR_EINVAL;
-  if (Cout % 32 != 0 || Cin % kWCK != 0) return TGSR_EUNSUPPORTED;
-  if ((int64_t)H * W >= (1 << 28) || (int64_t)Cin * H * W >= (1ll << 32)) return TGSR_EUNSUPPORTED;
-  if ((W & 3) || (x_bstride & 3) || (reinterpret_cast<uintptr_t>(x) & 15) || (reinterpret_cast<uintptr_t>(out) & 7) || (out_bstride & 1) ||
-      (residual && ((reinterpret_cast<uintptr_t>(residual) & 7) || (res_bstride & 1))))
-    return TGSR_EUNSUPPORTED;
+// stat != NULL: the statistics entry (plain epilogue, no affine, no residual)
+static int wino_conv3x3(const ConvCall& c, float* stat, void* stream) {
+  static_assert(kWCK == kConvStage && WinoGeo<2>::ROWS == 2 && WinoGeo<1>::ROWS == 4, "the plan's stage and tile rows are the kernel's");
+  const ConvPlan p = conv_plan(TGSR_CONV_FORM_WINO, c);
+  if (p.status != TGSR_OK) return p.status;
   WinoArgs a;
-  a.x = x; a.xbs = x_bstride; a.B = B; a.Cin = Cin; a.H = H; a.W = W; a.upack = upack; a.Cout = Cout;
-  a.scale = scale; a.shift = shift; a.res = residual; a.rbs = res_bstride; a.out = out; a.obs = out_bstride;
-  const int nh = Cout % 64 == 0 ? 2 : 1;
-  wino_geometry(B, Cin, H, W, Cout, a);
-  a.stat = stat;
-  if (stat && (glu || residual || scale)) return TGSR_EINVAL;     // statistics are of the raw convolution output
-  dim3 grid((unsigned)(B * a.tiles_x * a.tiles_y * a.ngroups));
+  conv_fill(a, c, p);
+  a.upack = c.pack; a.res = c.res; a.rbs = c.rbs; a.nstages = p.stages; a.ngroups = p.groups; a.stat = stat; a.nslots = p.nslots;
   size_t dyn = 0;
 #ifdef TGSR_WINO_STAMPS
   if (const char* e = getenv("TGSR_WINO_DYN")) dyn = (size_t)atoi(e);   // diagnostic: extra LDS to force 1 workgroup per CU
 #endif
-  if (nh == 2) {
-    if (glu) hipLaunchKernelGGL((wino_conv3x3_kernel<true, 2>), grid, dim3(256), dyn, as_stream(stream), a);
-    else if (stat) hipLaunchKernelGGL((wino_conv3x3_kernel<false, 2, true>), grid, dim3(256), dyn, as_stream(stream), a);
-    else hipLaunchKernelGGL((wino_conv3x3_kernel<false, 2>), grid, dim3(256), dyn, as_stream(stream), a);
-  } else {
-    if (glu) hipLaunchKernelGGL((wino_conv3x3_kernel<true, 1>), grid, dim3(256), dyn, as_stream(stream), a);
-    else if (stat) hipLaunchKernelGGL((wino_conv3x3_kernel<false, 1, true>), grid, dim3(256), dyn, as_stream(stream), a);
-    else hipLaunchKernelGGL((wino_conv3x3_kernel<false, 1>), grid, dim3(256), dyn, as_stream(stream), a);
+  hipStream_t s = as_stream(stream);
+  switch (p.t[1] * 10 + p.t[0] * 2 + p.t[2]) {           // <GLU, NH, STATS>
+    case 22: hipLaunchKernelGGL((wino_conv3x3_kernel<true, 2>), p.grid, p.block, dyn, s, a); break;
+    case 21: hipLaunchKernelGGL((wino_conv3x3_kernel<false, 2, true>), p.grid, p.block, dyn, s, a); break;
+    case 20: hipLaunchKernelGGL((wino_conv3x3_kernel<false, 2>), p.grid, p.block, dyn, s, a); break;
+    case 12: hipLaunchKernelGGL((wino_conv3x3_kernel<true, 1>), p.grid, p.block, dyn, s, a); break;
+    case 11: hipLaunchKernelGGL((wino_conv3x3_kernel<false, 1, true>), p.grid, p.block, dyn, s, a); break;
+    case 10: hipLaunchKernelGGL((wino_conv3x3_kernel<false, 1>), p.grid, p.block, dyn, s, a); break;
+    default: return note_error("wino_conv3x3_kernel", "the plan names no instance", 0);
   }
   return note_launch(hipGetLastError(), "wino_conv3x3_kernel");
 }
@@ -550,14 +524,14 @@ extern "C" int tgsr_wino_conv3x3_fwd(const float* x, int64_t x_bstride, int B, i
                                      const float* upack, int Cout, const float* scale, const float* shift,
                                      const float* residual, int64_t res_bstride, float* out, int64_t out_bstride,
                                      int epilogue, void* stream) {
-  return wino_conv3x3(x, x_bstride, B, Cin, H, W, upack, Cout, scale, shift, residual, res_bstride, out, out_bstride,
-                      epilogue, nullptr, stream);
+  return wino_conv3x3({x, x_bstride, B, Cin, H, W, upack, Cout, scale, shift, residual, res_bstride, out, out_bstride, epilogue, 0, 0},
+                      nullptr, stream);
 }
 
 extern "C" int tgsr_wino_conv3x3_stats_fwd(const float* x, int64_t x_bstride, int B, int Cin, int H, int W,
                                            const float* upack, int Cout, float* out, int64_t out_bstride,
                                            float* stat_partial, void* stream) {
   if (!stat_partial) return TGSR_EINVAL;
-  return wino_conv3x3(x, x_bstride, B, Cin, H, W, upack, Cout, nullptr, nullptr, nullptr, 0, out, out_bstride,
-                      TGSR_EPI_AFFINE, stat_partial, stream);
+  return wino_conv3x3({x, x_bstride, B, Cin, H, W, upack, Cout, nullptr, nullptr, nullptr, 0, out, out_bstride, TGSR_EPI_AFFINE, 0, 1},
+                      stat_partial, stream);
 }

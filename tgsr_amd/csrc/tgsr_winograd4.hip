@@ -30,6 +30,7 @@
 // GLU: a channel block holds 8 value channels and their 8 gates, ordered so that a lane's four accumulator registers
 // are (value, value, gate, gate) of two output channels - the gate never leaves the lane.
 #include "tgsr_common.h"
+#include "tgsr_conv_plan.h"
 
 #include <type_traits>
 
@@ -806,13 +807,8 @@ extern "C" int64_t tgsr_packed_wino4_weight_elems(int Cout, int Cin) {
 }
 
 static int pack_wino4_weight(const float* w, float* upack, int Cout, int Cin, int glu, int tr, void* stream) {
-  if (!w || !upack || Cout < 1 || Cin < 1) return TGSR_EINVAL;
-  if (Cout % 64 != 0) return TGSR_EUNSUPPORTED;
-  const int64_t total = tgsr_packed_wino4_weight_elems(Cout, Cin);
-  const int blocks = (int)((total + 255) / 256 < 2048 ? (total + 255) / 256 : 2048);
-  hipLaunchKernelGGL(pack_wino4_weight_kernel, dim3(blocks), dim3(256), 0, as_stream(stream), w, upack, Cout, Cin, glu ? 1 : 0, tr,
-                     total);
-  return note_launch(hipGetLastError(), "pack_wino4_weight_kernel");
+  return launch_pack(pack_wino4_weight_kernel, "pack_wino4_weight_kernel", 64, 2048, tgsr_packed_wino4_weight_elems(Cout, Cin), stream, w,
+                     upack, Cout, Cin, glu ? 1 : 0, tr);
 }
 
 extern "C" int tgsr_pack_wino4_weight(const float* w, float* upack, int Cout, int Cin, int glu, void* stream) {
@@ -823,66 +819,52 @@ extern "C" int tgsr_pack_wino4_weight_dgrad(const float* w, float* upack, int Co
   return pack_wino4_weight(w, upack, Cout, Cin, 0, 1, stream);
 }
 
-static void wino4_geometry(int B, int Cin, int H, int W, int Cout, Wino4Args& a) {
-  a.tiles_x = (W + 63) / 64; a.tiles_y = (H + 7) / 8; a.nstages = Cin / k4CK; a.ngroups = Cout / 64;
-  a.nslots = B * a.tiles_y * a.tiles_x * 2;
-}
-
 extern "C" int tgsr_wino4_stats_nslots(int B, int H, int W, int Cout) {
-  if (B < 1 || H < 1 || W < 1 || Cout < 1 || Cout % 64 != 0) return 0;
-  Wino4Args a;
-  wino4_geometry(B, 4, H, W, Cout, a);
-  return a.nslots;
+  return conv_tiles(TGSR_CONV_FORM_WINO4, B, H, W, Cout, TGSR_EPI_AFFINE, 0, 1).nslots;
 }
 
-static int wino4_conv3x3(const float* x, int64_t x_bstride, int B, int Cin, int H, int W, const float* upack, int Cout,
-                         const float* scale, const float* shift, const float* residual, int64_t res_bstride, float* out,
-                         int64_t out_bstride, int epilogue, float* stat, void* stream) {
-  if (!x || !upack || !out || B < 1 || Cin < 1 || H < 1 || W < 1 || Cout < 1) return TGSR_EINVAL;
-  if ((scale == nullptr) != (shift == nullptr)) return TGSR_EINVAL;
-  const bool glu = epilogue == TGSR_EPI_AFFINE_GLU;
-  if (!glu && epilogue != TGSR_EPI_AFFINE) return TGSR_EINVAL;
-  if (glu && residual) return TGSR_EINVAL;
-  if (stat && (glu || residual || scale)) return TGSR_EINVAL;     // statistics are of the raw convolution output
-  if (Cout % 64 != 0 || Cin % k4CK != 0) return TGSR_EUNSUPPORTED;
-  if ((int64_t)H * W >= (1 << 28) || (int64_t)Cin * H * W >= (1ll << 32)) return TGSR_EUNSUPPORTED;
-  if ((W & 3) || (x_bstride & 3) || (reinterpret_cast<uintptr_t>(x) & 15) || (reinterpret_cast<uintptr_t>(out) & 15) ||
-      (out_bstride & 3) || (residual && ((reinterpret_cast<uintptr_t>(residual) & 15) || (res_bstride & 3))))
-    return TGSR_EUNSUPPORTED;
+// Both kernels' launcher (form = TGSR_CONV_FORM_WINO4 | _WINO4W).  stat != NULL: the statistics entry (plain epilogue, no affine, no residual)
+static int wino4_launch(int form, const ConvCall& c, float* stat, void* stream) {
+  static_assert(k4CK == kConvStage && k4TR == 8 + 2 && k4TC == 64 + 8, "the plan's stage and tile are the kernels'");
+  const ConvPlan p = conv_plan(form, c);
+  if (p.status != TGSR_OK) return p.status;
+  const bool wide = form == TGSR_CONV_FORM_WINO4W;
   Wino4Args a;
-  a.x = x; a.xbs = x_bstride; a.B = B; a.Cin = Cin; a.H = H; a.W = W; a.upack = upack; a.Cout = Cout;
-  a.scale = scale; a.shift = shift; a.res = residual; a.rbs = res_bstride; a.out = out; a.obs = out_bstride;
-  wino4_geometry(B, Cin, H, W, Cout, a);
-  a.stat = stat;
-  const dim3 grid((unsigned)(B * a.tiles_x * a.tiles_y * a.ngroups));
-  if (glu) hipLaunchKernelGGL((wino4_conv3x3_kernel<true>), grid, dim3(512), 0, as_stream(stream), a);
-  else if (stat) hipLaunchKernelGGL((wino4_conv3x3_kernel<false, true>), grid, dim3(512), 0, as_stream(stream), a);
-  else hipLaunchKernelGGL((wino4_conv3x3_kernel<false>), grid, dim3(512), 0, as_stream(stream), a);
-  return note_launch(hipGetLastError(), "wino4_conv3x3_kernel");
+  conv_fill(a, c, p);
+  a.upack = c.pack; a.res = c.res; a.rbs = c.rbs; a.nstages = p.stages; a.ngroups = p.groups; a.stat = stat; a.nslots = p.nslots;
+  hipStream_t s = as_stream(stream);
+  switch ((wide ? p.t[1] * 10 : 0) + p.t[0] * 2 + p.t[wide ? 2 : 1]) {           // <GLU, STATS> | <GLU, NB, STATS>
+    case 2: hipLaunchKernelGGL((wino4_conv3x3_kernel<true>), p.grid, p.block, 0, s, a); break;
+    case 1: hipLaunchKernelGGL((wino4_conv3x3_kernel<false, true>), p.grid, p.block, 0, s, a); break;
+    case 0: hipLaunchKernelGGL((wino4_conv3x3_kernel<false>), p.grid, p.block, 0, s, a); break;
+    case 82: hipLaunchKernelGGL((wino4w_conv3x3_kernel<true, 8>), p.grid, p.block, 0, s, a); break;
+    case 81: hipLaunchKernelGGL((wino4w_conv3x3_kernel<false, 8, true>), p.grid, p.block, 0, s, a); break;
+    case 80: hipLaunchKernelGGL((wino4w_conv3x3_kernel<false, 8>), p.grid, p.block, 0, s, a); break;
+    case 42: hipLaunchKernelGGL((wino4w_conv3x3_kernel<true, 4>), p.grid, p.block, 0, s, a); break;
+    case 41: hipLaunchKernelGGL((wino4w_conv3x3_kernel<false, 4, true>), p.grid, p.block, 0, s, a); break;
+    case 40: hipLaunchKernelGGL((wino4w_conv3x3_kernel<false, 4>), p.grid, p.block, 0, s, a); break;
+    default: return note_error("wino4_conv3x3_kernel", "the plan names no instance", 0);
+  }
+  return note_launch(hipGetLastError(), wide ? "wino4w_conv3x3_kernel" : "wino4_conv3x3_kernel");
 }
 
 extern "C" int tgsr_wino4_conv3x3_fwd(const float* x, int64_t x_bstride, int B, int Cin, int H, int W, const float* upack,
                                       int Cout, const float* scale, const float* shift, const float* residual,
                                       int64_t res_bstride, float* out, int64_t out_bstride, int epilogue, void* stream) {
-  return wino4_conv3x3(x, x_bstride, B, Cin, H, W, upack, Cout, scale, shift, residual, res_bstride, out, out_bstride, epilogue,
-                       nullptr, stream);
+  return wino4_launch(TGSR_CONV_FORM_WINO4, {x, x_bstride, B, Cin, H, W, upack, Cout, scale, shift, residual, res_bstride, out, out_bstride,
+                                             epilogue, 0, 0}, nullptr, stream);
 }
 
 extern "C" int tgsr_wino4_conv3x3_stats_fwd(const float* x, int64_t x_bstride, int B, int Cin, int H, int W, const float* upack,
                                             int Cout, float* out, int64_t out_bstride, float* stat_partial, void* stream) {
   if (!stat_partial) return TGSR_EINVAL;
-  return wino4_conv3x3(x, x_bstride, B, Cin, H, W, upack, Cout, nullptr, nullptr, nullptr, 0, out, out_bstride, TGSR_EPI_AFFINE,
-                       stat_partial, stream);
+  return wino4_launch(TGSR_CONV_FORM_WINO4, {x, x_bstride, B, Cin, H, W, upack, Cout, nullptr, nullptr, nullptr, 0, out, out_bstride,
+                                             TGSR_EPI_AFFINE, 0, 1}, stat_partial, stream);
 }
 
 static int pack_wino4_wide_weight(const float* w, float* upack, int Cout, int Cin, int glu, int tr, void* stream) {
-  if (!w || !upack || Cout < 1 || Cin < 1) return TGSR_EINVAL;
-  if (Cout % 64 != 0) return TGSR_EUNSUPPORTED;
-  const int64_t total = tgsr_packed_wino4_weight_elems(Cout, Cin);
-  const int blocks = (int)((total + 255) / 256 < 2048 ? (total + 255) / 256 : 2048);
-  hipLaunchKernelGGL(pack_wino4w_weight_kernel, dim3(blocks), dim3(256), 0, as_stream(stream), w, upack, Cout, Cin, glu ? 1 : 0,
-                     Cout % 128 == 0 ? 8 : 4, tr, total);
-  return note_launch(hipGetLastError(), "pack_wino4w_weight_kernel");
+  return launch_pack(pack_wino4w_weight_kernel, "pack_wino4w_weight_kernel", 64, 2048, tgsr_packed_wino4_weight_elems(Cout, Cin), stream, w,
+                     upack, Cout, Cin, glu ? 1 : 0, Cout % 128 == 0 ? 8 : 4, tr);
 }
 
 extern "C" int tgsr_pack_wino4_wide_weight(const float* w, float* upack, int Cout, int Cin, int glu, void* stream) {
@@ -893,56 +875,21 @@ extern "C" int tgsr_pack_wino4_wide_weight_dgrad(const float* w, float* upack, i
   return pack_wino4_wide_weight(w, upack, Cout, Cin, 0, 1, stream);
 }
 
-static int wino4_wide_conv3x3(const float* x, int64_t x_bstride, int B, int Cin, int H, int W, const float* upack, int Cout,
-                              const float* scale, const float* shift, const float* residual, int64_t res_bstride, float* out,
-                              int64_t out_bstride, int epilogue, float* stat, void* stream) {
-  if (!x || !upack || !out || B < 1 || Cin < 1 || H < 1 || W < 1 || Cout < 1) return TGSR_EINVAL;
-  if ((scale == nullptr) != (shift == nullptr)) return TGSR_EINVAL;
-  const bool glu = epilogue == TGSR_EPI_AFFINE_GLU;
-  if (!glu && epilogue != TGSR_EPI_AFFINE) return TGSR_EINVAL;
-  if (glu && residual) return TGSR_EINVAL;
-  if (stat && (glu || residual || scale)) return TGSR_EINVAL;     // statistics are of the raw convolution output
-  if (Cout % 64 != 0 || Cin % (2 * k4CK) != 0) return TGSR_EUNSUPPORTED;       // an even number of 4-channel stages
-  if ((int64_t)H * W >= (1 << 28) || (int64_t)Cin * H * W >= (1ll << 32)) return TGSR_EUNSUPPORTED;
-  if ((W & 3) || (x_bstride & 3) || (reinterpret_cast<uintptr_t>(x) & 15) || (reinterpret_cast<uintptr_t>(out) & 15) ||
-      (reinterpret_cast<uintptr_t>(upack) & 15) || (out_bstride & 3) ||
-      (residual && ((reinterpret_cast<uintptr_t>(residual) & 15) || (res_bstride & 3))))
-    return TGSR_EUNSUPPORTED;
-  const int nb = Cout % 128 == 0 ? 8 : 4;                  // 128-row groups where the layer has them, else 64-row groups
-  Wino4Args a;
-  a.x = x; a.xbs = x_bstride; a.B = B; a.Cin = Cin; a.H = H; a.W = W; a.upack = upack; a.Cout = Cout;
-  a.scale = scale; a.shift = shift; a.res = residual; a.rbs = res_bstride; a.out = out; a.obs = out_bstride;
-  a.tiles_x = (W + 63) / 64; a.tiles_y = (H + 3) / 4; a.nstages = Cin / k4CK; a.ngroups = Cout / (16 * nb);
-  a.stat = stat; a.nslots = B * a.tiles_y * a.tiles_x;
-  const dim3 grid((unsigned)(B * a.tiles_x * a.tiles_y * a.ngroups));
-  if (nb == 8) {
-    if (glu) hipLaunchKernelGGL((wino4w_conv3x3_kernel<true, 8>), grid, dim3(512), 0, as_stream(stream), a);
-    else if (stat) hipLaunchKernelGGL((wino4w_conv3x3_kernel<false, 8, true>), grid, dim3(512), 0, as_stream(stream), a);
-    else hipLaunchKernelGGL((wino4w_conv3x3_kernel<false, 8>), grid, dim3(512), 0, as_stream(stream), a);
-  } else {
-    if (glu) hipLaunchKernelGGL((wino4w_conv3x3_kernel<true, 4>), grid, dim3(256), 0, as_stream(stream), a);
-    else if (stat) hipLaunchKernelGGL((wino4w_conv3x3_kernel<false, 4, true>), grid, dim3(256), 0, as_stream(stream), a);
-    else hipLaunchKernelGGL((wino4w_conv3x3_kernel<false, 4>), grid, dim3(256), 0, as_stream(stream), a);
-  }
-  return note_launch(hipGetLastError(), "wino4w_conv3x3_kernel");
-}
-
 extern "C" int tgsr_wino4_wide_conv3x3_fwd(const float* x, int64_t x_bstride, int B, int Cin, int H, int W, const float* upack,
                                            int Cout, const float* scale, const float* shift, const float* residual,
                                            int64_t res_bstride, float* out, int64_t out_bstride, int epilogue, void* stream) {
-  return wino4_wide_conv3x3(x, x_bstride, B, Cin, H, W, upack, Cout, scale, shift, residual, res_bstride, out, out_bstride,
-                            epilogue, nullptr, stream);
+  return wino4_launch(TGSR_CONV_FORM_WINO4W, {x, x_bstride, B, Cin, H, W, upack, Cout, scale, shift, residual, res_bstride, out, out_bstride,
+                                              epilogue, 0, 0}, nullptr, stream);
 }
 
 extern "C" int tgsr_wino4_wide_stats_nslots(int B, int H, int W, int Cout) {
-  if (B < 1 || H < 1 || W < 1 || Cout < 1 || Cout % 64 != 0) return 0;
-  return B * ((H + 3) / 4) * ((W + 63) / 64);
+  return conv_tiles(TGSR_CONV_FORM_WINO4W, B, H, W, Cout, TGSR_EPI_AFFINE, 0, 1).nslots;
 }
 
 extern "C" int tgsr_wino4_wide_conv3x3_stats_fwd(const float* x, int64_t x_bstride, int B, int Cin, int H, int W,
                                                  const float* upack, int Cout, float* out, int64_t out_bstride,
                                                  float* stat_partial, void* stream) {
   if (!stat_partial) return TGSR_EINVAL;
-  return wino4_wide_conv3x3(x, x_bstride, B, Cin, H, W, upack, Cout, nullptr, nullptr, nullptr, 0, out, out_bstride,
-                            TGSR_EPI_AFFINE, stat_partial, stream);
+  return wino4_launch(TGSR_CONV_FORM_WINO4W, {x, x_bstride, B, Cin, H, W, upack, Cout, nullptr, nullptr, nullptr, 0, out, out_bstride,
+                                              TGSR_EPI_AFFINE, 0, 1}, stat_partial, stream);
 }

@@ -97,8 +97,9 @@ def _nchw_bstride(t: torch.Tensor, name: str) -> Tuple[torch.Tensor, int]:
 #   up          the nearest x2 up-sampling is part of the kernel;  gate_only: it has the GLU epilogue only
 #   kernel      the name it reports to `profile`
 #   shape(cin, cout, H, W)   the shapes the kernel takes (H x W of the input)
-#   align       out / residual must start on this many bytes with batch strides that keep every image there (x: always 16 where
-#               a form has a requirement at all; 0: the kernel takes any address)
+#   align       out / residual must start on this many bytes with batch strides that keep every image there; 0: the kernel takes
+#               any address.  (x: 16 bytes for the Winograd forms, any address for direct and upconv.  csrc/tgsr_conv_plan.h holds the
+#               library's table of the same requirements; tests/test_infer_abi_host.py ties the two.)
 Form = collections.namedtuple("Form", "name what op op_plain pack_op fwd fwd_plain tail stats nslots pack pack_dgrad elems pack_arg "
                                       "up gate_only kernel shape align")
 
@@ -133,9 +134,11 @@ FORMS = {f.name: f for f in (
          "tgsr_pack_wino4_wide_weight", "tgsr_pack_wino4_wide_weight_dgrad", "tgsr_packed_wino4_weight_elems", "glu",
          False, False, "wino4w_conv3x3_kernel", lambda cin, cout, H, W: _wino4_shape(cin, cout, H, W) and _wino4_form(cin) == "wino4w", 16),
     # the upBlock forms: sub-pixel (four 2x2 convs on the pre-upsample tensor), Winograd F(2x2) and F(4x4) on the up-sampled grid
+    # (upconv's 8 bytes are the library's requirement, stated for whoever places `out`; conv3x3_form does not route on it: an `out` off
+    # 8 bytes there is the wrapper's error, as it always was)
     Form("upconv", "upconv3x3_glu", "upconv3x3_glu", None, None, "tgsr_upconv3x3_glu_fwd", None, "", None, None,
          "tgsr_pack_upconv_weight", None, "tgsr_packed_upconv_weight_elems", "",
-         True, True, "upconv_glu_mfma_kernel", lambda cin, cout, H, W: cout % 64 == 0, 0),
+         True, True, "upconv_glu_mfma_kernel", lambda cin, cout, H, W: cout % 64 == 0, 8),
     Form("upwino", "upwino_glu", "upwino_glu", "upwino", "pack_upwino_weight", "tgsr_upwino_glu_fwd", "tgsr_upwino_fwd", "", None, None,
          "tgsr_pack_upwino_weight", None, "tgsr_packed_upwino_weight_elems", "glu",
          True, False, "upwino_glu_kernel", lambda cin, cout, H, W: cout % 64 == 0 and cin % 4 == 0 and W % 4 == 0, 8),
