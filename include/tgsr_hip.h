@@ -405,6 +405,28 @@ int tgsr_func_attention_fwd(const float* query, const float* context, int B, int
                             float* weighted_context, float* attn, void* stream);
 
 /*
+ * Text-image retrieval (csrc/tgsr_retrieval.hip): N images scored against a candidate list of captions each.  Evaluation only, no
+ * backward.  No allocation, no synchronisation, no atomics (the same bits on every run); everything on `stream`, capturable.
+ * cand int32 [N][K] holds caption indices into a pool of M, or is NULL (then K must equal M and cand[n][k] = k).  A cand entry
+ * outside [0, M) is an EMPTY slot: nothing is read for it and sim = -inf.  N, M, K >= 1.
+ *
+ * tgsr_damsm_gallery_fwd  sim[n][k] = words_similarity of image n and caption cand[n][k] (losses.py:251-287, one entry per pair;
+ *     the value tgsr_damsm_words_fwd gives the pair, before gamma3).  words [M][ndf][Tw], cap_lens int32 [M] or NULL (= Tw; clamped
+ *     into [1, Tw] like tgsr_damsm_words_fwd), ctx [N][ndf][S].  Limits as tgsr_damsm_words_fwd: ndf % 32 == 0, 32 <= ndf <= 512,
+ *     Tw <= 32, S <= 320 (TGSR_EUNSUPPORTED otherwise).  One workgroup scores two neighbouring columns of a row; two captions of at
+ *     most 16 words share one MFMA tile.  sim for an (image, caption) pair is the same bits wherever the pair stands in cand.
+ * tgsr_sent_gallery_fwd   sim[n][k] = gamma3 * <cnn[n], rnn[c]> / max(|cnn[n]| * |rnn[c]|, eps), c = cand[n][k]  (losses.py:234-250);
+ *     cnn [N][ndf], rnn [M][ndf], ndf >= 1.
+ * tgsr_retrieval_ranks    rank[n] = #{k : sim[n][k] > sim[n][t]} + #{k < t : sim[n][k] == sim[n][t]}, t = target[n]: the position of
+ *     column t in a stable descending sort of row n; target[n] outside [0, K) -> rank[n] = -1.  sim [N][K] row-major, K >= 1.
+ */
+int tgsr_damsm_gallery_fwd(const float* words, const int32_t* cap_lens, const float* ctx, const int32_t* cand, int N, int M,
+                           int K, int ndf, int Tw, int S, float gamma1, float gamma2, float* sim, void* stream);
+int tgsr_sent_gallery_fwd(const float* cnn, const float* rnn, const int32_t* cand, int N, int M, int K, int ndf, float eps,
+                          float gamma3, float* sim, void* stream);
+int tgsr_retrieval_ranks(const float* sim, const int32_t* target, int N, int K, int32_t* rank, void* stream);
+
+/*
  * The two trainable heads of CNN_ENCODER (util.py:300-301, 364-367) as fp32 MFMA GEMMs with bias:
  * tgsr_conv1x1_fwd : emb_features, conv1x1 Cin -> Cout on [B][Cin][S] (S = ih*iw, 17*17) -> out [B][Cout][S]
  * tgsr_linear_fwd  : emb_cnn_code, out[b][o] = sum_k w[o][k] x[b][k] + bias[o]; x [B][K], w [Cout][K]

@@ -436,6 +436,17 @@ damsm_words_bwd = _define("damsm_words_bwd(Tensor img_features, Tensor words_emb
 func_attention = _define("func_attention(Tensor query, Tensor context, float gamma1) -> (Tensor, Tensor)",
                          lambda q, c, g1: ops.func_attention(q, c, g1),
                          lambda q, c, g1: (torch.empty_like(q), q.new_empty(q.shape[0], q.shape[2], c.shape[2], c.shape[3])))
+# text-image retrieval (tgsr_amd.retrieval reads them; evaluation only, no autograd formula): similarities of N images against candidate
+# captions out of a pool of M (`cand` int [N, K], -1 = an empty slot; None = every caption), and the rank of a target column per row
+damsm_gallery = _define("damsm_gallery(Tensor img_features, Tensor words_emb, int[] cap_lens, float gamma1, float gamma2, "
+                        "Tensor? cand=None) -> Tensor",
+                        lambda f, w, lens, g1, g2, cand=None: ops.damsm_gallery(f, w, list(lens), g1, g2, cand),
+                        lambda f, w, lens, g1, g2, cand=None: f.new_empty(f.shape[0], w.shape[0] if cand is None else cand.shape[1]))
+sent_gallery = _define("sent_gallery(Tensor cnn_code, Tensor rnn_code, float eps, float gamma3, Tensor? cand=None) -> Tensor",
+                       lambda x, y, eps, g3, cand=None: ops.sent_gallery(x, y, eps, g3, cand),
+                       lambda x, y, eps, g3, cand=None: x.new_empty(x.shape[0], y.shape[0] if cand is None else cand.shape[1]))
+retrieval_ranks = _define("retrieval_ranks(Tensor sim, Tensor target) -> Tensor", lambda sim, t: ops.retrieval_ranks(sim, t),
+                          lambda sim, t: sim.new_empty(sim.shape[0], dtype=torch.int32))
 
 
 # ------------------------------------------------------------------------------------------------ CA_NET (inference)

@@ -78,6 +78,30 @@ def words_loss(img_features, words_emb, labels, cap_lens, class_ids, batch_size)
     return loss0, loss1, att_maps
 
 
+def sent_similarity(cnn_code, rnn_code, eps=1e-8):
+    """losses.py:234-250: the gamma3-scaled cosine of every image code [N, D] with every sentence code [M, D] -> [N, M] (the
+    reference's [1, b, D] form is the same matrix), one launch of the gallery kernel (tgsr_sent_gallery_fwd).  An evaluation
+    function: the result carries no grad_fn (`sent_loss` is the differentiable form)."""
+    if cnn_code.dim() == 3 and cnn_code.shape[0] == 1:
+        cnn_code, rnn_code = cnn_code[0], rnn_code[0]
+    if cnn_code.dim() != 2 or rnn_code.dim() != 2:
+        raise ValueError("sent_similarity: [b, D] or [1, b, D] codes expected, got %s and %s" % (tuple(cnn_code.shape), tuple(rnn_code.shape)))
+    return C.sent_gallery(cnn_code.detach(), rnn_code.detach(), float(eps), float(cfg.TRAIN.SMOOTH.GAMMA3), None)
+
+
+def words_similarity(img_features, words_emb, cap_lens, batch_size):
+    """losses.py:251-287: similarities[j][i] = log sum_w exp(gamma2 * cos(word_w of caption i, its region context in image j)) for the
+    first `batch_size` captions -> [b, batch_size], not scaled by gamma3 (the reference's callers do that).  The per-caption Python
+    loop is one launch of the gallery kernel (tgsr_damsm_gallery_fwd).  An evaluation function: the result carries no grad_fn
+    (`words_loss` is the differentiable form)."""
+    lens = cap_lens.data.tolist() if torch.is_tensor(cap_lens) else list(cap_lens)
+    batch_size = int(batch_size)
+    if batch_size < 1 or batch_size > words_emb.shape[0] or batch_size > len(lens):
+        raise ValueError("words_similarity: batch_size %d against %d captions and %d lengths" % (batch_size, words_emb.shape[0], len(lens)))
+    return C.damsm_gallery(img_features.detach(), words_emb.detach()[:batch_size], [int(v) for v in lens[:batch_size]],
+                           float(cfg.TRAIN.SMOOTH.GAMMA1), float(cfg.TRAIN.SMOOTH.GAMMA2), None)
+
+
 def MSE(fake, label):
     """losses.py:779-784: sum over the image scales of the mean squared error."""
     return sum(F.mse_loss(f, t) for f, t in zip(fake, label))

@@ -926,6 +926,92 @@ def func_attention(query: torch.Tensor, context: torch.Tensor, gamma1: float):
     return wc, attn
 
 
+# ----------------------------------------------------------------------------------------- text-image retrieval
+def check_candidates(cand: torch.Tensor, N: int, M: int) -> torch.Tensor:
+    """The host check of a CPU candidate table: int [N, K] with entries in [-1, M) (-1 = an empty slot).  Returns it as a
+    contiguous int32 tensor, still on the host."""
+    if cand.is_cuda:
+        raise TgsrError("check_candidates reads a host tensor (a device table is taken as it is)")
+    if cand.dtype not in (torch.int32, torch.int64) or cand.dim() != 2 or cand.shape[0] != N or cand.shape[1] < 1:
+        raise TgsrError("cand must be an int32 / int64 [N = %d, K >= 1] tensor, got %s %s" % (N, cand.dtype, tuple(cand.shape)))
+    lo, hi = int(cand.min()), int(cand.max())
+    if lo < -1 or hi >= M:
+        raise TgsrError("cand entries must be in [-1, %d) (-1 = an empty slot), got [%d, %d]" % (M, lo, hi))
+    return cand.to(torch.int32).contiguous()
+
+
+def _candidates(cand, N: int, M: int, dev):
+    """(device int32 table or None, K).  A host table is range-checked before the upload; a device table is taken as it is (the
+    kernels treat an entry outside [0, M) as an empty slot)."""
+    if cand is None:
+        return None, M
+    if not cand.is_cuda:
+        return check_candidates(cand, N, M).to(dev), cand.shape[1]
+    if cand.dtype != torch.int32 or cand.dim() != 2 or cand.shape[0] != N or cand.shape[1] < 1:
+        raise TgsrError("a device cand must be an int32 [N = %d, K >= 1] tensor, got %s %s" % (N, cand.dtype, tuple(cand.shape)))
+    return cand.contiguous(), cand.shape[1]
+
+
+def damsm_gallery(img_features: torch.Tensor, words_emb: torch.Tensor, cap_lens, gamma1: float, gamma2: float,
+                  cand: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Word-level similarities of N images against candidate captions out of a pool of M, one launch: sim [N, K] with
+    sim[n][k] = log sum_w exp(gamma2 * cos) of image n and caption cand[n][k] (what damsm_words_similarity gives the pair).
+    img_features [N,ndf,ih,iw], words_emb [M,ndf,Tw], cap_lens M ints, cand int [N,K] (host: checked to lie in [-1, M); device: taken
+    as it is) or None = every caption (K = M).  An empty slot (-1) scores -inf.  Evaluation only: no backward."""
+    _need_hip(img_features, words_emb, cand if cand is not None and cand.is_cuda else None)
+    if img_features.dim() != 4 or words_emb.dim() != 3 or img_features.shape[1] != words_emb.shape[1]:
+        raise TgsrError("damsm_gallery: img_features [N,ndf,ih,iw] and words_emb [M,ndf,Tw] expected, got %s and %s"
+                        % (tuple(img_features.shape), tuple(words_emb.shape)))
+    N, ndf, ih, iw = img_features.shape
+    M, _, Tw = words_emb.shape
+    lens = [int(v) for v in (cap_lens.tolist() if torch.is_tensor(cap_lens) else cap_lens)]
+    if len(lens) != M or min(lens) < 1 or max(lens) > Tw:
+        raise TgsrError("damsm_gallery: cap_lens %s invalid for words %s" % (lens, tuple(words_emb.shape)))
+    ctx = _f32(img_features.detach(), "img_features").contiguous()
+    words = _f32(words_emb.detach(), "words_emb").contiguous()
+    dev = ctx.device
+    cand_d, K = _candidates(cand, N, M, dev)
+    sim = torch.empty(N, K, dtype=torch.float32, device=dev)
+    rc = _lib.lib().tgsr_damsm_gallery_fwd(_p(words), _p(_lens_on_device(tuple(lens), dev)), _p(ctx), _p(cand_d), N, M, K, ndf, Tw,
+                                           ih * iw, float(gamma1), float(gamma2), _p(sim), _stream())
+    check(rc, "tgsr_damsm_gallery_fwd")
+    return sim
+
+
+def sent_gallery(cnn_code: torch.Tensor, rnn_code: torch.Tensor, eps: float, gamma3: float,
+                 cand: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Sentence-level similarities: sim [N, K] = gamma3 * cos(cnn_code[n], rnn_code[cand[n][k]]) with the reference's clamp of the
+    norm product at eps (losses.py:234-250).  cnn_code [N,ndf], rnn_code [M,ndf]; cand as in damsm_gallery."""
+    _need_hip(cnn_code, rnn_code, cand if cand is not None and cand.is_cuda else None)
+    if cnn_code.dim() != 2 or rnn_code.dim() != 2 or cnn_code.shape[1] != rnn_code.shape[1]:
+        raise TgsrError("sent_gallery: cnn_code [N,ndf] and rnn_code [M,ndf] expected, got %s and %s"
+                        % (tuple(cnn_code.shape), tuple(rnn_code.shape)))
+    N, ndf = cnn_code.shape
+    M = rnn_code.shape[0]
+    x = _f32(cnn_code.detach(), "cnn_code").contiguous()
+    y = _f32(rnn_code.detach(), "rnn_code").contiguous()
+    cand_d, K = _candidates(cand, N, M, x.device)
+    sim = torch.empty(N, K, dtype=torch.float32, device=x.device)
+    rc = _lib.lib().tgsr_sent_gallery_fwd(_p(x), _p(y), _p(cand_d), N, M, K, ndf, float(eps), float(gamma3), _p(sim), _stream())
+    check(rc, "tgsr_sent_gallery_fwd")
+    return sim
+
+
+def retrieval_ranks(sim: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
+    """rank [N] int32: the position of column target[n] in a stable descending sort of row n of sim [N, K], by counting (no sort);
+    -1 where target[n] is outside [0, K).  target: int32 [N] on the device."""
+    _need_hip(sim, target)
+    if sim.dim() != 2 or target.dim() != 1 or target.shape[0] != sim.shape[0] or target.dtype != torch.int32:
+        raise TgsrError("retrieval_ranks: sim [N,K] float32 and target [N] int32 expected, got %s and %s %s"
+                        % (tuple(sim.shape), target.dtype, tuple(target.shape)))
+    s = _f32(sim, "sim").contiguous()
+    N, K = s.shape
+    rank = torch.empty(N, dtype=torch.int32, device=s.device)
+    rc = _lib.lib().tgsr_retrieval_ranks(_p(s), _p(target.contiguous()), N, K, _p(rank), _stream())
+    check(rc, "tgsr_retrieval_ranks")
+    return rank
+
+
 # ----------------------------------------------------------------------------------------- CNN_ENCODER heads
 CONV1X1_GCONV = os.environ.get("TGSR_CONV1X1_GCONV", "1") != "0"
 

@@ -24,7 +24,7 @@ import numpy as np
 import torch
 import torch.distributed as dist
 
-from . import autograd, metrics, model, parallel
+from . import autograd, metrics, model, parallel, retrieval
 from .miscc import losses
 from .miscc.config import cfg
 from .miscc.utils import copy_G_params, load_params  # noqa: F401  (miscc/utils.py:467-474: the generator EMA helpers)
@@ -807,23 +807,41 @@ class SRTrainer:
                 torch.cuda.set_rng_state(rng_dev, self.device)
 
     @torch.no_grad()
-    def evaluate(self, batches, ema=True, shave=0, max_batches=None):
+    def evaluate(self, batches, ema=True, shave=0, max_batches=None, r_precision=None, generator=None):
         """Score a validation set: `batches` yields (captions, cap_lens, LR, LRb, hr_pyramid); the generators run in eval mode
         (SRPipeline.from_modules over this trainer's modules, no copies) with the EMA weights (`ema`, the ones `snapshot` saves by
         default) or the current ones, and every output scale is scored against hr_pyramid[k] on the device (tgsr_amd.metrics:
         PSNR / RMSE on RGB and Y, SSIM on Y, `shave` border pixels removed) - no synchronisation per batch, one at the end.
         Returns {"fine": [per scale], "fake": [per scale]}, per scale {"psnr": [N], "rmse", "psnr_y", "rmse_y", "ssim_y", "n": N,
         "mean": {...}} over the N images seen.  Afterwards the trainer is exactly as it was (`_eval_weights`).
-        Data parallel: every rank passes ITS batches; the rows are gathered in rank order and every rank returns the same dict."""
+        Data parallel: every rank passes ITS batches; the rows are gathered in rank order and every rank returns the same dict.
+        `r_precision` = K (default None: nothing below happens) asks whether the output is consistent with its caption: the batches
+        then carry `class_ids` as a sixth element, the finest `fine` image of every batch goes through `image_encoder` (required), and
+        the dict gains "r_precision": {"sent": ..., "words": ...} - each the result of retrieval.r_precision over the images seen,
+        against the candidate table sample_candidates(class_ids, K, generator): the own caption and K - 1 captions of other classes.
+        Data parallel: that entry scores the calling rank's items only (region features are not gathered across ranks)."""
         if getattr(self, "_eval_pipe", None) is None:
             self._eval_pipe = SRPipeline.from_modules(self.text_encoder, self.netGL, self.netGH, device=self.device)
+        if r_precision is not None and self.image_encoder is None:
+            raise ValueError("evaluate(r_precision=%r) needs the trainer's image_encoder" % (r_precision,))
         book = metrics.ScoreBook(shave)
         nscales = 0
+        seen = {"regions": [], "codes": [], "words": [], "sents": [], "lens": [], "class_ids": []}
         with torch.cuda.device(self.device), self._eval_weights(ema):
-            for k, (captions, cap_lens, LR, LRb, hr_pyramid) in enumerate(batches):
+            for k, batch in enumerate(batches):
+                if r_precision is None:
+                    captions, cap_lens, LR, LRb, hr_pyramid = batch
+                else:
+                    captions, cap_lens, LR, LRb, hr_pyramid, class_ids = batch
                 if max_batches is not None and k >= max_batches:
                     break
                 out = self._eval_pipe(captions, cap_lens, LR, LRb)
+                if r_precision is not None:
+                    words_embs, sent_emb, _mask = self._text(captions, cap_lens)
+                    feats, code = self.image_encoder(out["fine"][-1])
+                    seen["regions"].append(feats); seen["codes"].append(code); seen["words"].append(words_embs); seen["sents"].append(sent_emb)
+                    seen["lens"] += [int(v) for v in (cap_lens.tolist() if torch.is_tensor(cap_lens) else cap_lens)]
+                    seen["class_ids"] += [int(v) for v in (class_ids.tolist() if torch.is_tensor(class_ids) else class_ids)]
                 nscales = len(hr_pyramid)
                 for name in ("fine", "fake"):
                     if len(out[name]) != nscales:
@@ -839,7 +857,15 @@ class SRTrainer:
         res = book.result()
         if not res:
             raise ValueError("evaluate: no validation batch")
-        return {name: [res[(name, i)] for i in range(nscales)] for name in ("fine", "fake")}
+        scores = {name: [res[(name, i)] for i in range(nscales)] for name in ("fine", "fake")}
+        if r_precision is not None:
+            cand = retrieval.sample_candidates(seen["class_ids"], int(r_precision), generator)
+            Tw = max(w.shape[2] for w in seen["words"])
+            words = [w if w.shape[2] == Tw else torch.nn.functional.pad(w, (0, Tw - w.shape[2])) for w in seen["words"]]
+            with torch.cuda.device(self.device):
+                feats = [torch.cat(seen[key]) for key in ("regions", "codes")] + [torch.cat(words), torch.cat(seen["sents"])]
+                scores["r_precision"] = {mode: retrieval.r_precision(*feats, seen["lens"], cand, mode=mode) for mode in retrieval.MODES}
+        return scores
 
     def snapshot_due(self, epoch, max_epoch=None):
         return snapshot_due(epoch, max_epoch)
@@ -986,6 +1012,39 @@ class DAMSMTrainer:
                 features, pooled = self.image_encoder.run_trunk(imgs)
                 yield features, pooled, captions, cap_lens, class_ids
         return self.evaluate_features(through_trunk())
+
+    @torch.no_grad()
+    def evaluate_retrieval(self, batches, ks=(1, 5, 10), max_items=None):
+        """Retrieval accuracy of the two encoders on a validation set (not in the reference's loop, which prints only the two summed
+        losses): `batches` yields what `evaluate` takes, (imgs, captions, cap_lens, class_ids), or what `evaluate_features` takes,
+        (features, pooled, captions, cap_lens, class_ids).  Both encoders in eval mode and left there, like `evaluate`.  The region
+        features, image codes and text embeddings of every item (at most `max_items`) are gathered on the device and scored as ONE
+        gallery by retrieval.retrieval_scores: recall@k and the median rank, image -> text and text -> image, for the sentence and
+        the word similarity.  Data parallel: every rank scores the items of ITS batches only (no gather of region features)."""
+        self.text_encoder.eval()
+        self.image_encoder.eval()
+        regions, codes, words, sents, lens, n = [], [], [], [], [], 0
+        with torch.cuda.device(self.device):
+            for batch in batches:
+                if max_items is not None and n >= max_items:
+                    break
+                if len(batch) == 4:
+                    imgs, captions, cap_lens, _cls = batch
+                    features, pooled = self.image_encoder.run_trunk(imgs)
+                else:
+                    features, pooled, captions, cap_lens, _cls = batch
+                B = captions.shape[0]
+                take = B if max_items is None else min(B, max_items - n)
+                wf, code = self.image_encoder.heads(features, pooled)
+                we, se = self.text_encoder(captions, cap_lens, self.text_encoder.init_hidden(B))
+                regions.append(wf[:take]); codes.append(code[:take]); words.append(we[:take]); sents.append(se[:take])
+                lens += [int(v) for v in (cap_lens.tolist() if torch.is_tensor(cap_lens) else cap_lens)][:take]
+                n += take
+            if n == 0:
+                raise ValueError("evaluate_retrieval: no validation batch")
+            Tw = max(w.shape[2] for w in words)            # batches may differ in their longest caption: pad the word axis
+            words = [w if w.shape[2] == Tw else torch.nn.functional.pad(w, (0, Tw - w.shape[2])) for w in words]
+            return retrieval.retrieval_scores(torch.cat(regions), torch.cat(codes), torch.cat(words), torch.cat(sents), lens, ks)
 
     def snapshot_due(self, epoch, max_epoch=None):
         return snapshot_due(epoch, max_epoch)
