@@ -842,6 +842,29 @@ int tgsr_sr_metrics(const void* sr, int sr_f32, const void* hr, int hr_f32, int 
 int tgsr_rgb_to_y_u8(const uint8_t* rgb, int B, int H, int W, uint8_t* y, void* stream);
 
 /*
+ * Attention panels (csrc/tgsr_attnviz.hip): one tile per caption word, the word's attention map thresholded, expanded, blurred,
+ * stretched to bytes and pasted over the image - build_super_imagesall / build_super_images2 (miscc/utils.py:202-451) on the
+ * device.  The arithmetic is stated in tgsr_amd/attnviz.py and DESIGN.md 3.12.
+ *   att [B][T][h][w] fp32; cap_lens int32 [B] ON THE DEVICE (the caller checks its host copy; the kernels clamp into [1, T]); words
+ *   at and behind cap_lens[b] are not read.  img [B][3][Vh][Vw], (Vh, Vw) = (u h, u w): fp32 in [-1, 1] (img_f32 != 0; quantised
+ *   ((v + 1) / 2) * 255, round half to even, clamp) or uint8.  Mh [Vh][h], Mw [Vw][w] fp64: the resize-then-blur operators (the
+ *   identity for u = 1).  Per word j < n = cap_lens[b]: thresh = 2 / n in fp64, conf[b][j] = sum x [x > 2 thresh] (0 behind the
+ *   caption), x <- x [x > thresh], tile = Mh . x . Mw^T on the fp64 MFMA, byte = trunc((tile - min) / (max - min) * 255), black where
+ *   max == min.  panel uint8 [B][Vh][K (Vw + 2)][3]: slot s of row b shows word order[b][s] for s < min(K, n), blended by Pillow's
+ *   paste through the constant mask alpha (t = m alpha + i (255 - alpha) + 128; ((t >> 8) + t) >> 8), followed by two black columns;
+ *   slots at and behind min(K, n) are black.  by_conf != 0: slots by descending conf, ties to the HIGHER word index; else slot = word.
+ *   order int32 [B][T]: the word of every slot s < n (also those at and behind K), -1 behind.  maps_or_null: uint8 [B][T][Vh][Vw],
+ *   the un-blended map bytes (black behind the caption).  ws: tgsr_attn_panels_ws_elems(...) float64.
+ * Two launches on `stream`, no atomics, no host synchronisation: capturable, the same bits on every run.  Refused before any launch:
+ * TGSR_EINVAL for a missing pointer, B, T, K < 1, K > T, u < 1, alpha outside [0, 255]; TGSR_EUNSUPPORTED for h or w outside
+ * [2, 128], Vh or Vw > 512, T > 64 (tgsr_attn_panels_ws_elems returns 0 for those shapes).
+ */
+int64_t tgsr_attn_panels_ws_elems(int B, int T, int h, int w, int u);
+int tgsr_attn_panels(const float* att, const int32_t* cap_lens, const void* img, int img_f32, const double* Mh, const double* Mw,
+                     int B, int T, int h, int w, int u, int alpha, int K, int by_conf, double* ws, uint8_t* panel,
+                     uint8_t* maps_or_null, double* conf, int32_t* order, void* stream);
+
+/*
  * Whole-image inference by overlapping tiles (SRPipeline.upscale; the reference's arbitrary-size example path,
  * datasets.py:200-278, followed by the fully convolutional generators): the cut and the reassembly of a tile batch.
  * table: int32 [Tb][6] = (y0, x0, oy0, oy1, ox0, ox1) in LR pixels, once in host memory (table_host, checked here) and once in

@@ -449,6 +449,22 @@ retrieval_ranks = _define("retrieval_ranks(Tensor sim, Tensor target) -> Tensor"
                           lambda sim, t: sim.new_empty(sim.shape[0], dtype=torch.int32))
 
 
+# attention panels (tgsr_amd.attnviz reads it): (panel, conf, order, maps) - one tile per caption word, the word's attention map
+# expanded by the fp64 operators Mh / Mw and pasted over the image; `maps` is an empty tensor without with_maps
+def _attn_panels_fake(images, att, cap_lens, Mh, Mw, u, alpha, K, by_conf, with_maps):
+    B, T, h, w = att.shape
+    u8 = dict(dtype=torch.uint8)
+    return (att.new_empty((B, u * h, K * (u * w + 2), 3), **u8), att.new_empty((B, T), dtype=torch.float64),
+            att.new_empty((B, T), dtype=torch.int32), att.new_empty((B, T, u * h, u * w) if with_maps else (0,), **u8))
+
+
+attn_panels = _define("attn_panels(Tensor images, Tensor att, int[] cap_lens, Tensor Mh, Tensor Mw, int u, int alpha, int K, "
+                      "bool by_conf, bool with_maps) -> (Tensor, Tensor, Tensor, Tensor)",
+                      lambda im, att, lens, Mh, Mw, u, alpha, K, by_conf, with_maps:
+                      ops.attn_panels(im, att, list(lens), Mh, Mw, u, alpha, K, by_conf, with_maps),
+                      _attn_panels_fake)
+
+
 # ------------------------------------------------------------------------------------------------ CA_NET (inference)
 def _ca_net(sent_emb, w, b, ncf, eps):
     c, mu, logvar = ops.ca_net(sent_emb, w, b, ncf, eps)

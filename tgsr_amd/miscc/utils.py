@@ -4,7 +4,8 @@
 In scope (used by the training counterparts): `weights_init` (utils.py:454-464), `load_params` / `copy_G_params`
 (:467-474: the generator EMA helpers), `mkdir_p` (:477-485).  Out of scope (attention-map
 visualisation with PIL / skimage and a hard-coded Windows font path): `build_super_images*` import fine and raise when
-called - a caller that wants the PNG panels keeps its own miscc/utils.py, which install_dropin() leaves in place.
+called - a caller that wants the PNG panels calls `tgsr_amd.attnviz.build_super_imagesall` / `build_super_images2` (the
+panels on the device) or keeps its own miscc/utils.py, which install_dropin() leaves in place.
 """
 import errno
 import os
@@ -54,9 +55,10 @@ def mkdir_p(path):
 
 def _visualisation(name):
     def fn(*args, **kwargs):
-        raise NotImplementedError("miscc.utils.%s draws attention-map panels with PIL/skimage (utils.py:74-451): "
-                                  "visualisation is outside tgsr_amd's scope; keep the caller's own miscc/utils.py on "
-                                  "sys.path (install_dropin() then leaves it in place)" % name)
+        raise NotImplementedError("miscc.utils.%s draws attention-map panels with PIL/skimage (utils.py:74-451) and is not "
+                                  "switched over here: tgsr_amd.attnviz builds build_super_imagesall / build_super_images2 on "
+                                  "the device (call those), or keep the caller's own miscc/utils.py on sys.path "
+                                  "(install_dropin() then leaves it in place)" % name)
     fn.__name__ = name
     return fn
 

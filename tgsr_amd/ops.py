@@ -2079,6 +2079,58 @@ def rgb_to_y(rgb: torch.Tensor) -> torch.Tensor:
     return out
 
 
+# ----------------------------------------------------------------------------------------- attention panels
+ATTN_MAX_SIDE, ATTN_MAX_TILE, ATTN_MAX_WORDS = 128, 512, 64
+
+
+def check_cap_lens(cap_lens, B: int, T: int) -> list:
+    """The host check of the caption lengths of an attention panel: B ints in [1, T].  Returns them as a list."""
+    lens = [int(v) for v in (cap_lens.tolist() if torch.is_tensor(cap_lens) else cap_lens)]
+    if len(lens) != B or min(lens) < 1 or max(lens) > T:
+        raise TgsrError("attn_panels: cap_lens %s must be %d lengths in [1, %d]" % (lens, B, T))
+    return lens
+
+
+def attn_panels(images: torch.Tensor, att: torch.Tensor, cap_lens, Mh: torch.Tensor, Mw: torch.Tensor, u: int, alpha: int, K: int,
+                by_conf: bool, with_maps: bool):
+    """tgsr_attn_panels: (panel uint8 [B, Vh, K (Vw + 2), 3], conf float64 [B, T], order int32 [B, T], maps uint8 [B, T, Vh, Vw] or
+    [0]) from att [B, T, h, w] float32, cap_lens (B host ints in [1, T]), images [B, 3, u h, u w] float32 or uint8 and the fp64
+    operators Mh [u h, h], Mw [u w, w] (attnviz.expand_operator).  The arithmetic: tgsr_amd/attnviz.py."""
+    if att.dim() != 4:
+        raise TgsrError("attn_panels: att [B, T, h, w] expected, got %s" % (tuple(att.shape),))
+    B, T, h, w = att.shape
+    lens = check_cap_lens(cap_lens, B, T)
+    _need_hip(images, att, Mh, Mw)
+    u, alpha, K = int(u), int(alpha), int(K)
+    Vh, Vw = u * h, u * w
+    if images.dtype not in (torch.float32, torch.uint8) or tuple(images.shape) != (B, 3, Vh, Vw):
+        raise TgsrError("attn_panels: images must be float32 or uint8 [%d, 3, %d, %d], got %s %s"
+                        % (B, Vh, Vw, images.dtype, tuple(images.shape)))
+    for name, m, shape in (("Mh", Mh, (Vh, h)), ("Mw", Mw, (Vw, w))):
+        if m.dtype != torch.float64 or tuple(m.shape) != shape:
+            raise TgsrError("attn_panels: %s must be float64 %s, got %s %s" % (name, shape, m.dtype, tuple(m.shape)))
+    if not (1 <= K <= T) or not (0 <= alpha <= 255) or u < 1:
+        raise TgsrError("attn_panels: K %d (1..%d), alpha %d (0..255), u %d (>= 1)" % (K, T, alpha, u))
+    L = _lib.lib()
+    n_ws = L.tgsr_attn_panels_ws_elems(B, T, h, w, u)
+    if n_ws <= 0:
+        raise TgsrError("attn_panels: maps of %d x %d (sides 2..%d), tiles of %d x %d (<= %d) and %d words (<= %d) are what the "
+                        "kernels take" % (h, w, ATTN_MAX_SIDE, Vh, Vw, ATTN_MAX_TILE, T, ATTN_MAX_WORDS))
+    dev = att.device
+    att = _f32(att.detach(), "att").contiguous()
+    images = images.detach().contiguous()
+    ws = torch.empty(n_ws, dtype=torch.float64, device=dev)
+    panel = torch.empty(B, Vh, K * (Vw + 2), 3, dtype=torch.uint8, device=dev)
+    maps = torch.empty((B, T, Vh, Vw) if with_maps else (0,), dtype=torch.uint8, device=dev)
+    conf = torch.empty(B, T, dtype=torch.float64, device=dev)
+    order = torch.empty(B, T, dtype=torch.int32, device=dev)
+    rc = L.tgsr_attn_panels(_p(att), _p(_lens_on_device(tuple(lens), dev)), _p(images), int(images.dtype == torch.float32),
+                            _p(Mh.contiguous()), _p(Mw.contiguous()), B, T, h, w, u, alpha, K, int(bool(by_conf)), _p(ws), _p(panel),
+                            _p(maps) if with_maps else None, _p(conf), _p(order), _stream())
+    check(rc, "tgsr_attn_panels")
+    return panel, conf, order, maps
+
+
 # ----------------------------------------------------------------------------------------- discriminator convolutions
 def _dconv(kind: int):
     L = _lib.lib()

@@ -364,6 +364,39 @@ class SRPipeline:
         return res
 
     @torch.no_grad()
+    def attention_panels(self, out, captions, cap_lens, ixtoword=None, stage=0, top_k=None):
+        """The attention panels of a step's result (tgsr_amd.attnviz: the second file gen_exampleSRHL writes per image,
+        trainer_objective.py:157-163 - one tile per caption word, the word's attention map of `stage` blurred, stretched and blended
+        over the finest SR image).  `out`: what `__call__` returns (att [B, T, h, w] per stage) or an `upscale(with_att=True)`
+        result (one image, att [cap_len, h, w], any rectangular size).  The tile is the finest image's size, u = that size / the
+        stage's map size: ValueError unless it is the same integer on both axes.  top_k: None = every word in caption order
+        (build_super_imagesall), else the top_k words by descending conf (build_super_images2).
+        Returns attnviz.attention_panels' dict (device tensors); with `ixtoword` also "image" (uint8 numpy: per image the text strip
+        on its panel row, ready for Image.fromarray(...).save) and "sentences" - that part synchronises."""
+        from . import attnviz
+        if "att" not in out:
+            raise ValueError("attention_panels: the result carries no attention maps (upscale(..., with_att=True))")
+        att, img = out["att"][stage], out["fine"][-1]
+        lens = _host_lens(cap_lens) if torch.is_tensor(cap_lens) or isinstance(cap_lens, (list, tuple)) else [int(cap_lens)]
+        if att.dim() == 3:                                                  # an upscale result: one image
+            att, img = att.unsqueeze(0), img.unsqueeze(0)
+        H, W, h, w = int(img.shape[2]), int(img.shape[3]), int(att.shape[2]), int(att.shape[3])
+        if H % h or W % w or H // h != W // w:
+            raise ValueError("attention_panels: the %d x %d image is no integer multiple of stage %d's %d x %d attention maps"
+                             % (H, W, stage, h, w))
+        with torch.cuda.device(att.device):
+            res = attnviz.attention_panels(img.contiguous(), att.contiguous(), lens, top_k=top_k)
+            if ixtoword is not None:
+                panel = res["panel"].cpu().numpy()
+                strip, res["sentences"] = attnviz.text_strip(captions, ixtoword, W, order=res["order"] if top_k is not None else None,
+                                                             numbered=top_k is not None, n_cols=panel.shape[2] // (W + 2))
+                rows = []
+                for b in range(panel.shape[0]):
+                    rows += [strip[b * attnviz.FONT_MAX:(b + 1) * attnviz.FONT_MAX], panel[b]]
+                res["image"] = np.concatenate(rows, 0)
+        return res
+
+    @torch.no_grad()
     def __call__(self, captions, cap_lens, LR, LRb, num_words=None):
         """trainer_objective.py:134-146.  Returns the same tensors the reference loop produces.  Runs under the
         pipeline's device (the kernels launch on the CURRENT device's stream; ops refuse tensors that live elsewhere).
