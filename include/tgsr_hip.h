@@ -1152,6 +1152,36 @@ int tgsr_lp_word_attention_fwd(int dtype, const void* h, int h_cpitch, const flo
                                int mask_mode, int B, int idf, int T, int H, int W, void* c_img, int c_cpitch, int c_coff,
                                float* attn, void* stream);
 
+/*
+ * The objectives that read the generator's word-attention maps (the reference's miscc/losses.py; tgsr_attn_losses.hip).
+ *
+ * tgsr_attn_confidence - the per-word weights of words_reweight_loss (:150-163): att fp32 [B][T][Q] dense (any 4-byte aligned base),
+ * cap_lens int32 [B] ON THE DEVICE (no launch argument depends on the lengths), conf fp32 [B][T]:
+ *   conf[b][t] = the fp32 sum of the values of att[b][t] strictly above (float)(2.0 * (2.0 / (double)cap_lens[b]))   for t < cap_lens[b],
+ *              = 0 without reading the map                                                                          for t >= cap_lens[b];
+ *   a row whose cap_lens[b] lies outside [1, T] is written as zeros.  One workgroup per map, a fixed reduction tree.
+ *   B <= 65535, T <= 255, Q >= 1.
+ *
+ * tgsr_weight_mse_fwd - one scale of weight_MSE (:792-804): fake, label fp32 [B][C][H][W], att fp32 [B][T][h][w], all dense,
+ * H = r h and W = r w for one integer r >= 1, T <= 255.
+ *   wmax[b][y][x] = max_t att[b][t][y][x],  widx = the word that holds it (the lowest on a tie),
+ *   loss[0]       = sum_{b,c,Y,X} (T wmax[b][Y / r][X / r]) (fake - label)^2 / (H W B C),
+ *   wlast         = NULL, or fp32 [B][1][H][W]: wmax at (Y / r, X / r) - nn.Upsample(size=(H, W)) of the maximum, bit for bit.
+ *   ws: tgsr_weight_mse_ws_elems(...) floats (0 = a shape the entry refuses); the workgroups' partial sums, added in index order.
+ * tgsr_weight_mse_bwd - grad fp32 [1] on the device (the gradient reaching loss[0]); writes whichever of these is not NULL (one at least):
+ *   d_fake  = grad 2 T wmax[Y / r][X / r] (fake - label) / (H W B C),   d_label = -d_fake,
+ *   d_att fp32 [B][T][h][w], written completely: grad T / (H W B C) sum_{c, r x r} (fake - label)^2 at widx, 0 at the other words.
+ * 16 bytes per lane where every pointer is 16-byte aligned, w % 4 == 0 and r in {1, 2, 4}; element by element otherwise.  No atomics.
+ * Every entry returns TGSR_EINVAL without launching (and without touching an output) for a NULL pointer, a size < 1, T > 255,
+ * H % h != 0, W % w != 0 or H / h != W / w.
+ */
+int tgsr_attn_confidence(const float* att, const int32_t* cap_lens, int B, int T, int Q, float* conf, void* stream);
+int64_t tgsr_weight_mse_ws_elems(int B, int C, int T, int H, int W, int h, int w);
+int tgsr_weight_mse_fwd(const float* fake, const float* label, const float* att, int B, int C, int T, int H, int W, int h, int w,
+                        float* ws, float* loss, float* wmax, uint8_t* widx, float* wlast, void* stream);
+int tgsr_weight_mse_bwd(const float* grad, const float* fake, const float* label, const float* wmax, const uint8_t* widx, int B, int C,
+                        int T, int H, int W, int h, int w, float* d_fake, float* d_label, float* d_att, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

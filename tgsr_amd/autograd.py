@@ -596,6 +596,29 @@ class DamsmWords(torch.autograd.Function):
         return g_img, g_words, None, None, None
 
 
+class WeightMSE(torch.autograd.Function):
+    """One scale of weight_MSE (losses.py:796-800): (term, wlast) = tgsr::weight_mse, backward = tgsr::weight_mse_bwd.  Differentiable
+    w.r.t. fake, label and the attention maps (their gradient goes to the word that held each map pixel's maximum, the lowest on a
+    tie); `wlast` (the up-sampled maximum, [0] unless asked for) is returned without gradient."""
+
+    @staticmethod
+    def forward(ctx, fake, label, att, want_wlast):
+        term, wmax, widx, wlast = C.weight_mse(fake, label, att, bool(want_wlast))
+        ctx.save_for_backward(fake, label, wmax, widx)
+        ctx.T = int(att.shape[1])
+        ctx.mark_non_differentiable(wlast)
+        return term, wlast
+
+    @staticmethod
+    def backward(ctx, grad_term, _grad_wlast):
+        fake, label, wmax, widx = ctx.saved_tensors
+        need = ctx.needs_input_grad[:3]
+        if not any(need):
+            return None, None, None, None
+        d_fake, d_label, d_att = C.weight_mse_bwd(grad_term.contiguous(), fake.detach(), label.detach(), wmax, widx, ctx.T, *need)
+        return (d_fake if need[0] else None), (d_label if need[1] else None), (d_att if need[2] else None), None
+
+
 class BiLSTM(torch.autograd.Function):
     """RNN_ENCODER's bidirectional LSTM (util.py:233-260) in training mode: forward = tgsr::bilstm_train on the embedded
     (and dropped-out) inputs, backward = tgsr::bilstm_bwd (BPTT, one workgroup per sample and direction) plus four GEMMs

@@ -607,6 +607,31 @@ sr_metrics = _define("sr_metrics(Tensor sr, Tensor hr, int shave=0) -> Tensor", 
 rgb_to_y = _define("rgb_to_y(Tensor rgb) -> Tensor", lambda rgb: ops.rgb_to_y(rgb),
                    lambda rgb: rgb.new_empty(rgb.shape[0], rgb.shape[2], rgb.shape[3], dtype=torch.uint8))
 
+# the objectives that read the generator's word-attention maps (miscc.losses.weight_MSE / words_reweight_loss): cap_lens is an int32
+# DEVICE tensor; weight_mse returns (term [], wmax [B, h, w], widx uint8 [B, h, w], wlast [B, 1, H, W] or [0]); autograd.WeightMSE
+# is the differentiable form over weight_mse / weight_mse_bwd (absent gradients come back as [0])
+attn_confidence = _define("attn_confidence(Tensor att, Tensor cap_lens) -> Tensor", lambda att, lens: ops.attn_confidence(att, lens),
+                          lambda att, lens: att.new_empty(att.shape[0], att.shape[1]))
+weight_mse = _define("weight_mse(Tensor fake, Tensor label, Tensor att, bool want_wlast) -> (Tensor, Tensor, Tensor, Tensor)",
+                     lambda fake, label, att, wl: ops.weight_mse(fake, label, att, wl),
+                     lambda fake, label, att, wl: (
+                         fake.new_empty(()), att.new_empty(att.shape[0], att.shape[2], att.shape[3]),
+                         att.new_empty(att.shape[0], att.shape[2], att.shape[3], dtype=torch.uint8),
+                         fake.new_empty((fake.shape[0], 1, fake.shape[2], fake.shape[3]) if wl else (0,))))
+
+
+def _weight_mse_bwd(grad, fake, label, wmax, widx, T, need_fake, need_label, need_att):
+    return tuple(t if t is not None else fake.new_empty(0)
+                 for t in ops.weight_mse_bwd(grad, fake, label, wmax, widx, T, need_fake, need_label, need_att))
+
+
+weight_mse_bwd = _define("weight_mse_bwd(Tensor grad, Tensor fake, Tensor label, Tensor wmax, Tensor widx, int T, bool need_fake, "
+                         "bool need_label, bool need_att) -> (Tensor, Tensor, Tensor)", _weight_mse_bwd,
+                         lambda grad, fake, label, wmax, widx, T, nf, nl, na: (
+                             torch.empty_like(fake, memory_format=torch.contiguous_format) if nf else fake.new_empty(0),
+                             torch.empty_like(fake, memory_format=torch.contiguous_format) if nl else fake.new_empty(0),
+                             fake.new_empty((wmax.shape[0], T, wmax.shape[1], wmax.shape[2]) if na else (0,))))
+
 
 # whole images by overlapping tiles (SRPipeline.upscale): `table` is the host int32 [Tb, 6] window table, `table_dev` its device copy
 def _tile_gather(img, img2, table, table_dev, th, tw):

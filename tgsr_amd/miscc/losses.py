@@ -6,6 +6,9 @@ mask, the x gamma3 scale and the two cross entropies act on a [B, B] matrix and 
 [B,256]x[256,B] product (a plain library GEMM).  `KL_loss` and `MSE` (losses.py:779-810) are scalar reductions.
 Both are differentiable: words_loss through the HIP backward of the DAMSM kernel (tgsr_damsm_words_bwd, autograd.DamsmWords),
 sent_loss through torch autograd over its [B, B] matrix.
+The objectives that read the generator's word-attention maps - `weight_MSE` (:792-804), `words_reweight_loss` (:137-232),
+`generator_re_weight_loss` (:318-350) - run on the kernels of tgsr_attn_losses.hip; their torch compositions, for
+CPU tensors and for what the kernels do not take, live here and nowhere else.
 """
 import contextlib
 
@@ -15,6 +18,7 @@ import torch
 import torch.nn.functional as F
 
 from .. import custom_ops as C
+from .. import ops
 from .config import cfg
 
 
@@ -59,16 +63,17 @@ def sent_loss(cnn_code, rnn_code, labels, class_ids, batch_size, eps=1e-8):
     return _ranking_ce(scores, labels)
 
 
-def words_loss(img_features, words_emb, labels, cap_lens, class_ids, batch_size):
-    """losses.py:65-136.  words_emb(query): batch x nef x seq_len; img_features(context): batch x nef x 17 x 17.
-    Returns (loss0, loss1, att_maps) with att_maps[i] = [1, cap_len_i, 17, 17]."""
-    lens = cap_lens.data.tolist() if torch.is_tensor(cap_lens) else list(cap_lens)
+def _damsm_sim(img_features, words_emb, lens):
+    """(sim [B, B], att [B, T, 17, 17]) of the batched DAMSM kernel, through autograd.DamsmWords when a gradient is wanted."""
     if torch.is_grad_enabled() and (img_features.requires_grad or words_emb.requires_grad):
         from ..autograd import DamsmWords
-        sim, att = DamsmWords.apply(img_features, words_emb, lens, cfg.TRAIN.SMOOTH.GAMMA1, cfg.TRAIN.SMOOTH.GAMMA2)
-    else:
-        sim, att = C.damsm_words(img_features, words_emb, [int(v) for v in lens], float(cfg.TRAIN.SMOOTH.GAMMA1),
-                                 float(cfg.TRAIN.SMOOTH.GAMMA2))
+        return DamsmWords.apply(img_features, words_emb, lens, cfg.TRAIN.SMOOTH.GAMMA1, cfg.TRAIN.SMOOTH.GAMMA2)
+    return C.damsm_words(img_features, words_emb, [int(v) for v in lens], float(cfg.TRAIN.SMOOTH.GAMMA1),
+                         float(cfg.TRAIN.SMOOTH.GAMMA2))
+
+
+def _words_ranking(sim, att, lens, labels, class_ids, batch_size):
+    """losses.py:114-136: the per-caption maps, x gamma3, same-class pairs masked out, cross entropy along both axes."""
     att_maps = [att[i:i + 1, :lens[i]].contiguous() for i in range(batch_size)]
     similarities = sim * cfg.TRAIN.SMOOTH.GAMMA3
     masks = _class_masks(class_ids, batch_size, sim.device)
@@ -76,6 +81,85 @@ def words_loss(img_features, words_emb, labels, cap_lens, class_ids, batch_size)
         similarities = similarities.masked_fill(masks, -float('inf'))
     loss0, loss1 = _ranking_ce(similarities, labels)
     return loss0, loss1, att_maps
+
+
+def words_loss(img_features, words_emb, labels, cap_lens, class_ids, batch_size):
+    """losses.py:65-136.  words_emb(query): batch x nef x seq_len; img_features(context): batch x nef x 17 x 17.
+    Returns (loss0, loss1, att_maps) with att_maps[i] = [1, cap_len_i, 17, 17]."""
+    lens = cap_lens.data.tolist() if torch.is_tensor(cap_lens) else list(cap_lens)
+    sim, att = _damsm_sim(img_features, words_emb, lens)
+    return _words_ranking(sim, att, lens, labels, class_ids, batch_size)
+
+
+def _damsm_sim_torch(img_features, words_emb, lens):
+    """`_damsm_sim` as a torch composition (losses.py:73-113 through func_attention, GlobalAttention.py:33-74), all captions at
+    once: what words_reweight_loss computes on CPU tensors.  (words_loss itself has no CPU form and refuses them.)"""
+    B, nef, T = words_emb.shape
+    g1, g2 = float(cfg.TRAIN.SMOOTH.GAMMA1), float(cfg.TRAIN.SMOOTH.GAMMA2)
+    ctx = img_features.reshape(img_features.shape[0], nef, -1)                          # [j, d, r]
+    valid = torch.arange(T, device=words_emb.device)[None, :] < torch.as_tensor(lens, device=words_emb.device)[:, None]   # [i, l]
+    s = torch.einsum("jdr,idl->jirl", ctx, words_emb)
+    a1 = torch.softmax(s.masked_fill(~valid[None, :, None, :], -float("inf")), dim=3)   # over the caption's words, per region
+    a2 = torch.softmax(a1.transpose(2, 3) * g1, dim=3)                                  # over the regions, per word  [j, i, l, r]
+    wc = torch.einsum("jdr,jilr->jild", ctx, a2)
+    word = words_emb.transpose(1, 2)[None].expand(wc.shape[0], -1, -1, -1)              # [j, i, l, d]
+    cos = (word * wc).sum(3) / (word.norm(p=2, dim=3) * wc.norm(p=2, dim=3)).clamp_min(1e-8)
+    sim = torch.log((torch.exp(cos * g2) * valid[None]).sum(2))                         # [j, i]
+    att = a2[torch.arange(B), torch.arange(B)] * valid[:, :, None]                      # image i on caption i
+    return sim, att.reshape(B, T, *img_features.shape[2:]).detach()
+
+
+def _attn_maps(attn_map):
+    """The generator's maps as one [B, T', Q] tensor: a [B, T', h, w] tensor, or a list of per-image maps [T', h, w] /
+    [1, T', h, w] (zero rows are appended where the images' maps differ in words)."""
+    if torch.is_tensor(attn_map):
+        return attn_map.detach().flatten(2)
+    maps = [m.detach().reshape(-1, m.shape[-2] * m.shape[-1]) for m in attn_map]
+    width = max(m.shape[0] for m in maps)
+    return torch.stack([m if m.shape[0] == width else F.pad(m, (0, 0, 0, width - m.shape[0])) for m in maps])
+
+
+def _attn_confidence_torch(att, lens):
+    """conf [B, T'] of words_reweight_loss as a torch composition (losses.py:150-163 for every caption at once): the map's values
+    strictly above float32(2 * (2 / n)), summed, for the caption's n words; zero behind them, and - as the kernel - a zero row for a
+    length outside [1, T']."""
+    lens = [n if 1 <= n <= att.shape[1] else 0 for n in lens]
+    thr = torch.tensor([2. * (2. / float(n)) if n else float("inf") for n in lens], dtype=torch.float32, device=att.device)
+    valid = torch.arange(att.shape[1], device=att.device)[None, :] < torch.as_tensor(lens, device=att.device)[:, None]
+    return (att * (att > thr[:, None, None]).float()).sum(2) * valid
+
+
+def attn_confidence(attn_map, cap_lens, fused=None):
+    """The per-word weights of words_reweight_loss (losses.py:150-163), detached: conf [B, T'] float32, conf[i, j] = the sum of the
+    values of word j's map of image i that lie strictly above 2 * (2 / cap_lens[i]) - compared in float32, as torch compares a
+    float32 map with a Python double - for j < cap_lens[i], 0 behind.  One launch of tgsr_attn_confidence on HIP tensors (the
+    reference: one `.cpu().numpy()` per word and caption); the torch composition on CPU tensors or with fused=False."""
+    lens = [int(v) for v in (cap_lens.data.tolist() if torch.is_tensor(cap_lens) else cap_lens)]
+    att = _attn_maps(attn_map)
+    if att.shape[0] != len(lens):
+        raise ValueError("attention maps of %d images against %d caption lengths" % (att.shape[0], len(lens)))
+    if fused is None:
+        fused = att.is_cuda and att.dtype == torch.float32 and att.shape[1] <= ops.WMSE_MAX_WORDS
+    if not fused:
+        return _attn_confidence_torch(att, lens)
+    return C.attn_confidence(att, ops._lens_on_device(tuple(lens), att.device))
+
+
+def words_reweight_loss(img_features, words_emb, labels, cap_lens, class_ids, batch_size, attn_map, fused=None):
+    """losses.py:137-232: words_loss on the word embeddings scaled by `attn_confidence` of the generator's attention maps
+    (`attn_map`: [B, T', h, w] or a list of per-image maps), the factor detached as in the reference (it passes through numpy
+    there).  A caption of n <= 4 words has a threshold >= 1: its words enter as zero vectors, the losses stay finite and those
+    words receive a zero gradient.  `fused` (not a reference argument): None = the kernels on HIP tensors, the torch compositions
+    on CPU tensors; False = the compositions.  Returns (loss0, loss1, att_maps) like words_loss."""
+    lens = cap_lens.data.tolist() if torch.is_tensor(cap_lens) else list(cap_lens)
+    conf = attn_confidence(attn_map, lens, fused=fused).to(words_emb.dtype)
+    T = words_emb.shape[2]
+    conf = conf[:, :T] if conf.shape[1] >= T else F.pad(conf, (0, T - conf.shape[1]))
+    scaled = words_emb * conf[:, None, :]
+    if fused is None:
+        fused = scaled.is_cuda
+    sim, att = _damsm_sim(img_features, scaled, lens) if fused else _damsm_sim_torch(img_features, scaled, lens)
+    return _words_ranking(sim, att, lens, labels, class_ids, batch_size)
 
 
 def sent_similarity(cnn_code, rnn_code, eps=1e-8):
@@ -105,6 +189,49 @@ def words_similarity(img_features, words_emb, cap_lens, batch_size):
 def MSE(fake, label):
     """losses.py:779-784: sum over the image scales of the mean squared error."""
     return sum(F.mse_loss(f, t) for f, t in zip(fake, label))
+
+
+def _weight_mse_torch(fake, label, att):
+    """One scale of weight_MSE as the reference writes it (losses.py:796-800): (term, wups)."""
+    w = att.max(dim=1, keepdim=True)[0]
+    wups = F.interpolate(w, size=(fake.shape[2], fake.shape[3]))                  # nn.Upsample's default: nearest
+    l2 = (att.shape[1] * wups) * (fake - label).pow(2)
+    return l2.sum() / (fake.shape[2] * fake.shape[3] * fake.shape[0] * fake.shape[1]), wups
+
+
+def _weight_mse_fusable(fake, label, att):
+    """Float32 HIP tensors of shapes the kernels take: the shape rule is ops.check_weight_mse's, asked, not restated."""
+    if not all(torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 for t in (fake, label, att)):
+        return False
+    try:
+        ops.check_weight_mse(fake.shape, label.shape, att.shape)
+    except ops.TgsrError:
+        return False
+    return True
+
+
+def weight_MSE(fake, label, weight, fused=None):
+    """losses.py:792-804: sum over the image scales of sum(T wups (fake - label)^2) / (H W B C) with wups = the per-pixel maximum
+    over the T words of the scale's attention map `weight[i]` [B, T, h, w], up-sampled (nearest) to the image.  Returns (mseloss,
+    wlast), wlast = the last scale's wups [B, 1, H, W].  Differentiable w.r.t. fake, label and weight; the map's gradient goes to
+    the word that held the maximum, the lowest index on a tie (the reference pins none).
+    `fused` (not a reference argument): None = one forward and one backward launch per scale (autograd.WeightMSE) where the
+    tensors are float32 HIP tensors, H / h = W / w is an integer and T <= 255, the torch composition of the reference's
+    expression elsewhere (CPU tensors, any other ratio); False = the composition; True = the kernels or an error.  On the fused
+    path `wlast` carries no grad_fn: a caller that differentiates through wlast passes fused=False.  The two forms differ on a NaN
+    in a map: the kernels' strict comparison passes it over (the maximum of the other words), torch.max propagates it."""
+    mseloss, wlast = 0, None
+    for i in range(len(fake)):
+        last = i == len(fake) - 1
+        if fused or (fused is None and _weight_mse_fusable(fake[i], label[i], weight[i])):
+            from ..autograd import WeightMSE
+            mse, wups = WeightMSE.apply(fake[i], label[i], weight[i], last)
+        else:
+            mse, wups = _weight_mse_torch(fake[i], label[i], weight[i])
+        if last:
+            wlast = wups
+        mseloss = mseloss + mse
+    return mseloss, wlast
 
 
 def KL_loss(mu, logvar):
@@ -252,6 +379,28 @@ def generator_loss(netsD, image_encoder, fake_imgs, real_labels, words_embs, sen
     always has one; its Inception-v3 weights are third-party and not shipped) leaves the ranking term out.  `enc_out` (not a
     reference argument): `image_encoder(fake_imgs[-1])` computed by the caller already - the encoder reads the fake image only, not
     the discriminators, so train.SRTrainer runs it beside the discriminator updates that precede this call."""
+    return _generator_loss(words_loss, netsD, image_encoder, fake_imgs, real_labels, words_embs, sent_emb, match_labels, cap_lens,
+                           class_ids, w, s, g, streams, lazy_log, gather_negatives, enc_out)
+
+
+def generator_re_weight_loss(netsD, image_encoder, fake_imgs, real_labels, words_embs, sent_emb, match_labels, cap_lens,
+                             class_ids, w=1, s=1, g=1, attn=None, streams=None, lazy_log=False, enc_out=None, fused=None):
+    """losses.py:318-350: generator_loss with `words_reweight_loss` on the attention maps `attn` ([B, T, h, w] or a list of
+    per-image maps) in place of words_loss - the same terms, order and log text.  streams / lazy_log / enc_out as in
+    generator_loss, `fused` as in words_reweight_loss.  There is no gather_negatives form: the confidences would have to be
+    gathered with the words."""
+    if attn is None and image_encoder is not None and len(netsD) > 0:
+        raise ValueError("generator_re_weight_loss: attn (the generator's attention maps) is required for the ranking term")
+
+    def words(regions, words_embs, labels, cap_lens, class_ids, B):
+        return words_reweight_loss(regions, words_embs, labels, cap_lens, class_ids, B, attn, fused=fused)
+    return _generator_loss(words, netsD, image_encoder, fake_imgs, real_labels, words_embs, sent_emb, match_labels, cap_lens,
+                           class_ids, w, s, g, streams, lazy_log, False, enc_out)
+
+
+def _generator_loss(words_fn, netsD, image_encoder, fake_imgs, real_labels, words_embs, sent_emb, match_labels, cap_lens,
+                    class_ids, w, s, g, streams, lazy_log, gather_negatives, enc_out):
+    """The body of generator_loss / generator_re_weight_loss; words_fn = words_loss or its re-weighted form."""
     B = real_labels.size(0)
     total, parts = 0, []
     advs = []
@@ -296,7 +445,7 @@ def generator_loss(netsD, image_encoder, fake_imgs, real_labels, words_embs, sen
             if gather_negatives:        # (not a reference argument) data parallel: the ranking term of the global batch
                 w0, w1, s0, s1, scale, _ = damsm_terms(regions, code, words_embs, sent_emb, cap_lens, class_ids, gather=True)
             else:
-                w0, w1, _ = words_loss(regions, words_embs, match_labels, cap_lens, class_ids, B)
+                w0, w1, _ = words_fn(regions, words_embs, match_labels, cap_lens, class_ids, B)
                 s0, s1 = sent_loss(code, sent_emb, match_labels, class_ids, B)
                 scale = 1
             w_term = w * (w0 + w1) * cfg.TRAIN.SMOOTH.LAMBDA

@@ -2131,6 +2131,113 @@ def attn_panels(images: torch.Tensor, att: torch.Tensor, cap_lens, Mh: torch.Ten
     return panel, conf, order, maps
 
 
+# ----------------------------------------------------------------------------------------- attention-guided losses
+WMSE_MAX_WORDS = 255     # the saved argmax word of a map pixel is one byte
+
+
+def _dense_f32(t, name: str, what: str, form: str) -> torch.Tensor:
+    """A non-empty float32 tensor of as many dimensions as `form` ("[B, C, H, W]") names, or TgsrError."""
+    if not torch.is_tensor(t) or t.dtype != torch.float32 or t.dim() != form.count(",") + 1:
+        raise TgsrError("%s: %s must be a float32 %s tensor, got %s"
+                        % (what, name, form, "%s %s" % (t.dtype, tuple(t.shape)) if torch.is_tensor(t) else type(t).__name__))
+    if t.numel() == 0:
+        raise TgsrError("%s: %s %s is empty" % (what, name, tuple(t.shape)))
+    return t
+
+
+def check_weight_mse(fake_shape, label_shape, att_shape) -> Tuple[int, ...]:
+    """The shape checks of tgsr_weight_mse_fwd / _bwd (include/tgsr_hip.h) on the host and with a message: fake, label [B, C, H, W]
+    against att [B, T, h, w] with H = r h, W = r w for one integer r >= 1 and T <= 255.  Returns (B, C, T, H, W, h, w, r) or raises
+    TgsrError.  Touches no device."""
+    fs, ls, ms = (tuple(int(v) for v in s) for s in (fake_shape, label_shape, att_shape))
+    if len(fs) != 4 or len(ms) != 4 or min(fs) < 1 or min(ms) < 1:
+        raise TgsrError("weight_mse: fake [B, C, H, W] and att [B, T, h, w] expected, got %s and %s" % (fs, ms))
+    if ls != fs:
+        raise TgsrError("weight_mse: fake %s and label %s differ in shape" % (fs, ls))
+    (B, C, H, W), (Bm, T, h, w) = fs, ms
+    if Bm != B:
+        raise TgsrError("weight_mse: %d images against the maps of %d" % (B, Bm))
+    if T > WMSE_MAX_WORDS:
+        raise TgsrError("weight_mse: %d words per map, the kernels take at most %d (the saved argmax is one byte)" % (T, WMSE_MAX_WORDS))
+    if H % h or W % w or H // h != W // w:
+        raise TgsrError("weight_mse: %d x %d images over %d x %d maps is no integer ratio (the kernels take H = r h, W = r w; "
+                        "miscc.losses.weight_MSE(fused=False) interpolates any size)" % (H, W, h, w))
+    return B, C, T, H, W, h, w, H // h
+
+
+def attn_confidence(att: torch.Tensor, cap_lens: torch.Tensor) -> torch.Tensor:
+    """conf float32 [B, T] of words_reweight_loss (tgsr_attn_confidence): for t < cap_lens[b] the fp32 sum of the values of
+    att[b, t] strictly above float32(2 * (2 / cap_lens[b])), 0 behind the caption's length; a length outside [1, T] gives a zero
+    row.  att: float32 [B, T, ...] (the trailing dimensions are one map); cap_lens: int32 [B] ON THE DEVICE - nothing here reads it
+    on the host."""
+    if not torch.is_tensor(att) or att.dtype != torch.float32 or att.dim() < 3 or att.numel() == 0:
+        raise TgsrError("attn_confidence: att must be a non-empty float32 [B, T, ...] tensor, got %s"
+                        % ("%s %s" % (att.dtype, tuple(att.shape)) if torch.is_tensor(att) else type(att).__name__))
+    B, T = int(att.shape[0]), int(att.shape[1])
+    if T > WMSE_MAX_WORDS or B > 65535:
+        raise TgsrError("attn_confidence: %d captions of %d words; the kernel takes at most 65535 of %d" % (B, T, WMSE_MAX_WORDS))
+    if not torch.is_tensor(cap_lens) or cap_lens.dtype != torch.int32 or tuple(cap_lens.shape) != (B,):
+        raise TgsrError("attn_confidence: cap_lens must be an int32 [%d] tensor, got %s"
+                        % (B, "%s %s" % (cap_lens.dtype, tuple(cap_lens.shape)) if torch.is_tensor(cap_lens) else type(cap_lens).__name__))
+    _need_hip(att, cap_lens)
+    att = att.detach().contiguous()
+    conf = torch.empty(B, T, dtype=torch.float32, device=att.device)
+    check(_lib.lib().tgsr_attn_confidence(_p(att), _p(cap_lens.contiguous()), B, T, att.numel() // (B * T), _p(conf), _stream()),
+          "tgsr_attn_confidence")
+    return conf
+
+
+def weight_mse(fake: torch.Tensor, label: torch.Tensor, att: torch.Tensor, want_wlast: bool = False):
+    """One scale of weight_MSE (tgsr_weight_mse_fwd): (loss [], wmax float32 [B, h, w], widx uint8 [B, h, w], wlast float32
+    [B, 1, H, W] or [0]) - the term sum(T wups (fake - label)^2) / (H W B C), the per-pixel maximum over the words and its word (the
+    lowest on a tie) for `weight_mse_bwd`, and on request the up-sampled maximum."""
+    for name, t in (("fake", fake), ("label", label), ("att", att)):
+        _dense_f32(t, name, "weight_mse", "[B, T, h, w]" if name == "att" else "[B, C, H, W]")
+    B, C, T, H, W, h, w, _r = check_weight_mse(fake.shape, label.shape, att.shape)
+    _need_hip(fake, label, att)
+    fake, label, att = fake.detach().contiguous(), label.detach().contiguous(), att.detach().contiguous()
+    dev = fake.device
+    L = _lib.lib()
+    ws = torch.empty(L.tgsr_weight_mse_ws_elems(B, C, T, H, W, h, w), dtype=torch.float32, device=dev)
+    loss = torch.empty((), dtype=torch.float32, device=dev)
+    wmax = torch.empty(B, h, w, dtype=torch.float32, device=dev)
+    widx = torch.empty(B, h, w, dtype=torch.uint8, device=dev)
+    wlast = torch.empty((B, 1, H, W) if want_wlast else (0,), dtype=torch.float32, device=dev)
+    check(L.tgsr_weight_mse_fwd(_p(fake), _p(label), _p(att), B, C, T, H, W, h, w, _p(ws), _p(loss), _p(wmax), _p(widx),
+                                _p(wlast) if want_wlast else None, _stream()), "tgsr_weight_mse_fwd")
+    return loss, wmax, widx, wlast
+
+
+def weight_mse_bwd(grad: torch.Tensor, fake: torch.Tensor, label: torch.Tensor, wmax: torch.Tensor, widx: torch.Tensor, T: int,
+                   need_fake: bool = True, need_label: bool = False, need_att: bool = False):
+    """(d_fake, d_label, d_att) of weight_mse (tgsr_weight_mse_bwd), None where not asked for: grad the [] gradient of the term,
+    wmax / widx what the forward saved, T the number of words.  d_att [B, T, h, w] is written completely (zeros off the argmax)."""
+    for name, t in (("fake", fake), ("label", label)):
+        _dense_f32(t, name, "weight_mse_bwd", "[B, C, H, W]")
+    _dense_f32(wmax, "wmax", "weight_mse_bwd", "[B, h, w]")
+    if not torch.is_tensor(widx) or widx.dtype != torch.uint8 or widx.shape != wmax.shape:
+        raise TgsrError("weight_mse_bwd: widx must be uint8 %s like wmax, got %s"
+                        % (tuple(wmax.shape), "%s %s" % (widx.dtype, tuple(widx.shape)) if torch.is_tensor(widx) else type(widx).__name__))
+    if not torch.is_tensor(grad) or grad.dtype != torch.float32 or grad.numel() != 1:
+        raise TgsrError("weight_mse_bwd: grad must be one float32 value, got %s"
+                        % ("%s %s" % (grad.dtype, tuple(grad.shape)) if torch.is_tensor(grad) else type(grad).__name__))
+    T = int(T)
+    if T < 1:
+        raise TgsrError("weight_mse_bwd: T = %d words" % T)
+    B, C, T, H, W, h, w, _r = check_weight_mse(fake.shape, label.shape, (wmax.shape[0], T, wmax.shape[1], wmax.shape[2]))
+    if not (need_fake or need_label or need_att):
+        raise TgsrError("weight_mse_bwd: no gradient asked for")
+    _need_hip(grad, fake, label, wmax, widx)
+    fake, label = fake.detach().contiguous(), label.detach().contiguous()
+    dev = fake.device
+    d_fake = torch.empty(B, C, H, W, dtype=torch.float32, device=dev) if need_fake else None
+    d_label = torch.empty(B, C, H, W, dtype=torch.float32, device=dev) if need_label else None
+    d_att = torch.empty(B, T, h, w, dtype=torch.float32, device=dev) if need_att else None
+    check(_lib.lib().tgsr_weight_mse_bwd(_p(grad.contiguous()), _p(fake), _p(label), _p(wmax.contiguous()), _p(widx.contiguous()),
+                                         B, C, T, H, W, h, w, _p(d_fake), _p(d_label), _p(d_att), _stream()), "tgsr_weight_mse_bwd")
+    return d_fake, d_label, d_att
+
+
 # ----------------------------------------------------------------------------------------- discriminator convolutions
 def _dconv(kind: int):
     L = _lib.lib()

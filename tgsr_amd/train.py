@@ -114,7 +114,8 @@ class GraphPolicy:
 
 class SRTrainer:
     def __init__(self, n_words, device="cuda", low="lr", lr=None, ema_decay=0.999, image_encoder=None,
-                 discriminators=False, d_lr=None, gather_negatives=None, weightmap=False, use_act=True):
+                 discriminators=False, d_lr=None, gather_negatives=None, weightmap=False, use_act=True, pixel_loss="mse",
+                 reweight=False):
         """image_encoder: optional frozen module image [B,3,256,256] -> (region features [B,nef,17,17], cnn_code
         [B,nef]) (a CNN_ENCODER with its trunk): adds the DAMSM ranking term of generator_loss (losses.py:375-386)
         on the finest image, x TRAIN.SMOOTH.LAMBDA.
@@ -127,11 +128,27 @@ class SRTrainer:
         trainer TGSR was forked from) are the build's declaration.
         weightmap / use_act: NetG_highweight's form (model.py:212-298).  weightmap=True trains the maps a1..a3 (64 / 128 /
         256 pixels: 32 x 32 LR) with the other generator parameters (flat gradient bucket, Adam, EMA); use_act=False drops
-        the heads' Tanh."""
+        the heads' Tanh.
+        pixel_loss: "mse" (default) or "weight_mse" - the pixel term becomes weight_MSE(fake_imgL, HR, att)[0] + weight_MSE(fine_im,
+        HR, att)[0] (losses.py:792-804) on the three attention maps G_SR_NET_low returns (32^2 / 64^2 / 128^2 under the 64^2 / 128^2 /
+        256^2 images).  The reference ships no training loop: pairing both generators' images with the same maps is the build's
+        declaration, like the update order.  The maps leave the generator's attention kernels without a gradient path, so the term
+        reads them as weights.
+        reweight: the ranking term scales every word by the confidence of the LAST attention map (words_reweight_loss /
+        generator_re_weight_loss, losses.py:137-232, 318-350; detached, as there); needs `image_encoder`.
+        Either option keeps the generators' update on the eager path (`_g_graphs`); reweight with gather_negatives and more than
+        one rank is refused: the confidences would have to be gathered with the words."""
+        if pixel_loss not in ("mse", "weight_mse"):
+            raise ValueError("pixel_loss must be 'mse' or 'weight_mse', got %r" % (pixel_loss,))
+        self.pixel_loss, self.reweight = pixel_loss, bool(reweight)
+        if self.reweight and image_encoder is None:
+            raise ValueError("reweight=True re-weights the DAMSM ranking term: it needs an image_encoder")
+        self._att, self.attn_fused = None, None        # the step's attention maps; `fused` of the attention-guided losses
         self.device = torch.device(device)
         cuda = self.device.type == "cuda"
         # data parallel: the DAMSM ranking term on the gathered global batch (parallel.GATHER_NEGATIVES, default on) or per shard
         self.gather_negatives = parallel.GATHER_NEGATIVES if gather_negatives is None else bool(gather_negatives)
+        self._check_reweight()
         self._packs = autograd.PackCache() if (cuda and os.environ.get("TGSR_PACK_CACHE", "1") != "0") else None
         self.image_encoder = image_encoder
         self.text_encoder = RNN_ENCODER(n_words, nhidden=cfg.TEXT.EMBEDDING_DIM).to(self.device).eval()
@@ -246,6 +263,17 @@ class SRTrainer:
         # the stream the generators' graphs are captured on, and the branch their re-pack launches fork onto
         self._gcap, self._gpack = streams(2) if self._graph_capable else (None, None)
 
+    @property
+    def _attn_losses(self):
+        """A loss of this trainer reads the generator's attention maps (pixel_loss="weight_mse" or reweight)."""
+        return self.pixel_loss == "weight_mse" or self.reweight
+
+    def _check_reweight(self):
+        if self.reweight and self.gather_negatives and dp_world() > 1:
+            raise ValueError("reweight=True with gather_negatives on %d ranks: the ranking term of the gathered global batch would "
+                             "need every rank's word confidences gathered too, which is not built; pass gather_negatives=False"
+                             % dp_world())
+
     def _adam(self, bucket, params, lr, capturable):
         """FlatAdam over this bucket (TGSR_FLAT_ADAM), else torch's Adam over `params`: Adam(lr, betas (0.5, 0.999)) either way."""
         if self._flat_adam:
@@ -338,7 +366,8 @@ class SRTrainer:
     def _forward_nets(self, LR, LRb, words_embs, sent_emb, mask):
         # (NetG_highweight's trunk on a second stream beside G_SR_NET_low, forward and backward, was measured: 11.9 ms
         # against 11.6 ms on one stream once the weight gradients have their side stream - not kept)
-        fake_imgL, _att, mu, logvar = self.netGL(LR, sent_emb, words_embs, mask)
+        fake_imgL, att, mu, logvar = self.netGL(LR, sent_emb, words_embs, mask)
+        self._att = [a.detach() for a in att] if self._attn_losses else None
         fine_im, _a, _one = self.netGH(LR, fake_imgL, LRb)
         return fake_imgL, fine_im, mu, logvar
 
@@ -360,9 +389,16 @@ class SRTrainer:
         outputs on the finest fake image when `_encode_early` has computed them already."""
         B = sent_emb.shape[0]
         real_labels, _fake, match_labels = prepare_labels(B, self.device)
-        adv, _log = losses.generator_loss(self.netsD, self.image_encoder, fine_im, real_labels, words_embs, sent_emb,
-                                          match_labels, cap_lens, class_ids, streams=self._dstreams or None, lazy_log=True,
-                                          gather_negatives=self.gather_negatives, enc_out=enc_out)
+        if self.reweight:
+            self._check_reweight()
+            adv, _log = losses.generator_re_weight_loss(self.netsD, self.image_encoder, fine_im, real_labels, words_embs, sent_emb,
+                                                        match_labels, cap_lens, class_ids, attn=self._att[-1],
+                                                        streams=self._dstreams or None, lazy_log=True, enc_out=enc_out,
+                                                        fused=self.attn_fused)
+        else:
+            adv, _log = losses.generator_loss(self.netsD, self.image_encoder, fine_im, real_labels, words_embs, sent_emb,
+                                              match_labels, cap_lens, class_ids, streams=self._dstreams or None, lazy_log=True,
+                                              gather_negatives=self.gather_negatives, enc_out=enc_out)
         return adv + self._pixel_kl(fake_imgL, fine_im, mu, logvar, hr_pyramid)
 
     def _encode_early(self, image):
@@ -580,8 +616,9 @@ class SRTrainer:
         the optimizer's state or hyper-parameters drops every shape's capture, the failed ones included."""
         use = self._policy.replays(self._gsteps)
         self._gsteps += 1
-        if not use or (self.image_encoder is not None and self.gather_negatives and dp_world() > 1):
-            return None                     # (DAMSM on the gathered global batch all-gathers inside generator_loss)
+        if not use or self._attn_losses or (self.image_encoder is not None and self.gather_negatives and dp_world() > 1):
+            # (DAMSM on the gathered global batch all-gathers inside generator_loss; the attention-guided losses are not captured yet)
+            return None
         hyper = self._opt_key(self.opt) + (self.ema_decay,)
         if hyper != self._ghyper:
             self._ggraphs, self._ghyper = {}, hyper
@@ -592,6 +629,9 @@ class SRTrainer:
         return g or None
 
     def _pixel_kl(self, fake_imgL, fine_im, mu, logvar, hr_pyramid):
+        if self.pixel_loss == "weight_mse":
+            return (losses.weight_MSE(fake_imgL, hr_pyramid, self._att, fused=self.attn_fused)[0] +
+                    losses.weight_MSE(fine_im, hr_pyramid, self._att, fused=self.attn_fused)[0] + losses.KL_loss(mu, logvar))
         return losses.MSE(fake_imgL, hr_pyramid) + losses.MSE(fine_im, hr_pyramid) + losses.KL_loss(mu, logvar)
 
     def _loss_from(self, fake_imgL, fine_im, mu, logvar, words_embs, sent_emb, cap_lens, hr_pyramid, class_ids):
@@ -599,8 +639,17 @@ class SRTrainer:
         errG = self._pixel_kl(fake_imgL, fine_im, mu, logvar, hr_pyramid)
         if self.image_encoder is not None:
             region_features, cnn_code = self.image_encoder(fine_im[-1])
-            w0, w1, s0, s1, scale, _ = losses.damsm_terms(region_features, cnn_code, words_embs, sent_emb, cap_lens, class_ids,
-                                                          gather=self.gather_negatives)
+            if self.reweight:
+                self._check_reweight()
+                B = sent_emb.shape[0]
+                labels = torch.arange(B, device=sent_emb.device)
+                w0, w1, _ = losses.words_reweight_loss(region_features, words_embs, labels, cap_lens, class_ids, B, self._att[-1],
+                                                       fused=self.attn_fused)
+                s0, s1 = losses.sent_loss(cnn_code, sent_emb, labels, class_ids, B)
+                scale = 1
+            else:
+                w0, w1, s0, s1, scale, _ = losses.damsm_terms(region_features, cnn_code, words_embs, sent_emb, cap_lens, class_ids,
+                                                              gather=self.gather_negatives)
             errG = errG + (w0 + w1 + s0 + s1) * (cfg.TRAIN.SMOOTH.LAMBDA * scale)
         return errG
 
