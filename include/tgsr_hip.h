@@ -310,6 +310,19 @@ int tgsr_word_project_fwd(const float* words, const float* const* w_ctx, int nse
  * w_ih [2][4H][ninput], w_hh [2][4H][H], b_ih/b_hh [2][4H]  (direction 0 = forward, 1 = reverse; gate order i,f,g,o)
  * gates_ws workspace B*Tmax*2*4H floats.
  * words_emb [B][2H][Tmax] (zero beyond each length), sent_emb [B][2H].   H <= 256, 4H % 64 == 0.
+ *
+ * What holds for every entry point of this family (LSTM and GRU, forward and backward; tests/test_hip_rnn_abi.py):
+ *   - alignment: w_hh of a FORWARD call must be 16-byte aligned wherever a register kernel runs it - H in {32, 64, 128}, LSTM and
+ *     GRU, whose threads read their w_hh rows as float4; a w_hh that is not is refused with TGSR_EUNSUPPORTED (tgsr_last_error()
+ *     says so) before anything is launched.  The LSTM forward at any other H and both backwards read w_hh by single floats.  Every
+ *     other float / int32 operand, outputs and workspaces included, needs 4-byte alignment only (captions: 8), and the results do
+ *     not depend on it.
+ *   - lengths: cap_lens[b] is clamped into [0, Tmax]: a length above Tmax acts as Tmax; a length <= 0 gives a sample whose
+ *     words_emb rows and sent_emb row are all zero (and, in the backwards, all-zero gradient and hprev rows).
+ *   - tokens: a caption entry outside [0, ntoken) reads row 0 of emb / of the table.
+ *   - acts (training forms): the rows of the steps t >= cap_lens[b] are neither written by the forward nor read by the
+ *     backward; the caller need not clear them.
+ *   - the gate workspace is written before it is read: the results do not depend on what it held.
  */
 int tgsr_bilstm_fwd(const int64_t* captions, int width, const int32_t* cap_lens, int B, int Tmax, const float* emb,
                     int ntoken, int ninput, const float* w_ih, const float* w_hh, const float* b_ih,
@@ -328,11 +341,26 @@ int tgsr_bilstm_table_fwd(const int64_t* captions, int width, const int32_t* cap
                           void* stream);
 
 /*
+ * Which recurrence kernel the three LSTM forwards above and below (tgsr_bilstm_fwd, tgsr_bilstm_table_fwd,
+ * tgsr_bilstm_train_fwd) run for (H, Tmax): one of TGSR_LSTM_RECURRENT_*, or TGSR_EUNSUPPORTED (H < 1, H > 256 or
+ * 4H % 64 != 0).  Host only, launches nothing; the launcher switches on the same answer.  Every instance but
+ * TGSR_LSTM_RECURRENT_GENERIC reads w_hh as float4 (the alignment rule above).  The environment variable TGSR_LSTM_ONE_ROW
+ * (an A/B switch of the tools, read once per process) sends H = 128 to TGSR_LSTM_RECURRENT_128 at every Tmax.
+ */
+#define TGSR_LSTM_RECURRENT2_128 1    /* lstm_recurrent2_kernel<128, 24, 4>: H == 128, Tmax <= 24 (its steps are staged in LDS) */
+#define TGSR_LSTM_RECURRENT_128 2     /* lstm_recurrent_kernel<128>: H == 128, Tmax > 24 */
+#define TGSR_LSTM_RECURRENT_64 3      /* lstm_recurrent_kernel<64> */
+#define TGSR_LSTM_RECURRENT_32 4      /* lstm_recurrent_kernel<32> */
+#define TGSR_LSTM_RECURRENT_GENERIC 5 /* lstm_recurrent_generic_kernel: every other H, 4H threads */
+int tgsr_lstm_recurrent_plan(int H, int Tmax);
+
+/*
  * The GRU branch of RNN_ENCODER (util.py:207-211: `nn.GRU(ninput, nhidden, 1, batch_first=True, bidirectional=True)` when
  * cfg.RNN_TYPE == 'GRU'; forward util.py:233-260, sent_emb = the final hidden states, :257), eval mode, same packed-sequence
  * semantics.  Gate order r, z, n.  tgsr_gru_gate_table: table[ntoken][2][3H] = emb[tok] . w_ih[d]^T + b_ih[d] + b_hh_rz[d], where
  * b_hh_rz [2][3H] = b_hh with its n third zeroed (b_hn enters inside r * (W_hn h + b_hn)); tgsr_bigru_table_fwd: the recurrence
  * through the caption, b_hn [2][H].  words_emb [B][2H][Tmax] (zero behind a caption), sent_emb [B][2H].  H in {32, 64, 128}.
+ * w_hh [2][3H][H] 16-byte aligned; lengths, tokens and every other operand as stated at tgsr_bilstm_fwd.
  */
 int tgsr_gru_gate_table(const float* emb, int ntoken, int ninput, const float* w_ih, const float* b_ih, const float* b_hh_rz,
                         int H, float* table, void* stream);
@@ -347,7 +375,8 @@ int tgsr_bigru_table_fwd(const int64_t* captions, int width, const int32_t* cap_
  * through time from d_words [B][2H][Tmax] and d_sent [B][2H] (NULL = zero): dgx / dgh [B][Tmax][2][3H] = the gradients at the
  * input-side (x W_ih^T + b_ih) and hidden-side (h W_hh^T + b_hh) gate pre-activations, hprev [B][Tmax][2][H] = h of the previous
  * step, dbias [2][2][3H] = (d b_ih, d b_hh) (NULL: skipped).  The caller's GEMMs give dW_ih = dgx^T x, dW_hh = dgh^T hprev,
- * dx = dgx W_ih.  Fixed summation orders.  H in {32, 64, 128}.
+ * dx = dgx W_ih.  Fixed summation orders.  H in {32, 64, 128}.  dgx, dgh and hprev are zero at the steps behind a caption;
+ * acts rows of those steps are not written by the forward and not read by the backward.  w_hh: 16-byte aligned for the forward.
  */
 int tgsr_bigru_train_fwd(const float* x, const int32_t* cap_lens, int B, int Tmax, int ninput, const float* w_ih,
                          const float* w_hh, const float* b_ih, const float* b_hh_rz, const float* b_hn, int H, float* gates_ws,
@@ -363,7 +392,8 @@ int tgsr_bigru_bwd(const int32_t* cap_lens, int B, int Tmax, int H, const float*
  * caption), hprev [B][Tmax][2][H] (the hidden state entering each step) and dbias [2][4H] (= d b_ih = d b_hh; may be
  * NULL).  The weight / input gradients are plain GEMMs on those (tgsr_linear_fwd):
  *   dW_ih[d] = dgates[:, :, d]^T x,   dW_hh[d] = dgates[:, :, d]^T hprev[:, :, d],   dx = dgates W_ih.
- * H in {32, 64, 128} for the backward.
+ * H in {32, 64, 128} for the backward.  hprev is zero past the caption as dgates is; acts rows of the steps past a caption
+ * are not written by the forward and not read by the backward; alignment, lengths as stated at tgsr_bilstm_fwd.
  */
 int tgsr_bilstm_train_fwd(const float* x, const int32_t* cap_lens, int B, int Tmax, int ninput, const float* w_ih,
                           const float* w_hh, const float* b_ih, const float* b_hh, int H, float* gates_ws, float* acts,

@@ -31,6 +31,11 @@ CONV_PLAN_FIELDS = 15                                               # int fields
 (CONV_PLAN_FAMILY, CONV_PLAN_T, CONV_PLAN_GRID_X, CONV_PLAN_GRID_Y, CONV_PLAN_BLOCK, CONV_PLAN_TILES_X, CONV_PLAN_TILES_Y,
  CONV_PLAN_TILE_H, CONV_PLAN_TILE_W, CONV_PLAN_STAGES, CONV_PLAN_GROUPS, CONV_PLAN_NSLOTS) = (0, 1, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14)
 
+# what tgsr_lstm_recurrent_plan answers (TGSR_LSTM_RECURRENT_*) -> the recurrence instance the LSTM forwards launch
+LSTM_RECURRENT = {1: "lstm_recurrent2_kernel<128,24,4>", 2: "lstm_recurrent_kernel<128>", 3: "lstm_recurrent_kernel<64>",
+                  4: "lstm_recurrent_kernel<32>", 5: "lstm_recurrent_generic_kernel"}
+LSTM_RECURRENT_GENERIC = 5                                          # the one instance that reads w_hh by single floats
+
 _vp, _i, _i64, _f, _d = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_float, ctypes.c_double
 
 # name -> (restype, argtypes); must list every function of include/tgsr_hip.h (tests/test_abi.py checks it)
@@ -74,6 +79,7 @@ SIGNATURES = {
     "tgsr_bilstm_fwd": (_i, [_vp, _i, _vp, _i, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
     "tgsr_lstm_gate_table": (_i, [_vp, _i, _i, _vp, _vp, _vp, _i, _vp, _vp]),
     "tgsr_bilstm_table_fwd": (_i, [_vp, _i, _vp, _i, _i, _vp, _i, _vp, _i, _vp, _vp, _vp]),
+    "tgsr_lstm_recurrent_plan": (_i, [_i, _i]),
     "tgsr_bilstm_train_fwd": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
     "tgsr_bilstm_bwd": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "tgsr_damsm_words_fwd": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _f, _f, _vp, _vp, _vp]),

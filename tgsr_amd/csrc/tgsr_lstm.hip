@@ -87,7 +87,9 @@ __global__ __launch_bounds__(256) void lstm_input_gates_kernel(const int64_t* __
 
 __device__ __forceinline__ float sigmoidf_(float x) { return 1.f / (1.f + expf(-x)); }
 // the register kernel's step is latency, not throughput: v_exp_f32 / v_rcp_f32 forms (absolute error ~1e-7, far inside the
-// 1e-5 the encoder is pinned to) instead of the ~40-instruction library expf / tanhf
+// 1e-5 the encoder is pinned to) instead of the ~40-instruction library expf / tanhf.  Measured against fp64
+// (tests/test_hip_rnn_abi.py): h within 0.8e-7 .. 1.8e-7 at nn.LSTM-scale weights, 4.3e-7 (LSTM) / 6.7e-7 (GRU) with saturated
+// gates, 1.1 .. 4.3 x the distance of torch's fp32 run on the CPU - the range the library forms of the generic kernel have too.
 __device__ __forceinline__ float fsig_(float x) { return __builtin_amdgcn_rcpf(1.f + __expf(-x)); }
 __device__ __forceinline__ float ftanh_(float x) { return 1.f - 2.f * __builtin_amdgcn_rcpf(__expf(2.f * x) + 1.f); }
 
@@ -429,26 +431,59 @@ extern "C" int tgsr_debug_read_lstamps(unsigned long long* host, int n) {
 }
 #endif
 
+// Which recurrence instance launch_recurrent takes for (H, Tmax): the one place that decides it (include/tgsr_hip.h).
+extern "C" int tgsr_lstm_recurrent_plan(int H, int Tmax) {
+  static const bool one_row = getenv("TGSR_LSTM_ONE_ROW") != nullptr;       // A/B switch (tools, DESIGN 3.4)
+  if (H < 1 || H > 256 || (4 * H) % 64 != 0) return TGSR_EUNSUPPORTED;
+  if (H == 128 && !one_row && Tmax <= 24) return TGSR_LSTM_RECURRENT2_128;
+  if (H == 128) return TGSR_LSTM_RECURRENT_128;
+  if (H == 64) return TGSR_LSTM_RECURRENT_64;
+  if (H == 32) return TGSR_LSTM_RECURRENT_32;
+  return TGSR_LSTM_RECURRENT_GENERIC;
+}
+
+// The register kernels (every instance but the generic one, and gru_recurrent_kernel<H>) read their w_hh rows as float4.
+static int refuse_unaligned_w_hh(const float* w_hh, const char* what) {
+  if ((reinterpret_cast<uintptr_t>(w_hh) & 15) == 0) return TGSR_OK;
+  note_error(what, "w_hh must be 16-byte aligned for this H (its rows are read as float4)", TGSR_EUNSUPPORTED);
+  return TGSR_EUNSUPPORTED;
+}
+
+// 0, or the refusal of an LSTM forward: no instance for H, or a float4 instance and a w_hh it cannot read
+static int lstm_forward_refusal(int H, int Tmax, const float* w_hh) {
+  const int plan = tgsr_lstm_recurrent_plan(H, Tmax);
+  if (plan < 0) return plan;
+  return plan == TGSR_LSTM_RECURRENT_GENERIC ? TGSR_OK : refuse_unaligned_w_hh(w_hh, "lstm_recurrent_kernel");
+}
+
 static int launch_recurrent(const float* gates, const int32_t* cap_lens, int B, int Tmax, const float* w_hh, int H,
                             float* words_emb, float* sent_emb, const int64_t* captions, int width, int ntoken,
                             hipStream_t s, float* acts = nullptr) {
   dim3 grid(B, 2);
-  static const bool one_row = getenv("TGSR_LSTM_ONE_ROW") != nullptr;       // A/B switch (tools, DESIGN 3.4)
-  if (H == 128 && !one_row && Tmax <= 24)
-    hipLaunchKernelGGL((lstm_recurrent2_kernel<128, 24, 4>), grid, dim3(512), 0, s, gates, cap_lens, Tmax, w_hh, words_emb,
-                       sent_emb, captions, width, ntoken, acts);
-  else if (H == 128)
-    hipLaunchKernelGGL(lstm_recurrent_kernel<128>, grid, dim3(512), 0, s, gates, cap_lens, Tmax, w_hh, words_emb,
-                       sent_emb, captions, width, ntoken, acts);
-  else if (H == 64)
-    hipLaunchKernelGGL(lstm_recurrent_kernel<64>, grid, dim3(256), 0, s, gates, cap_lens, Tmax, w_hh, words_emb,
-                       sent_emb, captions, width, ntoken, acts);
-  else if (H == 32)
-    hipLaunchKernelGGL(lstm_recurrent_kernel<32>, grid, dim3(128), 0, s, gates, cap_lens, Tmax, w_hh, words_emb,
-                       sent_emb, captions, width, ntoken, acts);
-  else
-    hipLaunchKernelGGL(lstm_recurrent_generic_kernel, grid, dim3(4 * H), 0, s, gates, cap_lens, Tmax, H, w_hh,
-                       words_emb, sent_emb, captions, width, ntoken, acts);
+  switch (tgsr_lstm_recurrent_plan(H, Tmax)) {
+    case TGSR_LSTM_RECURRENT2_128:
+      hipLaunchKernelGGL((lstm_recurrent2_kernel<128, 24, 4>), grid, dim3(512), 0, s, gates, cap_lens, Tmax, w_hh, words_emb,
+                         sent_emb, captions, width, ntoken, acts);
+      break;
+    case TGSR_LSTM_RECURRENT_128:
+      hipLaunchKernelGGL(lstm_recurrent_kernel<128>, grid, dim3(512), 0, s, gates, cap_lens, Tmax, w_hh, words_emb,
+                         sent_emb, captions, width, ntoken, acts);
+      break;
+    case TGSR_LSTM_RECURRENT_64:
+      hipLaunchKernelGGL(lstm_recurrent_kernel<64>, grid, dim3(256), 0, s, gates, cap_lens, Tmax, w_hh, words_emb,
+                         sent_emb, captions, width, ntoken, acts);
+      break;
+    case TGSR_LSTM_RECURRENT_32:
+      hipLaunchKernelGGL(lstm_recurrent_kernel<32>, grid, dim3(128), 0, s, gates, cap_lens, Tmax, w_hh, words_emb,
+                         sent_emb, captions, width, ntoken, acts);
+      break;
+    case TGSR_LSTM_RECURRENT_GENERIC:
+      hipLaunchKernelGGL(lstm_recurrent_generic_kernel, grid, dim3(4 * H), 0, s, gates, cap_lens, Tmax, H, w_hh,
+                         words_emb, sent_emb, captions, width, ntoken, acts);
+      break;
+    default:
+      return TGSR_EUNSUPPORTED;
+  }
   return note_launch(hipGetLastError(), "lstm_recurrent_kernel");
 }
 
@@ -459,7 +494,7 @@ extern "C" int tgsr_bilstm_fwd(const int64_t* captions, int width, const int32_t
   if (!captions || !cap_lens || !emb || !w_ih || !w_hh || !b_ih || !b_hh || !gates_ws || !words_emb || !sent_emb)
     return TGSR_EINVAL;
   if (B < 1 || Tmax < 1 || Tmax > width || ntoken < 1 || ninput < 1 || H < 1) return TGSR_EINVAL;
-  if (H > 256 || (4 * H) % 64 != 0) return TGSR_EUNSUPPORTED;
+  if (const int rc = lstm_forward_refusal(H, Tmax, w_hh)) return rc;
   hipStream_t s = as_stream(stream);
   const int M = B * Tmax, N = 8 * H;
   hipLaunchKernelGGL(lstm_input_gates_kernel, dim3((N + 127) / 128, (M + 31) / 32), dim3(256), 0, s, captions, width,
@@ -633,6 +668,8 @@ extern "C" int tgsr_bigru_table_fwd(const int64_t* captions, int width, const in
                                     float* words_emb, float* sent_emb, void* stream) {
   if (!captions || !cap_lens || !table || !w_hh || !b_hn || !words_emb || !sent_emb) return TGSR_EINVAL;
   if (B < 1 || Tmax < 1 || Tmax > width || ntoken < 1 || H < 1) return TGSR_EINVAL;
+  if (H != 128 && H != 64 && H != 32) return TGSR_EUNSUPPORTED;
+  if (const int rc = refuse_unaligned_w_hh(w_hh, "gru_recurrent_kernel")) return rc;
   hipStream_t s = as_stream(stream);
   const dim3 grid(B, 2);
   if (H == 128)
@@ -659,6 +696,7 @@ extern "C" int tgsr_bigru_train_fwd(const float* x, const int32_t* cap_lens, int
     return TGSR_EINVAL;
   if (B < 1 || Tmax < 1 || ninput < 1 || H < 1) return TGSR_EINVAL;
   if (H != 128 && H != 64 && H != 32) return TGSR_EUNSUPPORTED;
+  if (const int rc = refuse_unaligned_w_hh(w_hh, "gru_recurrent_kernel(train)")) return rc;
   hipStream_t s = as_stream(stream);
   const int M = B * Tmax, N = 6 * H;
   hipLaunchKernelGGL(lstm_input_gates_kernel, dim3((N + 127) / 128, (M + 31) / 32), dim3(256), 0, s, (const int64_t*)nullptr, 1, 1,
@@ -708,7 +746,7 @@ extern "C" int tgsr_bilstm_table_fwd(const int64_t* captions, int width, const i
                                      float* sent_emb, void* stream) {
   if (!captions || !cap_lens || !table || !w_hh || !words_emb || !sent_emb) return TGSR_EINVAL;
   if (B < 1 || Tmax < 1 || Tmax > width || ntoken < 1 || H < 1) return TGSR_EINVAL;
-  if (H > 256 || (4 * H) % 64 != 0) return TGSR_EUNSUPPORTED;
+  if (const int rc = lstm_forward_refusal(H, Tmax, w_hh)) return rc;
   return launch_recurrent(table, cap_lens, B, Tmax, w_hh, H, words_emb, sent_emb, captions, width, ntoken,
                           as_stream(stream));
 }
@@ -721,7 +759,7 @@ extern "C" int tgsr_bilstm_train_fwd(const float* x, const int32_t* cap_lens, in
   if (!x || !cap_lens || !w_ih || !w_hh || !b_ih || !b_hh || !gates_ws || !acts || !words_emb || !sent_emb)
     return TGSR_EINVAL;
   if (B < 1 || Tmax < 1 || ninput < 1 || H < 1) return TGSR_EINVAL;
-  if (H > 256 || (4 * H) % 64 != 0) return TGSR_EUNSUPPORTED;
+  if (const int rc = lstm_forward_refusal(H, Tmax, w_hh)) return rc;
   hipStream_t s = as_stream(stream);
   const int M = B * Tmax, N = 8 * H;
   hipLaunchKernelGGL(lstm_input_gates_kernel, dim3((N + 127) / 128, (M + 31) / 32), dim3(256), 0, s,
