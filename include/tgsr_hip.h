@@ -505,6 +505,8 @@ int tgsr_text_tail_fwd(const float* words, const float* const* w_ctx, int nsets,
  *         the MFMA 32x32x16 A fragments of the scores GEMM (0, 1) and the context GEMM (2, 3);
  *     [B] uint32: bit t = (captions[b][t] == 0), t < T.
  * idf must be 32 (the generators' ngf).  src_out / mu / logvar / mask as tgsr_text_tail_fwd, bit-identical.
+ * Fragment f, lane l, element j holds src[i][t] with (i, t) = (16 f + 8 (l >> 5) + j, l & 31) for f < 2 and
+ * (l & 31, 16 (f - 2) + 8 (j >> 2) + 4 (l >> 5) + (j & 3)) for f >= 2; every element and every mask word is written.
  */
 int64_t tgsr_lp_att_pack_bytes(int nsets, int B);
 int tgsr_text_tail_lp_fwd(const float* words, const float* const* w_ctx, int nsets, int B, int idf, int cdf, int T,
@@ -1018,11 +1020,24 @@ int tgsr_conv_to3_bwd(const float* dy, const float* out, const float* addend, fl
  * reads / writes: two producers writing channel ranges [0,32) and [32,64) of one cpitch-64 image replace the
  * reference's torch.cat((h_code, c_code), 1) (util.py:771, 817).  All pointers are to element [0][0][0][0] of the
  * padded image.  Shapes: W % 32 == 0, H % 4 == 0 (every layer of the x8 / x16 generators at LR >= 32).
+ *
+ * What holds for every entry of this section (tests/test_hip_lp_abi.py calls each one on operands in a guarded arena):
+ *   - an lp image, a weight pack and `att_pack` are 16-byte aligned (the c_img of tgsr_lp_word_attention_fwd: 8-byte); channel
+ *     pitches and offsets are multiples of 8 elements unless an entry says 4; an offset is >= 0 and offset + width <= pitch.
+ *     An entry returns TGSR_EUNSUPPORTED for what breaks these rules, TGSR_EINVAL for a NULL that may not be NULL, a size < 1
+ *     or an unknown dtype / epilogue / act / mask_mode - always in front of the launch, no operand touched;
+ *   - a call writes the interior pixels x the channel range it names and nothing else: the border, the channels of the image
+ *     outside [coff, coff + width) and every input keep their bits.  Every element of the written range is written;
+ *   - per-sample images stay below 2 GiB: (H + 2) (W + 2) cpitch 2 < 2^31 for every image of a call (the residual's included);
+ *   - fp32 operands (scale, shift, addend, amap, src, attn, head_partial, low, high) are dense and 4-byte aligned unless an
+ *     entry says 16.
  */
 #define TGSR_DT_BF16 1
 #define TGSR_DT_F16 2
 
-/* fp32 NCHW [B][C][H][W] <-> channels [coff, coff + C) of an lp image (interior pixels only). */
+/* fp32 NCHW [B][C][H][W] <-> channels [coff, coff + C) of an lp image (interior pixels only).  Element by element: any H, W,
+ * cpitch and coff (2-byte aligned image, 4-byte aligned fp32 tensor); coff < 0 or coff + C > cpitch is TGSR_EINVAL.  One
+ * round-to-nearest-even per element on the way in, exact on the way out. */
 int tgsr_lp_from_nchw(int dtype, const float* x, void* out, int B, int C, int H, int W, int cpitch, int coff,
                       void* stream);
 int tgsr_lp_to_nchw(int dtype, const void* x, float* out, int B, int C, int H, int W, int cpitch, int coff,
@@ -1031,12 +1046,14 @@ int tgsr_lp_to_nchw(int dtype, const void* x, float* out, int B, int C, int H, i
 /* An lp image (any shape; the whole buffer incl. its zero border, n_elems % 8 == 0, 16-byte aligned) from one 2-byte type
  * to the other: TGSR_DT_F16 -> TGSR_DT_BF16 (one round-to-nearest-even) or back (exact while |x| < 65504).  Used where a
  * section of a generator runs with f16 operands inside the bf16 configuration (NetG_highweight's 32x32 trunk: the six
- * chained ResBlocks of model.py:258-262 are where 8-bit mantissas cost the finest image 7 dB; profiles/HISTORY.md 3.8d). */
+ * chained ResBlocks of model.py:258-262 are where 8-bit mantissas cost the finest image 7 dB; profiles/HISTORY.md 3.8d).
+ * Every refusal (NULL, n_elems < 8 or not a multiple of 8, equal or unknown types, a misaligned pointer) is TGSR_EINVAL. */
 int tgsr_lp_convert(int src_dtype, const void* src, int dst_dtype, void* dst, int64_t n_elems, void* stream);
 
 /* conv weight [Cout][Cin][3][3] (fp32, torch layout) -> MFMA fragment order
- * [kernel row 3][Cin/16][kernel column 3][Cout/32][lane 64][8], rounded to `dtype`
- * (tgsr_lp_packed_conv3x3_elems 2-byte elements).  Cout % 32 == 0, Cin % 16 == 0. */
+ * [kernel row dy 3][k16 Cin/16][kernel column dx 3][cb Cout/32][lane l 64][j 8], rounded to `dtype`
+ * (tgsr_lp_packed_conv3x3_elems 2-byte elements): element j of lane l = w[cb*32 + (l & 31)][k16*16 + 8 (l >> 5) + j][dy][dx].
+ * Cout % 32 == 0, Cin % 16 == 0 (else TGSR_EUNSUPPORTED).  Every element of the pack is written. */
 int64_t tgsr_lp_packed_conv3x3_elems(int Cout, int Cin);
 int tgsr_lp_pack_conv3x3_weight(int dtype, const float* w, void* wpack, int Cout, int Cin, void* stream);
 
@@ -1046,8 +1063,15 @@ int tgsr_lp_pack_conv3x3_weight(int dtype, const float* w, void* wpack, int Cout
  *   out = epilogue(scale * conv3x3(upsample ? nearest_x2(x) : x) + shift), epilogue = TGSR_EPI_AFFINE (+ residual when
  *   `residual` != NULL) or TGSR_EPI_AFFINE_GLU (Cout/2 output channels).
  * H, W are the OUTPUT size (x is H/2 x W/2 when upsample != 0; only with TGSR_EPI_AFFINE_GLU).  scale / shift fp32
- * [Cout] (NULL, NULL = identity).  (Cin, Cout) in {(64,128), (64,64), (32,64), (32,32)}: the generator's layers.
+ * [Cout] (NULL, NULL = identity).  (Cin, Cout) in {(64,128), (64,64), (32,64), (32,32)}: the generator's layers (GLU needs
+ * Cout >= 64; another pair, or `upsample` without GLU, is TGSR_EUNSUPPORTED; a residual with GLU is TGSR_EINVAL).
+ * x: channels [0, Cin) of an image of pitch x_cpitch >= Cin are read, the rest of it is not.  residual: channels [res_coff,
+ * res_coff + Cout) of an image of the output's size, which may be a third image.  out: channels [out_coff, out_coff + Cout or
+ * Cout/2) of every interior pixel are written; out must not be x (tiles read their neighbours' halo).
+ * tgsr_lp_conv3x3_plan: the output rows one workgroup of this entry takes at (B, H, W) - 8 where B (H/8) (W/32) >= 512 and
+ * H % 8 == 0, else 4 - or the TGSR_E code the entry gives for these sizes.  Host only; the launcher itself asks it.
  */
+int tgsr_lp_conv3x3_plan(int B, int H, int W);
 int tgsr_lp_conv3x3_fwd(int dtype, const void* x, int x_cpitch, int B, int Cin, int H, int W, const void* wpack,
                         int Cout, const float* scale, const float* shift, const void* residual, int res_cpitch,
                         int res_coff, void* out, int out_cpitch, int out_coff, int epilogue, int upsample,
@@ -1077,6 +1101,11 @@ int tgsr_lp_resblocks_fwd(int dtype, const void* x, int x_cpitch, int B, int H, 
  * rounded once to `dtype` - 16 products per low-res pixel instead of 36 (tgsr_lp_conv3x3_fwd(upsample = 1) is the
  * direct 9-tap form on the same layout).  H, W = size of the LOW-resolution input x; out [B][2H+2][2W+2][out_cpitch]
  * receives Cout/2 = 32 channels at out_coff.  Cout == 64, Cin in {32, 64}, W % 32 == 0, H % 4 == 0.
+ * The pack: [k16 Cin/16][column group 2][combo 8][cb 2][lane l 64][j 8]; combo = 4 a + 2 b + dys for row phase a, column
+ * phase b; it holds, for output channel cb*32 + (l & 31) and input channel k16*16 + 8 (l >> 5) + j, the fp32 sum - rows
+ * first, then columns - of the 3x3 taps that fall on low-res row offset a + dys - 1 and column offset (group 0: 2 b - 1;
+ * group 1: 0) of phase (a, b) (a = 0: rows {-1: w0, 0: w1 + w2}; a = 1: rows {0: w0 + w1, +1: w2}; the same for columns),
+ * rounded once.  Every element is written.  scale / shift NULL, NULL = identity.
  */
 int64_t tgsr_lp_packed_upconv_elems(int Cout, int Cin);
 int tgsr_lp_pack_upconv_weight(int dtype, const float* w, void* wpack, int Cout, int Cin, void* stream);
@@ -1092,13 +1121,16 @@ int tgsr_lp_upconv_glu_fwd(int dtype, const void* x, int x_cpitch, int B, int Ci
  *   head_wpack    tgsr_lp_pack_to3_weight of the head's [3][32][K][K] filter, head_k = K in {3, 5};
  *   head_partial  tgsr_lp_head_partial_elems(B, 2H, 2W, K) floats: a workgroup tile (8 x 64 outputs) holds only its own
  *                 pixels, so it writes the PARTIAL head sums of the (8 + 2P) x (64 + 2P) outputs they reach, layout
- *                 [B][2H/8][2W/64][3][8 + 2P][64 + 2P], P = K/2.
+ *                 [B][2H/8][2W/64][3][8 + 2P][64 + 2P], P = K/2.  EVERY element is written (zero contributions included):
+ *                 the combine reads all of it.  head_wpack NULL or head_k outside {3, 5} is TGSR_EINVAL.
+ * The feature image, where written, holds the bits tgsr_lp_upconv_glu_fwd gives.
  * tgsr_lp_head_combine adds the <= 4 partials of every pixel in a fixed order (tile rows, then columns: reproducible, no
  * float atomics) for up to 4 scales in ONE launch and finishes both generators' heads:
  *   low[s]  = sum of partial_low[s] (3x3 heads)  [tanh when low_tanh: GET_IMAGE_G of models16, util.py:894-905]
  *   high[s] = tanh(sum of partial_high[s] (5x5 heads)) + alpha * low[s]        (model.py:280, 288, 297)
  * H[s], W[s] = image size of scale s (multiples of 8 / 64); partial_low[s] == NULL: low[s] is an input (already
- * computed); partial_high[s] == NULL: high[s] is not produced.  low / high fp32 [B][3][H][W] dense.
+ * computed); partial_high[s] == NULL: high[s] is not produced (high[s] may then be NULL).  low / high fp32 [B][3][H][W]
+ * dense, 16-byte aligned.  H, W, partial_low, partial_high, low, high: HOST arrays of nscales entries; 1 <= nscales <= 4.
  */
 int64_t tgsr_lp_head_partial_elems(int B, int H, int W, int K);
 int tgsr_lp_upconv_glu_head_fwd(int dtype, const void* x, int x_cpitch, int B, int Cin, int H, int W, const void* wpack,
@@ -1124,7 +1156,8 @@ int tgsr_lp_head_combine_map(int nscales, int B, const int* H, const int* W, con
 /*
  * The two 3-channel stems on the fp32 LR image: conv3x3 3 -> 2C + BatchNorm(eval) affine + GLU, written as C channels
  * of an lp image (im2f util.py:741-744, convin model.py:228).  x [B][3][H][W] fp32 dense, w [2C][3][3][3] fp32 (torch
- * layout, NOT rounded: 27 MACs per output run on the VALU), scale / shift [2C].  C % 8 == 0.
+ * layout, NOT rounded: 27 MACs per output run on the VALU), scale / shift [2C], neither may be NULL.  C % 8 == 0,
+ * 8 <= C <= 64.  tgsr_lp_stem_fwd takes ANY H and W (a last column tile of W % 32 pixels writes those pixels only).
  */
 int tgsr_lp_stem_fwd(int dtype, const float* x, int B, int H, int W, const float* w, int C, const float* scale,
                      const float* shift, void* out, int out_cpitch, int out_coff, void* stream);
@@ -1138,7 +1171,8 @@ int tgsr_lp_stem_fwd(int dtype, const float* x, int B, int H, int W, const float
  * Same arithmetic as tgsr_lp_word_attention_fwd on the stored h (one shared device function: bit-identical results):
  * c_code -> channels [c_coff, c_coff + 32) of the same pixels of `out` (must not overlap [out_coff, out_coff + 32)),
  * attn [B][T][H_out * W_out] fp32 or NULL.  att_pack / att_nsets: what tgsr_text_tail_lp_fwd wrote for this batch; att_set:
- * which projection this stage attends through; use_mask 0: no mask; mask_mode as tgsr_word_attention_fwd.
+ * which projection this stage attends through; use_mask 0: no mask; mask_mode as tgsr_word_attention_fwd (0 or 1, else
+ * TGSR_EINVAL).  c_coff % 4 == 0, >= 0, c_coff + 32 <= out_cpitch.  1 <= T <= 32.  The stem form needs scale / shift.
  * The stand-alone attention launches - and their re-read of h - leave G_SR_NET_low's dependent chain.
  */
 int tgsr_lp_stem_att_fwd(int dtype, const float* x, int B, int H, int W, const float* w, int C, const float* scale,
@@ -1153,7 +1187,9 @@ int tgsr_lp_upconv_glu_att_fwd(int dtype, const void* x, int x_cpitch, int B, in
  * The image heads on an lp image (tgsr_conv_to3_fwd's reference sites: GET_IMAGE_G_noAct util.py:913-915; conv_output
  * + `one*. + a*SRb` model.py:224, 280/288/297).  w [3][32][K][K] fp32 -> wpack (K*512 2-byte elements: one 16-row MFMA
  * fragment per kernel row whose rows are the (output channel, kernel column) pairs); x = channels [0, 32) of an lp image; addend / out fp32 [B][3][H][W] dense.
- * Cin == 32, K in {3, 5}, W % 32 == 0, H % 8 == 0.
+ * Cin == 32, K in {3, 5}, W % 32 == 0, H % 8 == 0.  The pack [kernel row dy K][lane l 64][j 8]: element j of lane l =
+ * w[c][8 (l >> 4) + j][dy][dx] for row (l & 15) = c K + dx < 3 K, else 0; every element written.  act = TGSR_ACT_NONE
+ * (addend ignored) or TGSR_ACT_TANH_AXPY; addend NULL under TANH_AXPY: out = tanh(conv).  x_cpitch >= 32.
  */
 int tgsr_lp_pack_to3_weight(int dtype, const float* w, void* wpack, int Cin, int K, void* stream);
 int tgsr_lp_conv_to3_fwd(int dtype, const void* x, int x_cpitch, int B, int Cin, int H, int W, const void* wpack, int K,
@@ -1176,7 +1212,11 @@ int tgsr_lp_conv_to3_map_fwd(int dtype, const void* x, int x_cpitch, int B, int 
  * in tgsr_word_attention_fwd (0 = the reference's mask.repeat row order, GlobalAttention.py:109-116; 1 = per sample).
  * Writes c_code (rounded) to channels [c_coff, c_coff + idf) of c_img - normally the same image h lives in, which is
  * the reference's torch.cat((h_code, c_code), 1) - and the fp32 softmax to attn [B][T][H*W] (NULL = not needed).
- * idf == 32, T <= 32, W % 32 == 0.
+ * idf == 32, T <= 32, W % 32 == 0 (any H).  c_cpitch % 4 == 0, c_coff % 4 == 0, c_coff >= 0, c_img 8-byte aligned.  c_img == h
+ * with c_coff < 32 - c_code over the channels other tiles still read - is TGSR_EUNSUPPORTED, as in the fused forms; a
+ * mask_mode outside {0, 1} is TGSR_EINVAL.  src holds zeros at words t >= T.  A mask row with EVERY word masked is outside
+ * the contract (the softmax of an empty set: NaN, as in the reference).  mask [B][T] bytes, any alignment, any B (mode 0
+ * reads row (b H W + q) % B for pixel q of sample b).
  */
 int tgsr_lp_word_attention_fwd(int dtype, const void* h, int h_cpitch, const float* src, const uint8_t* mask,
                                int mask_mode, int B, int idf, int T, int H, int W, void* c_img, int c_cpitch, int c_coff,

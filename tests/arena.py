@@ -17,6 +17,17 @@ The buffer is int32 words; PATTERN is a quiet NaN no arithmetic produces (the pa
 strided operand and every input hold PATTERN / their values before the call and must hold the same bits after it; the interior of
 an output must hold no PATTERN word and only finite values; a workspace may be left partly unwritten but not overrun.  A uint8
 input (a mask) is padded to whole words, the padding bytes holding PATTERN's.
+
+Operands of 2-byte elements (the reduced-precision path) are guarded element by element: PATTERN16 is a NaN in bf16 and in f16 that
+no conversion produces (theirs are 0x7FC0 / 0x7E00).
+
+    img = a.place_lp(torch.bfloat16, B, H, W, cpitch, reads=[(0, x)], writes=[(32, 32)])   # an lp image [B][H+2][W+2][cpitch]
+    pk = a.place_output16(n, torch.bfloat16)                                               # a dense pack of n elements
+    m = a.place_output_u8((B, T))                                                          # a byte output, padded to whole words
+
+An lp image holds zeros on its one-pixel border, the values of `reads` (NCHW tensors, exactly representable) in their channel
+ranges and PATTERN16 in every other channel of the interior; the call may write the interior pixels x the channel ranges of
+`writes` and nothing else, and must leave no PATTERN16 and only finite values there.
 """
 import ctypes
 
@@ -24,6 +35,7 @@ import numpy as np
 import torch
 
 PATTERN = 0x7FC5A5A5
+PATTERN16 = 0x7FC5        # per 2-byte element
 GUARD = 16384             # words on each side of every operand: more than two image rows plus a tile at every shape of the suite
 
 _INPUT, _OUTPUT, _WS, _INOUT, _ABSENT = "input", "output", "ws", "inout", "absent"
@@ -64,6 +76,103 @@ class Region:
         if self.dtype == torch.uint8:          # a byte operand: whole words, the padding bytes behind the last element dropped
             return self.words().view(torch.uint8)[:int(np.prod(self.shape))].reshape(self.shape).clone()
         return self.words().view(self.dtype).reshape(self.shape).clone()
+
+    # what _commit needs of a region: its initial words and which of their bits the call may change
+    def initial(self, k, n):
+        """(words or None = PATTERN, writable bit mask) of run `k` (`n` words) of slices()."""
+        words = self.host[k * n:(k + 1) * n] if self.kind in (_INPUT, _INOUT) else None
+        return words, (-1 if self.kind in (_OUTPUT, _WS, _INOUT) else 0)
+
+    def refill(self, bits):
+        """A workspace-like operand before the second of two calls: every writable word holds `bits` (a finite float)."""
+        if self.kind == _WS:
+            self.arena.buffer()[self.offset:self.offset + self.per] = bits
+
+    def complaints(self, i):
+        if self.kind not in (_OUTPUT, _INOUT):
+            return []
+        w = self.words()
+        unwritten = int((w == PATTERN).sum())
+        if unwritten:
+            return ["%s #%d %s: %d of %d words never written" % (self.kind, i, self.shape, unwritten, w.numel())]
+        if self.dtype.is_floating_point and not bool(torch.isfinite(w.view(self.dtype)).all()):
+            return ["%s #%d %s holds non-finite values" % (self.kind, i, self.shape)]
+        return []
+
+
+def _pattern16(n):
+    return torch.full((n,), PATTERN16, dtype=torch.int16)
+
+
+class Region16(Region):
+    """A dense run of 2-byte elements (a weight pack, att_pack) or of bytes (a mask), padded to whole words; `image` holds its initial
+    elements, `mask` which of them the call may write (all ones / zero per element), `must` which of those it has to write."""
+
+    def __init__(self, arena, kind, offset, shape, dtype, image, mask, must, finite):
+        self.image, self.mask, self.must, self.finite = image, mask, must, finite
+        super().__init__(arena, kind, offset, shape, 1, image.view(torch.int32).numel(), None, dtype, None)
+        self.bstride = self.per
+
+    def initial(self, k, n):
+        return self.image.view(torch.int32), self.mask.view(torch.int32)
+
+    def refill(self, bits):
+        """Outputs of 2-byte elements count as workspace-like: an element the call never writes then differs between the two calls."""
+        if self.kind == _ABSENT or self.image.dtype != torch.int16:
+            return
+        fill = torch.tensor([1.5]).to(self.dtype if self.dtype.is_floating_point else torch.float16).view(torch.int16)
+        img = torch.where(self.must, fill.expand_as(self.image), self.image)
+        self.arena.buffer()[self.offset:self.offset + self.per] = img.view(torch.int32).to(self.arena.device)
+
+    def elements(self):
+        """The operand's elements as they are now (int16 or uint8, flat, padding included), on the host."""
+        return self.words().view(self.image.dtype)
+
+    def read(self):
+        e = self.elements()[:int(np.prod(self.shape))].reshape(self.shape).clone()
+        return e.view(self.dtype) if self.image.dtype == torch.int16 and self.dtype.itemsize == 2 else e
+
+    def complaints(self, i):
+        if self.kind == _ABSENT:
+            return []
+        e = self.elements()
+        unwritten = int(((e == self.image) & self.must).sum())
+        if unwritten:
+            return ["%s #%d %s: %d of %d elements never written" % (self.kind, i, self.shape, unwritten, int(self.must.sum()))]
+        if self.finite and not bool(torch.isfinite(e.view(self.dtype)[self.must]).all()):
+            return ["%s #%d %s holds non-finite values" % (self.kind, i, self.shape)]
+        return []
+
+
+class LpImage(Region16):
+    """A zero-bordered channels-last image [B][H+2][W+2][cpitch] of 2-byte elements."""
+
+    def __init__(self, arena, offset, dtype, B, H, W, cpitch, reads, writes, written):
+        img = torch.zeros(B, H + 2, W + 2, cpitch, dtype=torch.int16)
+        inner = img[:, 1:-1, 1:-1]
+        inner[:] = PATTERN16
+        mask, must = torch.zeros_like(img), torch.zeros(img.shape, dtype=torch.bool)
+        for coff, t in reads:
+            t = t.detach().cpu().float()
+            assert t.shape[0] == B and t.shape[2:] == (H, W) and 0 <= coff and coff + t.shape[1] <= cpitch
+            assert torch.equal(t.to(dtype).float(), t), "an input of an lp image is exactly representable in its type"
+            inner[..., coff:coff + t.shape[1]] = t.permute(0, 2, 3, 1).to(dtype).view(torch.int16)
+        for coff, c in (writes if written else ()):
+            assert 0 <= coff and coff + c <= cpitch
+            mask[:, 1:-1, 1:-1, coff:coff + c] = -1
+            must[:, 1:-1, 1:-1, coff:coff + c] = True
+        for coff, t in reads:                                     # a channel read AND written starts from its input: nothing to find there
+            must[:, 1:-1, 1:-1, coff:coff + t.shape[1]] = False
+        self.B, self.H, self.W, self.cpitch = B, H, W, cpitch
+        kind = _INOUT if (reads and writes) else _OUTPUT if writes else _INPUT
+        if writes and not written:
+            kind = _ABSENT
+        super().__init__(arena, kind, offset, (B, H + 2, W + 2, cpitch), dtype, img.reshape(-1), mask.reshape(-1), must.reshape(-1), True)
+
+    def nchw(self, coff, c):
+        """Channels [coff, coff + c) of the interior as fp32 [B][c][H][W]."""
+        e = self.elements().reshape(self.shape)[:, 1:-1, 1:-1, coff:coff + c]
+        return e.contiguous().view(self.dtype).float().permute(0, 3, 1, 2).contiguous()
 
 
 class Arena:
@@ -124,6 +233,50 @@ class Arena:
         shape, nb, per = self._split(shape, dtype, bstride is not None)
         return self._place(_OUTPUT if written else _ABSENT, shape, nb, per, bstride, align, skew, dtype, None)
 
+    def _place16(self, region, align, skew):
+        assert self._buf is None, "place every operand before taking the first pointer"
+        a = align // 4
+        region.offset = (self._cursor + a - 1) // a * a + skew
+        self.regions.append(region)
+        self._cursor = region.offset + region.span + self.guard
+        return region
+
+    def place_lp(self, dtype, B, H, W, cpitch, reads=(), writes=(), align=16, skew=0, written=True):
+        """An lp image: `reads` = [(coff, values [B][C][H][W])], `writes` = [(coff, C)] - an input, an output or, with both, an in/out
+        operand.  written=False: the call refuses - nothing of it may change."""
+        assert (B * (H + 2) * (W + 2) * cpitch) % 2 == 0
+        return self._place16(LpImage(self, 0, dtype, B, H, W, cpitch, list(reads), list(writes), written), align, skew)
+
+    def _dense16(self, kind, shape, dtype, values, written, finite, align, skew):
+        shape = tuple(int(s) for s in shape)
+        n = int(np.prod(shape))
+        img = _pattern16(n + (n & 1))
+        if values is not None:
+            img[:n] = values.reshape(-1)
+        mask, must = torch.zeros_like(img), torch.zeros(img.shape, dtype=torch.bool)
+        if kind == _OUTPUT:
+            mask[:n], must[:n] = -1, True
+        return self._place16(Region16(self, kind if written else _ABSENT, 0, shape, dtype, img, mask, must, finite), align, skew)
+
+    def place_input16(self, t, align=16, skew=0):
+        """A dense operand of 2-byte elements (bf16 / f16 / int16 tensor) the call only reads."""
+        t = t.detach().cpu().contiguous()
+        assert t.dtype.itemsize == 2
+        return self._dense16(_INPUT, t.shape, t.dtype, t.view(torch.int16), True, False, align, skew)
+
+    def place_output16(self, shape, dtype, align=16, skew=0, written=True, finite=True):
+        """A dense output of 2-byte elements, PATTERN16-prefilled; finite=False: raw bits (att_pack's mask words)."""
+        return self._dense16(_OUTPUT, shape, dtype, None, written, finite, align, skew)
+
+    def place_output_u8(self, shape, align=16, skew=0, written=True):
+        """A byte output (the text tail's mask): PATTERN's bytes before the call - none of them 0 or 1 - and behind its last element."""
+        shape = tuple(int(s) for s in shape)
+        n = int(np.prod(shape))
+        img = torch.full(((n + 3) // 4,), PATTERN, dtype=torch.int32).view(torch.uint8).clone()
+        mask, must = torch.zeros_like(img), torch.zeros(img.shape, dtype=torch.bool)
+        mask[:n], must[:n] = 255, True
+        return self._place16(Region16(self, _OUTPUT if written else _ABSENT, 0, shape, torch.uint8, img, mask, must, False), align, skew)
+
     def place_ws(self, n, align=16, skew=0):
         """A workspace of exactly `n` floats, PATTERN-prefilled (a NaN: whatever is read before it is written poisons the result)."""
         return self._place(_WS, (int(n),), 1, int(n), None, align, skew, torch.float32, None)
@@ -132,13 +285,13 @@ class Arena:
     def _commit(self):
         total = self._cursor
         host = torch.full((total,), PATTERN, dtype=torch.int32)
-        writable = torch.zeros(total, dtype=torch.bool)
+        writable = torch.zeros(total, dtype=torch.int32)           # per word, the bits the call may change
         for r in self.regions:
             for k, (lo, hi) in enumerate(r.slices()):
-                if r.kind in (_INPUT, _INOUT):
-                    host[lo:hi] = r.host[k * (hi - lo):(k + 1) * (hi - lo)]
-                if r.kind in (_OUTPUT, _WS, _INOUT):
-                    writable[lo:hi] = True
+                words, mask = r.initial(k, hi - lo)
+                if words is not None:
+                    host[lo:hi] = words
+                writable[lo:hi] = mask
         self._snap = host.to(self.device)
         self._writable = writable.to(self.device)
         self._buf = self._snap.clone()
@@ -158,8 +311,7 @@ class Arena:
         if ws_fill is not None:
             bits = int(np.float32(ws_fill).view(np.int32))
             for r in self.regions:
-                if r.kind == _WS:
-                    self._buf[r.offset:r.offset + r.per] = bits
+                r.refill(bits)
 
     # ---- the check ----
     def violations(self):
@@ -167,20 +319,13 @@ class Arena:
         if self.device.type == "cuda":
             torch.cuda.synchronize(self.device)
         buf, out = self.buffer(), []
-        touched = (buf != self._snap) & ~self._writable
+        touched = ((buf ^ self._snap) & ~self._writable) != 0
         if bool(touched.any()):
             where = touched.nonzero().view(-1).cpu()
             out.append("%d words outside every output were written, first at word %d (%s)"
                        % (len(where), int(where[0]), self.describe(int(where[0]))))
         for i, r in enumerate(self.regions):
-            if r.kind not in (_OUTPUT, _INOUT):
-                continue
-            w = r.words()
-            unwritten = int((w == PATTERN).sum())
-            if unwritten:
-                out.append("%s #%d %s: %d of %d words never written" % (r.kind, i, r.shape, unwritten, w.numel()))
-            elif r.dtype.is_floating_point and not bool(torch.isfinite(w.view(r.dtype)).all()):
-                out.append("%s #%d %s holds non-finite values" % (r.kind, i, r.shape))
+            out.extend(r.complaints(i))
         return out
 
     def check(self):

@@ -201,6 +201,7 @@ SIGNATURES = {
     "tgsr_lp_convert": (_i, [_i, _vp, _i, _vp, _i64, _vp]),
     "tgsr_lp_packed_conv3x3_elems": (_i64, [_i, _i]),
     "tgsr_lp_pack_conv3x3_weight": (_i, [_i, _vp, _vp, _i, _i, _vp]),
+    "tgsr_lp_conv3x3_plan": (_i, [_i, _i, _i]),
     "tgsr_lp_conv3x3_fwd": (_i, [_i, _vp, _i, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _i, _i, _vp, _i, _i, _i, _i, _vp]),
     "tgsr_lp_resblocks_flag_elems": (_i64, [_i, _i, _i]),
     "tgsr_lp_resblocks_fwd": (_i, [_i, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp, _i, _vp, _vp]),

@@ -157,6 +157,7 @@ static inline int lp_att_fuse(const void* att_pack, int att_nsets, int att_set, 
                        float* attn, LpAttFuse* f) {
   if (!att_pack || att_nsets < 1 || att_set < 0 || att_set >= att_nsets || (reinterpret_cast<uintptr_t>(att_pack) & 15))
     return TGSR_EINVAL;
+  if (mask_mode != 0 && mask_mode != 1) return TGSR_EINVAL;
   const char* p = static_cast<const char*>(att_pack);
   f->frag = p + (size_t)att_set * B * 4096;
   f->mbits = use_mask ? reinterpret_cast<const uint32_t*>(p + (size_t)att_nsets * B * 4096) : nullptr;

@@ -823,13 +823,20 @@ __global__ __launch_bounds__(256) void lp_convert_kernel(const u32x4* __restrict
   }
 }
 
+// rows per workgroup of lp_conv3x3_kernel (tgsr_lp_conv3x3_plan): 8 when that still gives >= 2 workgroups per CU, else 4
+static int lp_conv_rows(int B, int H, int W) {
+  if (B < 1 || H < 1 || W < 1) return TGSR_EINVAL;
+  if (W % 32 != 0 || H % 4 != 0) return TGSR_EUNSUPPORTED;
+  return ((int64_t)B * (H / 8) * (W / 32) >= 512 && H % 8 == 0) ? 8 : 4;
+}
+
 template <class T, int CIN, int COUT, int EPI, bool UP>
 static int launch_lp_conv_tr(const LpConvArgs& a0, hipStream_t s) {
   LpConvArgs a = a0;
-  // rows per workgroup: 8 when that still gives >= 2 workgroups per CU, else 4
-  const bool big = (int64_t)a.B * (a.H / 8) * (a.W / 32) >= 512 && a.H % 8 == 0;
+  const int rows = lp_conv_rows(a.B, a.H, a.W);
+  if (rows < 0) return rows;
   a.tiles_x = a.W / 32;
-  if (big) {
+  if (rows == 8) {
     a.tiles_y = a.H / 8;
     hipLaunchKernelGGL((lp_conv3x3_kernel<T, CIN, COUT, EPI, UP, 8>), dim3(a.B * a.tiles_x * a.tiles_y), dim3(256), 0, s, a);
   } else {
@@ -883,6 +890,8 @@ extern "C" int tgsr_lp_pack_conv3x3_weight(int dtype, const float* w, void* wpac
   return note_launch(hipGetLastError(), "lp_pack_conv3x3_kernel");
 }
 
+extern "C" int tgsr_lp_conv3x3_plan(int B, int H, int W) { return lp_conv_rows(B, H, W); }
+
 extern "C" int tgsr_lp_conv3x3_fwd(int dtype, const void* x, int x_cpitch, int B, int Cin, int H, int W, const void* wpack,
                                    int Cout, const float* scale, const float* shift, const void* residual, int res_cpitch,
                                    int res_coff, void* out, int out_cpitch, int out_coff, int epilogue, int upsample,
@@ -894,13 +903,15 @@ extern "C" int tgsr_lp_conv3x3_fwd(int dtype, const void* x, int x_cpitch, int B
   if (dtype != TGSR_DT_BF16 && dtype != TGSR_DT_F16) return TGSR_EINVAL;
   const int co = epilogue == TGSR_EPI_AFFINE_GLU ? Cout / 2 : Cout;
   if (W % 32 != 0 || H % 4 != 0 || (upsample && ((H | W) & 1))) return TGSR_EUNSUPPORTED;
-  if (x_cpitch < Cin || x_cpitch % 8 != 0 || out_cpitch % 8 != 0 || out_coff % 8 != 0 || out_coff + co > out_cpitch)
+  if (x_cpitch < Cin || x_cpitch % 8 != 0 || out_cpitch % 8 != 0 || out_coff < 0 || out_coff % 8 != 0 || out_coff + co > out_cpitch)
     return TGSR_EUNSUPPORTED;                      // rows of pixels move as 16-byte pieces: offsets / pitches % 8 channels
-  if (residual && (res_cpitch % 8 != 0 || res_coff % 8 != 0 || res_coff + co > res_cpitch)) return TGSR_EUNSUPPORTED;
+  if (residual && (res_cpitch % 8 != 0 || res_coff < 0 || res_coff % 8 != 0 || res_coff + co > res_cpitch)) return TGSR_EUNSUPPORTED;
   if ((reinterpret_cast<uintptr_t>(x) & 15) || (reinterpret_cast<uintptr_t>(wpack) & 15) ||
       (reinterpret_cast<uintptr_t>(out) & 15) || (reinterpret_cast<uintptr_t>(residual) & 15))
     return TGSR_EUNSUPPORTED;
-  if ((int64_t)(H + 2) * (W + 2) * (x_cpitch > out_cpitch ? x_cpitch : out_cpitch) * 2 >= (1ll << 31)) return TGSR_EUNSUPPORTED;
+  int maxcp = x_cpitch > out_cpitch ? x_cpitch : out_cpitch;
+  if (residual && res_cpitch > maxcp) maxcp = res_cpitch;
+  if ((int64_t)(H + 2) * (W + 2) * maxcp * 2 >= (1ll << 31)) return TGSR_EUNSUPPORTED;
   LpConvArgs a;
   a.x = static_cast<const char*>(x); a.xcp = x_cpitch; a.B = B; a.H = H; a.W = W;
   a.Hi = upsample ? H / 2 : H; a.Wi = upsample ? W / 2 : W;
@@ -1001,7 +1012,7 @@ static int lp_upconv_launch(int dtype, const void* x, int x_cpitch, int B, int C
   if (x_cpitch < Cin || x_cpitch % 8 != 0 || (reinterpret_cast<uintptr_t>(x) & 15) || (reinterpret_cast<uintptr_t>(wpack) & 15) ||
       (reinterpret_cast<uintptr_t>(head_wpack) & 15))
     return TGSR_EUNSUPPORTED;
-  if (out && (out_cpitch % 8 != 0 || out_coff % 8 != 0 || out_coff + 32 > out_cpitch || (reinterpret_cast<uintptr_t>(out) & 15) ||
+  if (out && (out_cpitch % 8 != 0 || out_coff < 0 || out_coff % 8 != 0 || out_coff + 32 > out_cpitch || (reinterpret_cast<uintptr_t>(out) & 15) ||
               (int64_t)(2 * H + 2) * (2 * W + 2) * out_cpitch * 2 >= (1ll << 31)))
     return TGSR_EUNSUPPORTED;
   LpConvArgs a;
@@ -1015,7 +1026,7 @@ static int lp_upconv_launch(int dtype, const void* x, int x_cpitch, int B, int C
   a.att = LpAttFuse{nullptr, nullptr, nullptr, 0, 0, 0};
   if (att) {
     // the attended tensor is G_SR_NET_low's 32-channel h_code: a 64 -> 64 (GLU: 32) upBlock whose image is written
-    if (!out || Cin != 64 || (hk != 0 && hk != 3) || att->T < 1 || att->T > 32 || att->coff % 4 != 0 ||
+    if (!out || Cin != 64 || (hk != 0 && hk != 3) || att->T < 1 || att->T > 32 || att->coff < 0 || att->coff % 4 != 0 ||
         att->coff + 32 > out_cpitch || (att->coff < out_coff + 32 && out_coff < att->coff + 32))
       return TGSR_EUNSUPPORTED;
     a.att = *att;

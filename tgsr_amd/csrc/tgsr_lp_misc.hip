@@ -325,7 +325,7 @@ using namespace tgsr;
 static int lp_stem_launch(int dtype, const float* x, int B, int H, int W, const float* w, int C, const float* scale,
                           const float* shift, void* out, int out_cpitch, int out_coff, const LpAttFuse* att, void* stream) {
   if (!x || !w || !scale || !shift || !out || B < 1 || H < 1 || W < 1 || C < 8) return TGSR_EINVAL;
-  if (C % 8 != 0 || out_cpitch % 8 != 0 || out_coff % 8 != 0 || out_coff + C > out_cpitch ||
+  if (C % 8 != 0 || out_cpitch % 8 != 0 || out_coff < 0 || out_coff % 8 != 0 || out_coff + C > out_cpitch ||
       (reinterpret_cast<uintptr_t>(out) & 15))
     return TGSR_EUNSUPPORTED;
   LpStemArgs a;
@@ -334,7 +334,7 @@ static int lp_stem_launch(int dtype, const float* x, int B, int H, int W, const 
   if (C > 64) return TGSR_EUNSUPPORTED;                      // 8 channel groups of 8 per 256-thread workgroup
   const dim3 grid((unsigned)((int64_t)B * H * ((W + 31) / 32)));
   if (att) {
-    if (C != 32 || W % 32 != 0 || att->T < 1 || att->T > 32 || att->coff % 4 != 0 || att->coff + 32 > out_cpitch ||
+    if (C != 32 || W % 32 != 0 || att->T < 1 || att->T > 32 || att->coff < 0 || att->coff % 4 != 0 || att->coff + 32 > out_cpitch ||
         (att->coff < out_coff + C && out_coff < att->coff + 32))
       return TGSR_EUNSUPPORTED;
     a.att = *att;
@@ -430,9 +430,11 @@ extern "C" int tgsr_lp_word_attention_fwd(int dtype, const void* h, int h_cpitch
                                           int mask_mode, int B, int idf, int T, int H, int W, void* c_img, int c_cpitch,
                                           int c_coff, float* attn, void* stream) {
   if (!h || !src || !c_img || B < 1 || T < 1 || H < 1 || W < 1) return TGSR_EINVAL;
-  if (idf != 32 || T > 32 || W % 32 != 0 || h_cpitch < 32 || h_cpitch % 8 != 0 || c_cpitch % 4 != 0 || c_coff % 4 != 0 ||
+  if (mask_mode != 0 && mask_mode != 1) return TGSR_EINVAL;
+  if (idf != 32 || T > 32 || W % 32 != 0 || h_cpitch < 32 || h_cpitch % 8 != 0 || c_cpitch % 4 != 0 || c_coff < 0 || c_coff % 4 != 0 ||
       c_coff + 32 > c_cpitch || (reinterpret_cast<uintptr_t>(h) & 15) || (reinterpret_cast<uintptr_t>(c_img) & 7))
     return TGSR_EUNSUPPORTED;
+  if (c_img == h && c_coff < 32) return TGSR_EUNSUPPORTED;      // c_code over h's own channels, which other tiles still read
   LpAttnArgs a;
   a.h = static_cast<const char*>(h); a.hcp = h_cpitch; a.src = src; a.mask = mask; a.mask_mode = mask_mode;
   a.B = B; a.T = T; a.H = H; a.W = W; a.c = static_cast<char*>(c_img); a.ccp = c_cpitch; a.cco = c_coff; a.attn = attn;
