@@ -1252,6 +1252,36 @@ int tgsr_weight_mse_fwd(const float* fake, const float* label, const float* att,
 int tgsr_weight_mse_bwd(const float* grad, const float* fake, const float* label, const float* wmax, const uint8_t* widx, int B, int C,
                         int T, int H, int W, int h, int w, float* d_fake, float* d_label, float* d_att, void* stream);
 
+/*
+ * The cycle-consistency objective (the reference's miscc/losses.py, CycleMSE :785-790; tgsr_cycle_mse.hip): every SR image of a
+ * pyramid resized back to the LR size with torch's bicubic rule and held to the LR input by a mean squared error.
+ *   sr   HOST array of n DEVICE pointers, sr[i] fp32 [B][C][H[i]][W[i]] dense (any 4-byte aligned base); H, W HOST arrays of n ints;
+ *   lr   fp32 [B][C][h][w] dense.  1 <= n <= 8; H[i] / h and W[i] / w are arbitrary and independent (down, identity, up).
+ *   Per axis, in float32 as torch computes it (align_corners=False, no antialiasing, A = -0.75):
+ *     scale = (float)H / h,  src = scale (y + 0.5f) - 0.5f (not clamped at 0),  t = src - floor(src),
+ *     taps floor(src) - 1 .. floor(src) + 2 clamped to [0, H - 1].
+ *
+ * tgsr_cycle_mse_fwd - one kernel launch for all n scales + one finish launch:
+ *   diff fp32 [n][B][C][h][w] = resized_i - lr (what the backward reads),
+ *   terms fp32 [n]:  terms[i] = sum(diff_i^2) / (B C h w)   (the partials added in index order in fp64, one fp32 division),
+ *   loss fp32 [1]:   loss[0] = terms[0] + terms[1] + ... in fp32, in that order (the reference's `+=`).
+ *   ws: tgsr_cycle_mse_ws_elems(...) floats (0 = a shape the entries refuse).
+ * tgsr_cycle_mse_bwd - one kernel launch for all scales, gather form; grad fp32 [1] ON THE DEVICE (the gradient reaching loss[0]):
+ *   d_sr HOST array of n DEVICE pointers (the array or any entry may be NULL: that gradient is not written),
+ *     d_sr[i][b][c][Y][X] = grad 2 / (B C h w) sum_{y, x} WY(y, Y) WX(x, X) diff_i[b][c][y][x],   WY(y, Y) = the sum of the weights of
+ *     output y whose clamped tap is Y - written completely, zeros where no tap lands (no memset);
+ *   d_lr NULL, or fp32 [B][C][h][w] = -grad 2 / (B C h w) sum_i diff_i.   One of the outputs at least.
+ *   16-byte stores into d_sr[i] where it is 16-byte aligned and W[i] % 4 == 0, element by element otherwise.
+ * No atomics: the same bits on every run.  Every entry returns TGSR_EINVAL without launching (and without touching an output) for a
+ * NULL required pointer (the arrays and every sr[i] included), a size < 1 or > 65536, n outside [1, 8], or a backward call that asks
+ * for no output.
+ */
+int64_t tgsr_cycle_mse_ws_elems(const int* H, const int* W, int n, int B, int C, int h, int w);
+int tgsr_cycle_mse_fwd(const float* const* sr, const int* H, const int* W, int n, const float* lr, int B, int C, int h, int w,
+                       float* ws, float* diff, float* loss, float* terms, void* stream);
+int tgsr_cycle_mse_bwd(const float* grad, const float* diff, const int* H, const int* W, int n, int B, int C, int h, int w,
+                       float* const* d_sr, float* d_lr, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

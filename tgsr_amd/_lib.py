@@ -181,6 +181,9 @@ SIGNATURES = {
     "tgsr_weight_mse_ws_elems": (_i64, [_i, _i, _i, _i, _i, _i, _i]),
     "tgsr_weight_mse_fwd": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "tgsr_weight_mse_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "tgsr_cycle_mse_ws_elems": (_i64, [_vp, _vp, _i, _i, _i, _i, _i]),
+    "tgsr_cycle_mse_fwd": (_i, [_vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    "tgsr_cycle_mse_bwd": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     "tgsr_tile_gather": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
     "tgsr_tile_stitch": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _i, _i, _i, _vp]),
     "tgsr_conv3x3_wgrad_plan": (_i, [_i, _vp, _vp, _i64, _i, _i, _i, _i, _i, _i, _vp]),

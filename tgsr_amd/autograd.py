@@ -619,6 +619,30 @@ class WeightMSE(torch.autograd.Function):
         return (d_fake if need[0] else None), (d_label if need[1] else None), (d_att if need[2] else None), None
 
 
+class CycleMSE(torch.autograd.Function):
+    """CycleMSE (losses.py:785-790) over a whole pyramid: apply(lr, *sr) -> (loss, terms) = tgsr::cycle_mse, backward =
+    tgsr::cycle_mse_bwd - one launch each for all scales, a gather-form backward without atomics (the same bits on every run, unlike
+    torch's upsample_bicubic2d_backward).  Differentiable w.r.t. every SR image and the LR image; `terms` (the per-scale means) is
+    returned without gradient.  The incoming gradient stays on the device: nothing here synchronises, so the term can be captured."""
+
+    @staticmethod
+    def forward(ctx, lr, *sr):
+        loss, terms, diff = C.cycle_mse(list(sr), lr)
+        ctx.save_for_backward(diff)
+        ctx.sizes = [int(v) for t in sr for v in t.shape[2:]]
+        ctx.mark_non_differentiable(terms)
+        return loss, terms
+
+    @staticmethod
+    def backward(ctx, grad_loss, _grad_terms):
+        diff, = ctx.saved_tensors
+        need = list(ctx.needs_input_grad)
+        if not any(need):
+            return (None,) * len(need)
+        out = C.cycle_mse_bwd(grad_loss.contiguous(), diff, ctx.sizes, need[1:], need[0])
+        return (out[-1] if need[0] else None,) + tuple(g if k else None for g, k in zip(out[:-1], need[1:]))
+
+
 class BiLSTM(torch.autograd.Function):
     """RNN_ENCODER's bidirectional LSTM (util.py:233-260) in training mode: forward = tgsr::bilstm_train on the embedded
     (and dropped-out) inputs, backward = tgsr::bilstm_bwd (BPTT, one workgroup per sample and direction) plus four GEMMs

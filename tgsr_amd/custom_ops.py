@@ -632,6 +632,27 @@ weight_mse_bwd = _define("weight_mse_bwd(Tensor grad, Tensor fake, Tensor label,
                              torch.empty_like(fake, memory_format=torch.contiguous_format) if nl else fake.new_empty(0),
                              fake.new_empty((wmax.shape[0], T, wmax.shape[1], wmax.shape[2]) if na else (0,))))
 
+# the cycle-consistency objective (miscc.losses.CycleMSE): all scales of a pyramid in one forward and one backward launch.  cycle_mse
+# returns (loss [], terms [n], diff [n, B, C, h, w]); cycle_mse_bwd takes the sizes (H_0, W_0, H_1, W_1, ...) and one flag per scale and
+# returns n + 1 tensors - d_sr[0..n-1], d_lr - absent gradients as [0]; autograd.CycleMSE is the differentiable form
+cycle_mse = _define("cycle_mse(Tensor[] sr, Tensor lr) -> (Tensor, Tensor, Tensor)", lambda sr, lr: ops.cycle_mse(sr, lr),
+                    lambda sr, lr: (lr.new_empty(()), lr.new_empty(len(sr)), lr.new_empty((len(sr),) + tuple(lr.shape))))
+
+
+def _cycle_mse_bwd(grad, diff, sizes, need_sr, need_lr):
+    d_sr, d_lr = ops.cycle_mse_bwd(grad, diff, sizes, need_sr, need_lr)
+    return [t if t is not None else diff.new_empty(0) for t in d_sr + [d_lr]]
+
+
+def _cycle_mse_bwd_fake(grad, diff, sizes, need_sr, need_lr):
+    _n, B, C, h, w = diff.shape
+    out = [diff.new_empty((B, C, sizes[2 * i], sizes[2 * i + 1]) if need else (0,)) for i, need in enumerate(need_sr)]
+    return out + [diff.new_empty((B, C, h, w) if need_lr else (0,))]
+
+
+cycle_mse_bwd = _define("cycle_mse_bwd(Tensor grad, Tensor diff, int[] sizes, bool[] need_sr, bool need_lr) -> Tensor[]",
+                        _cycle_mse_bwd, _cycle_mse_bwd_fake)
+
 
 # whole images by overlapping tiles (SRPipeline.upscale): `table` is the host int32 [Tb, 6] window table, `table_dev` its device copy
 def _tile_gather(img, img2, table, table_dev, th, tw):

@@ -9,6 +9,8 @@ sent_loss through torch autograd over its [B, B] matrix.
 The objectives that read the generator's word-attention maps - `weight_MSE` (:792-804), `words_reweight_loss` (:137-232),
 `generator_re_weight_loss` (:318-350) - run on the kernels of tgsr_attn_losses.hip; their torch compositions, for
 CPU tensors and for what the kernels do not take, live here and nowhere else.
+The cycle-consistency term `CycleMSE` (:785-790) runs on the kernels of tgsr_cycle_mse.hip, one forward and one
+backward launch for a whole pyramid; its torch composition lives here as well.
 """
 import contextlib
 
@@ -189,6 +191,43 @@ def words_similarity(img_features, words_emb, cap_lens, batch_size):
 def MSE(fake, label):
     """losses.py:779-784: sum over the image scales of the mean squared error."""
     return sum(F.mse_loss(f, t) for f, t in zip(fake, label))
+
+
+def _cycle_mse_torch(fakeSR, Real_LR):
+    """CycleMSE as the reference writes it (losses.py:785-790)."""
+    mseloss = 0
+    for i in range(len(fakeSR)):
+        fakeLR = F.interpolate(fakeSR[i], size=[Real_LR.shape[2], Real_LR.shape[3]], mode="bicubic")
+        mseloss = mseloss + F.mse_loss(fakeLR, Real_LR)
+    return mseloss
+
+
+def _cycle_mse_fusable(fakeSR, Real_LR):
+    """Dense float32 HIP tensors of shapes the kernels take: the shape rule is ops.check_cycle_mse's, asked, not restated."""
+    ts = list(fakeSR) + [Real_LR]
+    if not all(torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() for t in ts):
+        return False
+    try:
+        ops.check_cycle_mse([t.shape for t in fakeSR], Real_LR.shape)
+    except ops.TgsrError:
+        return False
+    return True
+
+
+def CycleMSE(fakeSR, Real_LR, fused=None):
+    """losses.py:785-790: sum over the SR images of a pyramid of mean((F.interpolate(fakeSR[i], size=[h, w], mode="bicubic") -
+    Real_LR)^2) - every SR image, resized back to the LR size (align_corners=False, no antialiasing), must give the LR input.
+    Differentiable w.r.t. every fakeSR[i] and Real_LR.
+    `fused` (not a reference argument): None = one forward and one backward launch for the whole pyramid (autograd.CycleMSE,
+    tgsr_cycle_mse.hip) where the tensors are dense float32 HIP tensors (any 4-byte aligned base: offset views are taken), at most
+    8 scales, with equal B and C; the torch composition of the reference's expression elsewhere (CPU tensors, other dtypes, strided
+    views, more scales); False = the composition; True = the kernels or an error.  The kernels' backward gathers - no atomics, the
+    same bits on every run, which torch's upsample_bicubic2d_backward does not promise on the device - and nothing in either
+    direction waits for the device, so the term can sit inside a captured update."""
+    if fused or (fused is None and _cycle_mse_fusable(fakeSR, Real_LR)):
+        from ..autograd import CycleMSE as _CycleMSE
+        return _CycleMSE.apply(Real_LR, *fakeSR)[0]
+    return _cycle_mse_torch(fakeSR, Real_LR)
 
 
 def _weight_mse_torch(fake, label, att):

@@ -2238,6 +2238,94 @@ def weight_mse_bwd(grad: torch.Tensor, fake: torch.Tensor, label: torch.Tensor, 
     return d_fake, d_label, d_att
 
 
+# ----------------------------------------------------------------------------------------- cycle-consistency loss
+CYCLE_MAX_SCALES = 8     # scale descriptors of one launch (tgsr_cycle_mse.hip)
+CYCLE_MAX_SIDE = 65536   # every image side: the backward's candidate ranges are float32 arithmetic
+
+
+def check_cycle_mse(sr_shapes, lr_shape) -> Tuple[int, ...]:
+    """The shape checks of tgsr_cycle_mse_fwd / _bwd (include/tgsr_hip.h) on the host and with a message: 1 to 8 SR images
+    [B, C, H_i, W_i] against one LR image [B, C, h, w], every size in [1, 65536], H_i / h and W_i / w arbitrary.  Returns
+    (n, B, C, h, w, (H_0, W_0, H_1, W_1, ...)) or raises TgsrError.  Touches no device."""
+    shapes = [tuple(int(v) for v in s) for s in sr_shapes]
+    ls = tuple(int(v) for v in lr_shape)
+    if not 1 <= len(shapes) <= CYCLE_MAX_SCALES:
+        raise TgsrError("cycle_mse: %d scales, the kernels take 1 to %d in one call" % (len(shapes), CYCLE_MAX_SCALES))
+    if len(ls) != 4 or min(ls) < 1:
+        raise TgsrError("cycle_mse: lr [B, C, h, w] expected (no empty dimension), got %s" % (ls,))
+    B, C, h, w = ls
+    sizes = []
+    for i, s in enumerate(shapes):
+        if len(s) != 4 or min(s) < 1:
+            raise TgsrError("cycle_mse: sr[%d] [B, C, H, W] expected (no empty dimension), got %s" % (i, s))
+        if s[:2] != (B, C):
+            raise TgsrError("cycle_mse: sr[%d] %s and lr %s differ in batch or channels" % (i, s, ls))
+        sizes += [s[2], s[3]]
+    if max(sizes + [h, w]) > CYCLE_MAX_SIDE:
+        raise TgsrError("cycle_mse: an image side of %d pixels, the kernels take at most %d" % (max(sizes + [h, w]), CYCLE_MAX_SIDE))
+    return len(shapes), B, C, h, w, tuple(sizes)
+
+
+def _int_array(values):
+    return (ctypes.c_int * len(values))(*values)
+
+
+def _ptr_array(tensors):
+    return (ctypes.c_void_p * len(tensors))(*[None if t is None else t.data_ptr() for t in tensors])
+
+
+def cycle_mse(sr, lr: torch.Tensor):
+    """CycleMSE (tgsr_cycle_mse_fwd): `sr` a list of 1 to 8 float32 images [B, C, H_i, W_i], `lr` float32 [B, C, h, w].  Returns
+    (loss [], terms [n], diff [n, B, C, h, w]): sum_i mean((bicubic(sr_i -> h x w) - lr)^2), its per-scale terms, and the
+    differences `cycle_mse_bwd` reads.  One forward launch for all scales and one finish launch; dense tensors at any 4-byte
+    aligned base."""
+    sr = list(sr)
+    for i, t in enumerate(sr):
+        _dense_f32(t, "sr[%d]" % i, "cycle_mse", "[B, C, H, W]")
+    _dense_f32(lr, "lr", "cycle_mse", "[B, C, h, w]")
+    n, B, C, h, w, sizes = check_cycle_mse([t.shape for t in sr], lr.shape)
+    _need_hip(lr, *sr)
+    sr, lr = [t.detach().contiguous() for t in sr], lr.detach().contiguous()
+    dev = lr.device
+    L = _lib.lib()
+    Hs, Ws = _int_array(sizes[0::2]), _int_array(sizes[1::2])
+    ws = torch.empty(L.tgsr_cycle_mse_ws_elems(Hs, Ws, n, B, C, h, w), dtype=torch.float32, device=dev)
+    loss = torch.empty((), dtype=torch.float32, device=dev)
+    terms = torch.empty(n, dtype=torch.float32, device=dev)
+    diff = torch.empty(n, B, C, h, w, dtype=torch.float32, device=dev)
+    check(L.tgsr_cycle_mse_fwd(_ptr_array(sr), Hs, Ws, n, _p(lr), B, C, h, w, _p(ws), _p(diff), _p(loss), _p(terms), _stream()),
+          "tgsr_cycle_mse_fwd")
+    return loss, terms, diff
+
+
+def cycle_mse_bwd(grad: torch.Tensor, diff: torch.Tensor, sizes, need_sr=None, need_lr: bool = False):
+    """(d_sr list, d_lr) of cycle_mse (tgsr_cycle_mse_bwd), None where not asked for: grad the [] gradient of the loss ON THE DEVICE,
+    diff [n, B, C, h, w] what the forward saved, sizes = (H_0, W_0, H_1, W_1, ...) of the SR images, need_sr one flag per scale
+    (default: all).  Every d_sr[i] [B, C, H_i, W_i] is written completely (zeros where no tap lands), in one launch for all scales."""
+    _dense_f32(diff, "diff", "cycle_mse_bwd", "[n, B, C, h, w]")
+    if not torch.is_tensor(grad) or grad.dtype != torch.float32 or grad.numel() != 1:
+        raise TgsrError("cycle_mse_bwd: grad must be one float32 value, got %s"
+                        % ("%s %s" % (grad.dtype, tuple(grad.shape)) if torch.is_tensor(grad) else type(grad).__name__))
+    sizes = [int(v) for v in sizes]
+    n, B, C, h, w = (int(v) for v in diff.shape)
+    if len(sizes) != 2 * n:
+        raise TgsrError("cycle_mse_bwd: %d sizes for the %d scales of diff %s (H and W of each expected)" % (len(sizes), n, tuple(diff.shape)))
+    check_cycle_mse([(B, C, sizes[2 * i], sizes[2 * i + 1]) for i in range(n)], (B, C, h, w))
+    need_sr = [True] * n if need_sr is None else [bool(v) for v in need_sr]
+    if len(need_sr) != n:
+        raise TgsrError("cycle_mse_bwd: %d need_sr flags for %d scales" % (len(need_sr), n))
+    if not (any(need_sr) or need_lr):
+        raise TgsrError("cycle_mse_bwd: no gradient asked for")
+    _need_hip(grad, diff)
+    diff = diff.detach().contiguous()
+    dev = diff.device
+    d_sr = [torch.empty(B, C, sizes[2 * i], sizes[2 * i + 1], dtype=torch.float32, device=dev) if need_sr[i] else None for i in range(n)]
+    d_lr = torch.empty(B, C, h, w, dtype=torch.float32, device=dev) if need_lr else None
+    check(_lib.lib().tgsr_cycle_mse_bwd(_p(grad.detach().contiguous()), _p(diff), _int_array(sizes[0::2]), _int_array(sizes[1::2]), n, B, C,
+                                        h, w, _ptr_array(d_sr), _p(d_lr), _stream()), "tgsr_cycle_mse_bwd")
+    return d_sr, d_lr
+
+
 # ----------------------------------------------------------------------------------------- discriminator convolutions
 def _dconv(kind: int):
     L = _lib.lib()

@@ -115,7 +115,7 @@ class GraphPolicy:
 class SRTrainer:
     def __init__(self, n_words, device="cuda", low="lr", lr=None, ema_decay=0.999, image_encoder=None,
                  discriminators=False, d_lr=None, gather_negatives=None, weightmap=False, use_act=True, pixel_loss="mse",
-                 reweight=False):
+                 reweight=False, cycle=0.0):
         """image_encoder: optional frozen module image [B,3,256,256] -> (region features [B,nef,17,17], cnn_code
         [B,nef]) (a CNN_ENCODER with its trunk): adds the DAMSM ranking term of generator_loss (losses.py:375-386)
         on the finest image, x TRAIN.SMOOTH.LAMBDA.
@@ -137,7 +137,18 @@ class SRTrainer:
         reweight: the ranking term scales every word by the confidence of the LAST attention map (words_reweight_loss /
         generator_re_weight_loss, losses.py:137-232, 318-350; detached, as there); needs `image_encoder`.
         Either option keeps the generators' update on the eager path (`_g_graphs`); reweight with gather_negatives and more than
-        one rank is refused: the confidences would have to be gathered with the words."""
+        one rank is refused: the confidences would have to be gathered with the words.
+        cycle: weight of the cycle-consistency term (default 0.0: the term does not exist).  With cycle > 0 the generators' loss gains
+        cycle * (CycleMSE(fake_imgL, LR) + CycleMSE(fine_im, LR)) (losses.py:785-790): both generators' pyramids, resized back to
+        the LR size by bicubic interpolation, are held to `LR`, the step's own LR input.  The reference defines the function and ships
+        no training loop: which images it is applied to, and against which LR tensor, is the build's declaration, like the pairing
+        above.  Each call is one forward and one backward launch of tgsr_cycle_mse.hip with nothing on the host that depends on
+        data, so - unlike the attention-guided options - the term leaves the generators' update on the captured path.  It is a
+        per-shard batch mean like MSE: nothing to do for data parallelism."""
+        self.cycle = float(cycle)
+        if not self.cycle >= 0.0 or self.cycle == float("inf"):
+            raise ValueError("cycle must be a finite weight >= 0, got %r" % (cycle,))
+        self._lr_in, self.cycle_fused = None, None     # the step's LR input (kept only with cycle > 0); `fused` of CycleMSE
         if pixel_loss not in ("mse", "weight_mse"):
             raise ValueError("pixel_loss must be 'mse' or 'weight_mse', got %r" % (pixel_loss,))
         self.pixel_loss, self.reweight = pixel_loss, bool(reweight)
@@ -368,6 +379,7 @@ class SRTrainer:
         # against 11.6 ms on one stream once the weight gradients have their side stream - not kept)
         fake_imgL, att, mu, logvar = self.netGL(LR, sent_emb, words_embs, mask)
         self._att = [a.detach() for a in att] if self._attn_losses else None
+        self._lr_in = LR if self.cycle > 0 else None
         fine_im, _a, _one = self.netGH(LR, fake_imgL, LRb)
         return fake_imgL, fine_im, mu, logvar
 
@@ -619,7 +631,7 @@ class SRTrainer:
         if not use or self._attn_losses or (self.image_encoder is not None and self.gather_negatives and dp_world() > 1):
             # (DAMSM on the gathered global batch all-gathers inside generator_loss; the attention-guided losses are not captured yet)
             return None
-        hyper = self._opt_key(self.opt) + (self.ema_decay,)
+        hyper = self._opt_key(self.opt) + (self.ema_decay, self.cycle)
         if hyper != self._ghyper:
             self._ggraphs, self._ghyper = {}, hyper
         key = self._g_key(gan, LR, words_embs, cap_lens, class_ids)
@@ -629,6 +641,13 @@ class SRTrainer:
         return g or None
 
     def _pixel_kl(self, fake_imgL, fine_im, mu, logvar, hr_pyramid):
+        base = self._pixel_kl_base(fake_imgL, fine_im, mu, logvar, hr_pyramid)
+        if self.cycle > 0:          # (cycle == 0: CycleMSE is not called and the loss is the expression it always was)
+            return base + self.cycle * (losses.CycleMSE(fake_imgL, self._lr_in, fused=self.cycle_fused) +
+                                        losses.CycleMSE(fine_im, self._lr_in, fused=self.cycle_fused))
+        return base
+
+    def _pixel_kl_base(self, fake_imgL, fine_im, mu, logvar, hr_pyramid):
         if self.pixel_loss == "weight_mse":
             return (losses.weight_MSE(fake_imgL, hr_pyramid, self._att, fused=self.attn_fused)[0] +
                     losses.weight_MSE(fine_im, hr_pyramid, self._att, fused=self.attn_fused)[0] + losses.KL_loss(mu, logvar))
