@@ -471,7 +471,8 @@ int tgsr_linear_fwd(const float* x, int B, int K, const float* w, const float* b
  * The discriminators' logit heads (nn.Conv2d(8 ndf, 1, kernel_size=4, stride=4) on a 4x4 map, called by
  * losses.py:292-316 / 359-366 as netD.COND_DNET / UNCOND_DNET): out[b] = sum_k x[b][k] w[k] + bias[0], one workgroup
  * per sample, fixed-order reduction.  Backward: dx[b][k] = dy[b] w[k] (dx may be NULL), dw[k] = sum_b dy[b] x[b][k]
- * (dw may be NULL).  x, w 16-byte aligned.
+ * (dw may be NULL).  Forward: x, w 16-byte aligned, at every K - one off is refused with TGSR_EUNSUPPORTED, also where K % 4 != 0
+ * and the kernel would read single floats.  The backward reads and writes single floats: a float's alignment is enough.
  */
 int tgsr_rowdot_fwd(const float* x, const float* w, const float* bias, float* out, int B, int K, void* stream);
 
@@ -480,6 +481,13 @@ int tgsr_rowdot_fwd(const float* x, const float* w, const float* bias, float* ou
  * mu = h[:ncf], logvar = h[ncf:] ([B][ncf] each); c_code = eps * exp(0.5 * logvar) + mu with eps [B][ncf] standard
  * normals drawn by the caller (the reference draws them from torch's generator, util.py:388-396).  c_code and eps may
  * both be NULL (the x8 generators discard c_code, model.py:51-52).
+ * Two kernels, chosen by tdim and by the alignment of sent_emb and w (every other operand is read by single floats):
+ *   tdim % 16 == 0, and for tdim % 64 == 0 sent_emb and w both 16-byte aligned: the MFMA form (16 samples x 4 channels per
+ *     workgroup; float4 operand loads when tdim % 64 == 0, single floats otherwise) - the form tgsr_text_tail_fwd runs;
+ *   every other tdim, and tdim % 64 == 0 with sent_emb or w off 16 bytes: the row-per-thread form, which keeps tdim + 4 ncf + 8
+ *     floats in LDS and is refused with TGSR_EUNSUPPORTED when (tdim + 4 ncf) * 4 bytes exceed 60 KB; it reads w by float4 when
+ *     tdim % 8 == 0 and w is 16-byte aligned, by single floats otherwise.
+ * The two forms sum in different orders: the same values within rounding, not the same bits.
  */
 int tgsr_ca_net_fwd(const float* sent_emb, const float* w, const float* bias, const float* eps, int B, int tdim, int ncf,
                     float* c_code, float* mu, float* logvar, void* stream);
@@ -802,7 +810,11 @@ int tgsr_leaky_relu(const float* x, const float* y_for_bwd, float* out, int64_t 
  */
 int tgsr_glu(const float* x, const float* dy, float* out, int64_t outer, int64_t half, void* stream);
 
-/* Backward of nn.Upsample(scale_factor=2, 'nearest'): out[bc][y][x] = sum of in[bc][2y..2y+1][2x..2x+1]. */
+/*
+ * Backward of nn.Upsample(scale_factor=2, 'nearest'): out[bc][y][x] = sum of in[bc][2y..2y+1][2x..2x+1], x dense [BC][2H][2W],
+ * out dense [BC][H][W].  x needs no more than a float's alignment: the kernel reads pairs with 8-byte loads where x is 8-byte
+ * aligned and single floats where it is not, (x00 + x01) + (x10 + x11) either way - the same bits.
+ */
 int tgsr_sumpool2x2(const float* x, int64_t BC, int H, int W, float* out, void* stream);
 
 /*

@@ -24,6 +24,7 @@ no conversion produces (theirs are 0x7FC0 / 0x7E00).
     img = a.place_lp(torch.bfloat16, B, H, W, cpitch, reads=[(0, x)], writes=[(32, 32)])   # an lp image [B][H+2][W+2][cpitch]
     pk = a.place_output16(n, torch.bfloat16)                                               # a dense pack of n elements
     m = a.place_output_u8((B, T))                                                          # a byte output, padded to whole words
+    img = a.place_output_u8((n,), lead=1, expect=ref)                                      # ... one byte off a word, of any byte values
 
 An lp image holds zeros on its one-pixel border, the values of `reads` (NCHW tensors, exactly representable) in their channel
 ranges and PATTERN16 in every other channel of the interior; the call may write the interior pixels x the channel ranges of
@@ -54,7 +55,7 @@ class Region:
 
     @property
     def address(self):
-        return self.arena.base_address() + 4 * self.offset
+        return self.arena.base_address() + 4 * self.offset + getattr(self, "lead", 0)     # lead: bytes, Region16 only
 
     @property
     def ptr(self):
@@ -108,8 +109,8 @@ class Region16(Region):
     """A dense run of 2-byte elements (a weight pack, att_pack) or of bytes (a mask), padded to whole words; `image` holds its initial
     elements, `mask` which of them the call may write (all ones / zero per element), `must` which of those it has to write."""
 
-    def __init__(self, arena, kind, offset, shape, dtype, image, mask, must, finite):
-        self.image, self.mask, self.must, self.finite = image, mask, must, finite
+    def __init__(self, arena, kind, offset, shape, dtype, image, mask, must, finite, lead=0):
+        self.image, self.mask, self.must, self.finite, self.lead = image, mask, must, finite, lead
         super().__init__(arena, kind, offset, shape, 1, image.view(torch.int32).numel(), None, dtype, None)
         self.bstride = self.per
 
@@ -129,7 +130,8 @@ class Region16(Region):
         return self.words().view(self.image.dtype)
 
     def read(self):
-        e = self.elements()[:int(np.prod(self.shape))].reshape(self.shape).clone()
+        lead = self.lead // self.image.dtype.itemsize
+        e = self.elements()[lead:lead + int(np.prod(self.shape))].reshape(self.shape).clone()
         return e.view(self.dtype) if self.image.dtype == torch.int16 and self.dtype.itemsize == 2 else e
 
     def complaints(self, i):
@@ -268,14 +270,22 @@ class Arena:
         """A dense output of 2-byte elements, PATTERN16-prefilled; finite=False: raw bits (att_pack's mask words)."""
         return self._dense16(_OUTPUT, shape, dtype, None, written, finite, align, skew)
 
-    def place_output_u8(self, shape, align=16, skew=0, written=True):
-        """A byte output (the text tail's mask): PATTERN's bytes before the call - none of them 0 or 1 - and behind its last element."""
+    def place_output_u8(self, shape, align=16, skew=0, written=True, lead=0, expect=None):
+        """A byte output (the text tail's mask): PATTERN's bytes before the call - none of them 0 or 1 - and behind its last element.
+        `lead` (0..3): the operand starts that many BYTES behind the word `align` and `skew` place, the bytes in front of it guarded
+        like those behind its last element (an output that is not word aligned).  `expect` (uint8, the right result): an output
+        whose values may be any byte (an image; 0xA5, 0xC5 and 0x7F are PATTERN's) counts as unwritten only where the byte it holds
+        after the call is PATTERN's and the right one is another."""
         shape = tuple(int(s) for s in shape)
         n = int(np.prod(shape))
-        img = torch.full(((n + 3) // 4,), PATTERN, dtype=torch.int32).view(torch.uint8).clone()
+        assert 0 <= lead <= 3
+        img = torch.full(((lead + n + 3) // 4,), PATTERN, dtype=torch.int32).view(torch.uint8).clone()
         mask, must = torch.zeros_like(img), torch.zeros(img.shape, dtype=torch.bool)
-        mask[:n], must[:n] = 255, True
-        return self._place16(Region16(self, _OUTPUT if written else _ABSENT, 0, shape, torch.uint8, img, mask, must, False), align, skew)
+        mask[lead:lead + n], must[lead:lead + n] = 255, True
+        if expect is not None:
+            must[lead:lead + n] = expect.reshape(-1) != img[lead:lead + n]
+        return self._place16(Region16(self, _OUTPUT if written else _ABSENT, 0, shape, torch.uint8, img, mask, must, False, lead),
+                             align, skew)
 
     def place_ws(self, n, align=16, skew=0):
         """A workspace of exactly `n` floats, PATTERN-prefilled (a NaN: whatever is read before it is written poisons the result)."""

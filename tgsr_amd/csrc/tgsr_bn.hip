@@ -518,17 +518,27 @@ __global__ __launch_bounds__(kBnThreads) void bn_fin_act_bwd_apply_kernel(
 }
 
 // out[bc][y][x] = sum of the 2x2 block of in[bc][2y..2y+1][2x..2x+1]   (backward of the nearest x2 up-sample)
+// Every pair lies an even number of floats behind `in`: 8-byte loads when `in` is 8-byte aligned, single floats otherwise
+// (a contiguous view at an odd offset of its storage) - the same sum in the same order either way.
 __global__ __launch_bounds__(256) void sumpool2x2_kernel(const float* __restrict__ in, int64_t BC, int H, int W,
                                                          float* __restrict__ out) {
   const int64_t total = BC * H * W;
+  const bool pairs = (reinterpret_cast<uintptr_t>(in) & 7) == 0;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
     const int x = (int)(i % W);
     const int64_t t = i / W;
     const int y = (int)(t % H);
     const int64_t bc = t / H;
     const float* r0 = in + (bc * 2 * H + 2 * y) * (int64_t)(2 * W) + 2 * x;
-    const float2 u = *reinterpret_cast<const float2*>(r0);
-    const float2 v = *reinterpret_cast<const float2*>(r0 + 2 * W);
+    const float* r1 = r0 + 2 * W;
+    float2 u, v;
+    if (pairs) {
+      u = *reinterpret_cast<const float2*>(r0);
+      v = *reinterpret_cast<const float2*>(r1);
+    } else {
+      u = make_float2(r0[0], r0[1]);
+      v = make_float2(r1[0], r1[1]);
+    }
     out[i] = (u.x + u.y) + (v.x + v.y);
   }
 }
