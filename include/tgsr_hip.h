@@ -937,6 +937,41 @@ int tgsr_tile_stitch(int n, const float* const* src, const int64_t* src_stride, 
                      int Tb, int th, int tw, void* stream);
 
 /*
+ * Geometric self-ensemble, x8 (csrc/tgsr_ensemble.hip; SRPipeline.upscale(ensemble=8), SRPipeline.self_ensemble): the network runs
+ * on the eight flips and rotations of a window, the eight outputs are mapped back and averaged.
+ * THE TRANSFORM.  Variant k = 0..7 has bits b0 = k & 1 (mirror the columns), b1 = k & 2 (mirror the rows), b2 = k & 4 (transpose,
+ * applied first).  For a window `win` of th x tw, variant k has shape (th', tw') = b2 ? (tw, th) : (th, tw); its pixel (i, j) is
+ * win[y][x] with
+ *     i' = b1 ? th' - 1 - i : i        j' = b0 ? tw' - 1 - j : j        (y, x) = b2 ? (j', i') : (i', j').
+ * Outputs at scale s follow the same rule with every size multiplied by s.  The ensemble value of an output pixel is
+ *     (((((((v0 + v1) + v2) + v3) + v4) + v5) + v6) + v7) * 0.125f       in float32, one rounding per operation,
+ * v_k = variant k's output at the position that maps back to the pixel, summed in ascending k: the same bits on every run.
+ * The window table and its rules are tgsr_tile_gather's (above), applied to every one of the N images; the same TGSR_EINVAL for
+ * each of them, for a missing pointer, N outside [1, 4096] and the cases named below.
+ *   tgsr_d8_gather  img (and img2 unless NULL; out2 is NULL exactly when img2 is): [N][3][H][W], both uint8 (is_u8 != 0:
+ *       tgsr_u8_normalize's arithmetic) or both float32 (a bit copy).  Variants k0 .. k0 + nk - 1, (k0, nk) one of (0, 8) - which
+ *       needs th == tw -, (0, 4), (4, 4).  out / out2: float32 [N][Tb][nk][3][th'][tw'] - the variants of a window are
+ *       consecutive rows of the pipeline batch; (4, 4) gives the transposed group, [N][Tb][4][3][tw][th].  One launch for both.
+ *   tgsr_d8_merge   n <= TGSR_STITCH_MAX outputs of the variant batch in one launch (host arrays of n entries; n N <= 65535).
+ *       nk = 8: srcA[e] float32 [N][Tb][8][C[e]][s th][s tw] (th == tw), srcB NULL or srcB[e] NULL.  nk = 4: srcA[e] holds
+ *       variants 0..3 as [N][Tb][4][C[e]][s th][s tw] and srcB[e] the transposed group 4..7 as [N][Tb][4][C[e]][s tw][s th];
+ *       a srcB[e] that is present with nk = 8 or missing with nk = 4 is TGSR_EINVAL.  A batch row is a dense (C, rows, columns)
+ *       block; src_stride[e] >= its size: elements between consecutive batch rows of srcA[e] and of srcB[e].  s = scale[e] in
+ *       [1, 64].  dst[e]: [N][C[e]][s H][s W], float32 (out_u8[e] == 0: the mean) or uint8 (tgsr_to_uint8's rule applied to the
+ *       float32 mean).  Only each window's owned rectangle (times s) is written, each pixel once; two rows that name the same
+ *       window (a padded last batch) write the same values twice.  No atomics, no workspace.
+ * Layout: a workgroup owns a 32 x 32 block on the window's side; every global access runs along rows of its image, as aligned
+ * 16-byte quads where the bases, the row pitches and the row strides are multiples of 4 elements, element by element otherwise
+ * (any H, W, offsets); the mirrors and the transpose happen between a padded LDS block and registers.  Plain loads and stores;
+ * capturable.
+ */
+int tgsr_d8_gather(const void* img, const void* img2, int is_u8, int N, int H, int W, const int32_t* table_host,
+                   const int32_t* table_dev, int Tb, int th, int tw, int k0, int nk, float* out, float* out2, void* stream);
+int tgsr_d8_merge(int n, const float* const* srcA, const float* const* srcB, const int64_t* src_stride, void* const* dst,
+                  const int* C, const int* scale, const int* out_u8, int nk, int N, int H, int W, const int32_t* table_host,
+                  const int32_t* table_dev, int Tb, int th, int tw, void* stream);
+
+/*
  * Weight gradient of tgsr_conv3x3_fwd: dw[Cout][Cin][3][3] = sum over (b, y, x) of grad_out * shifted input
  * (upsample=1: the input is read through the folded nearest-x2, H/W are the PRE-upsample sizes).
  * grad_out [B][Cout][Ho][Wo] dense; x [B][Cin][H][W] with batch stride; Cout % 32 == 0.

@@ -671,6 +671,31 @@ tile_stitch = _define("tile_stitch(Tensor[] tiles, Tensor(a!)[] outs, Tensor tab
                       lambda *a: None)
 
 
+# geometric self-ensemble (x8; SRPipeline.upscale(ensemble=8), self_ensemble): the variant batch of every window of N images, and
+# the mean of its outputs mapped back.  srcs_t: empty when srcs hold all eight variants, else the transposed group of every output
+def _d8_shape(img, table, th, tw, k0, nk):
+    hh, ww = (tw, th) if k0 == 4 else (th, tw)
+    return (img.shape[0], table.shape[0], nk, 3, hh, ww)
+
+
+def _d8_gather(img, img2, table, table_dev, th, tw, k0, nk):
+    lr, lrb = ops.d8_gather(img, table, th, tw, k0, nk, img2=img2, table_dev=table_dev)
+    return lr, (lrb if lrb is not None else lr.new_empty(0))
+
+
+d8_gather = _define("d8_gather(Tensor img, Tensor? img2, Tensor table, Tensor table_dev, int th, int tw, int k0, int nk) "
+                    "-> (Tensor, Tensor)", _d8_gather,
+                    lambda img, img2, table, table_dev, th, tw, k0, nk: (
+                        img.new_empty(_d8_shape(img, table, th, tw, k0, nk), dtype=torch.float32),
+                        img.new_empty(_d8_shape(img, table, th, tw, k0, nk) if img2 is not None else (0,), dtype=torch.float32)))
+d8_merge = _define("d8_merge(Tensor[] srcs, Tensor[] srcs_t, Tensor(a!)[] outs, Tensor table, Tensor table_dev, int H, int W, int th, "
+                   "int tw) -> ()",
+                   lambda srcs, srcs_t, outs, table, table_dev, H, W, th, tw:
+                   ops.d8_merge(list(srcs), list(outs), table, H, W, th, tw, srcs_t=list(srcs_t) if len(srcs_t) else None,
+                                table_dev=table_dev),
+                   lambda *a: None)
+
+
 # ================================================================================================ reduced-precision path
 # (lp images are mutable arguments: every kernel writes a channel slice of a caller-owned zero-bordered image)
 lp_conv3x3 = _define("lp_conv3x3(Tensor x, Tensor wpack, int cin, int cout, Tensor? scale, Tensor? shift, bool glu, bool upsample, "

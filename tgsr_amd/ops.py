@@ -2031,6 +2031,117 @@ def tile_stitch(tiles, outs, table, H: int, W: int, th: int, tw: int, table_dev:
     check(rc, "tgsr_tile_stitch")
 
 
+# ----------------------------------------------------------------------------------------- geometric self-ensemble (x8)
+D8_MAX_N = 4096          # images per d8_gather / d8_merge launch
+_D8_GROUPS = ((0, 8), (0, 4), (4, 4))
+
+
+def d8_gather(img: torch.Tensor, table, th: int, tw: int, k0: int = 0, nk: int = 8, img2: Optional[torch.Tensor] = None,
+              table_dev: Optional[torch.Tensor] = None):
+    """The variants k0 .. k0 + nk - 1 (tgsr_amd.tiles: the transform) of every window of N planar images [N, 3, H, W] (and of a
+    second batch of the same shape and dtype - the blurred LR - in the same launch) as float32 [N, Tb, nk, 3, th', tw']
+    (tgsr_d8_gather): uint8 is normalised exactly like `u8_normalize`, float32 is a bit copy.  (k0, nk): (0, 8) - square windows
+    only -, (0, 4) or (4, 4), the transposed group [N, Tb, 4, 3, tw, th].  table: host int32 [Tb, 6] (check_tile_table), applied to
+    every image; table_dev: its device copy where the caller keeps one.  Returns (LR, LRb) - LRb None without img2."""
+    for name, x in (("img", img), ("img2", img2)):
+        if x is None:
+            continue
+        if not torch.is_tensor(x) or x.dim() != 4 or x.shape[1] != 3 or x.dtype not in (torch.uint8, torch.float32):
+            raise TgsrError("d8_gather: %s must be a batch of planar uint8 or float32 [N, 3, H, W] images, got %s" % (
+                name, "%s %s" % (x.dtype, tuple(x.shape)) if torch.is_tensor(x) else type(x).__name__))
+    if img2 is not None and (img2.shape != img.shape or img2.dtype != img.dtype):
+        raise TgsrError("d8_gather: img2 is %s %s, img %s %s" % (img2.dtype, tuple(img2.shape), img.dtype, tuple(img.shape)))
+    N, H, W = int(img.shape[0]), int(img.shape[2]), int(img.shape[3])
+    k0, nk, th, tw = int(k0), int(nk), int(th), int(tw)
+    if not 1 <= N <= D8_MAX_N:
+        raise TgsrError("d8_gather: %d images (1 to %d per launch)" % (N, D8_MAX_N))
+    if (k0, nk) not in _D8_GROUPS:
+        raise TgsrError("d8_gather: variants k0 = %d, nk = %d - the groups are (0, 8), (0, 4) and (4, 4)" % (k0, nk))
+    if nk == 8 and th != tw:
+        raise TgsrError("d8_gather: all eight variants in one batch need a square window, got %d x %d - gather (0, 4) and (4, 4)"
+                        % (th, tw))
+    t = _tile_table_host(table, H, W, th, tw)
+    _need_hip(img, img2, table_dev)
+    tdev = _tile_table_dev(table_dev, t, img.device)
+    img = img.contiguous()
+    img2 = None if img2 is None else img2.contiguous()
+    Tb = t.shape[0]
+    hh, ww = (tw, th) if k0 == 4 else (th, tw)
+    out = torch.empty(N, Tb, nk, 3, hh, ww, dtype=torch.float32, device=img.device)
+    out2 = torch.empty_like(out) if img2 is not None else None
+    rc = _lib.lib().tgsr_d8_gather(_p(img), _p(img2), int(img.dtype == torch.uint8), N, H, W, _p(t), _p(tdev), Tb, th, tw, k0, nk,
+                                   _p(out), _p(out2), _stream())
+    if rc:
+        check_tile_table(t, H, W, th, tw)                  # the window at fault, by name
+    check(rc, "tgsr_d8_gather")
+    return out, out2
+
+
+def d8_merge(srcs, outs, table, H: int, W: int, th: int, tw: int, srcs_t=None, table_dev: Optional[torch.Tensor] = None) -> None:
+    """The owned rectangle of every window of the MEAN of the eight variant outputs, each mapped back (tgsr_amd.tiles: the
+    transform and the fixed float32 summation order), into the whole-image outputs, in one launch (tgsr_d8_merge).
+    srcs[e]: float32 [N * Tb * nk, C, s th, s tw], the outputs of the variant batch `d8_gather` made - a dense (C, s th, s tw) block
+    per batch row, any row stride.  Without srcs_t nk = 8 (square windows); with it nk = 4 and srcs_t[e] is the transposed group
+    [N * Tb * 4, C, s tw, s th] with the same row stride.  outs[e]: dense [N, C, s H, s W], float32 (the mean) or uint8 (`to_uint8`
+    of the mean); N and the scale s are read off the shapes.  Pixels no window owns keep what `outs` held."""
+    srcs, outs = list(srcs), list(outs)
+    n = len(srcs)
+    if n < 1 or n != len(outs) or n > STITCH_MAX:
+        raise TgsrError("d8_merge: %d variant outputs for %d images (1 to %d per launch)" % (n, len(outs), STITCH_MAX))
+    nk = 8 if srcs_t is None else 4
+    srcs_t = [None] * n if srcs_t is None else list(srcs_t)
+    if len(srcs_t) != n or any(x is None for x in srcs_t) != (nk == 8):
+        raise TgsrError("d8_merge: srcs_t holds the transposed group of EVERY output (%d entries), or is None when srcs hold all "
+                        "eight variants" % n)
+    th, tw, H, W = int(th), int(tw), int(H), int(W)
+    if nk == 8 and th != tw:
+        raise TgsrError("d8_merge: eight variants in one batch need a square window, got %d x %d - pass the transposed group as "
+                        "srcs_t" % (th, tw))
+    t = _tile_table_host(table, H, W, th, tw)
+    Tb = t.shape[0]
+    _need_hip(*srcs, *[x for x in srcs_t if x is not None], *outs, table_dev)
+    tdev = _tile_table_dev(table_dev, t, srcs[0].device)
+    N = int(outs[0].shape[0]) if torch.is_tensor(outs[0]) and outs[0].dim() == 4 else 0
+    if not 1 <= N <= D8_MAX_N or n * N > 65535:
+        raise TgsrError("d8_merge: outs[0] must be [N, C, s*%d, s*%d] with 1 <= N <= %d and %d N <= 65535, got %s"
+                        % (H, W, D8_MAX_N, n, tuple(outs[0].shape)))
+    rows = N * Tb * nk
+    Cs, ss, u8s, strides = [], [], [], []
+    for e, (x, xt, o) in enumerate(zip(srcs, srcs_t, outs)):
+        if x.dtype != torch.float32 or x.dim() != 4 or x.shape[0] != rows:
+            raise TgsrError("d8_merge: srcs[%d] must be float32 [%d, C, s*%d, s*%d] (N = %d images x %d windows x %d variants), got "
+                            "%s %s" % (e, rows, th, tw, N, Tb, nk, x.dtype, tuple(x.shape)))
+        C, s = int(x.shape[1]), int(x.shape[2]) // th
+        if s < 1 or s > 64 or tuple(x.shape[2:]) != (s * th, s * tw) or C < 1 or C > 65535:
+            raise TgsrError("d8_merge: srcs[%d] %s is no [%d, C, s*%d, s*%d] for an integer scale 1 <= s <= 64"
+                            % (e, tuple(x.shape), rows, th, tw))
+        block = C * s * th * s * tw
+        for name, y, hw in (("srcs", x, (s * th, s * tw)), ("srcs_t", xt, (s * tw, s * th))):
+            if y is None:
+                continue
+            if y.dtype != torch.float32 or tuple(y.shape) != (rows, C) + hw:
+                raise TgsrError("d8_merge: %s[%d] must be float32 %s, got %s %s" % (name, e, (rows, C) + hw, y.dtype, tuple(y.shape)))
+            if (y.stride(3) != 1 or y.stride(2) != hw[1] or (C > 1 and y.stride(1) != hw[0] * hw[1]) or y.stride(0) < block
+                    or y.stride(0) != x.stride(0)):
+                raise TgsrError("d8_merge: %s[%d] needs a dense (C, H, W) block per batch row and one row stride for both groups "
+                                "(strides %s)" % (name, e, tuple(y.stride())))
+        if o.dtype not in (torch.float32, torch.uint8) or tuple(o.shape) != (N, C, s * H, s * W) or not o.is_contiguous():
+            raise TgsrError("d8_merge: outs[%d] must be a dense float32 or uint8 [%d, %d, %d, %d], got %s %s"
+                            % (e, N, C, s * H, s * W, o.dtype, tuple(o.shape)))
+        Cs.append(C)
+        ss.append(s)
+        u8s.append(int(o.dtype == torch.uint8))
+        strides.append(x.stride(0))
+    srcA = (ctypes.c_void_p * n)(*[x.data_ptr() for x in srcs])
+    srcB = (ctypes.c_void_p * n)(*[None if x is None else x.data_ptr() for x in srcs_t])
+    dst = (ctypes.c_void_p * n)(*[o.data_ptr() for o in outs])
+    rc = _lib.lib().tgsr_d8_merge(n, srcA, srcB, (ctypes.c_int64 * n)(*strides), dst, (ctypes.c_int * n)(*Cs), (ctypes.c_int * n)(*ss),
+                                  (ctypes.c_int * n)(*u8s), nk, N, H, W, _p(t), _p(tdev), Tb, th, tw, _stream())
+    if rc:
+        check_tile_table(t, H, W, th, tw)                  # the window at fault, by name
+    check(rc, "tgsr_d8_merge")
+
+
 # ----------------------------------------------------------------------------------------- image quality
 METRICS_WINDOW = 11      # the SSIM window; a shaved crop may not be smaller
 

@@ -6,13 +6,64 @@ into overlapping windows, run as an ordinary fixed-shape batch and put back toge
 pixel a window owns is at least one receptive radius (`receptive_halo`) away from each window edge that is not an image
 edge, and a window edge on the image edge sees the zero padding the whole image would see there.  `plan_axis` /
 `plan_tiles` produce such windows; ops.tile_gather / ops.tile_stitch (tgsr_tiles.hip) cut and reassemble on the device.
+
+The geometric self-ensemble (x8, `SRPipeline.upscale(ensemble=8)`, `SRPipeline.self_ensemble`) runs the network on the eight
+flips and rotations of a window and averages the eight outputs, each mapped back.  THE TRANSFORM, stated once (repeated in
+include/tgsr_hip.h; ops.d8_gather / ops.d8_merge, tgsr_ensemble.hip, implement it):
+
+    variant k = 0..7 has bits b0 = k & 1 (mirror the columns), b1 = k & 2 (mirror the rows), b2 = k & 4 (transpose, applied
+    first).  For a window `win` of th x tw, variant k has shape (th', tw') = (tw, th) if b2 else (th, tw); its pixel (i, j) is
+    win[y][x] with  i' = th' - 1 - i if b1 else i,  j' = tw' - 1 - j if b0 else j,  (y, x) = (j', i') if b2 else (i', j').
+    Outputs at scale s follow the same rule with every size multiplied by s.  The ensemble value of an output pixel is
+    (((((((v0 + v1) + v2) + v3) + v4) + v5) + v6) + v7) * 0.125f in float32 - v_k = variant k's output at the position that maps
+    back to the pixel, summed in ascending k: a fixed order, the same bits on every run.
+
+`d8_shape` / `d8_index` / `d8_apply` / `d8_invert` are that definition as host reference maps.
 """
 import math
 
+import numpy as np
 import torch
 import torch.nn as nn
 
 DEFAULT_TILE = 128      # SRPipeline.upscale's window side in LR pixels (measured: tools/upscale_timing.py, DESIGN.md 3.10)
+D8 = 8                  # variants of the geometric self-ensemble: the symmetries of the square
+
+
+def d8_shape(k: int, th: int, tw: int):
+    """(th', tw'): the shape of variant k of a th x tw window."""
+    if not 0 <= int(k) < D8:
+        raise ValueError("d8: variant %r is not in 0..7" % (k,))
+    return (int(tw), int(th)) if k & 4 else (int(th), int(tw))
+
+
+def d8_index(k: int, th: int, tw: int):
+    """(y, x): two int64 [th', tw'] tensors - pixel (i, j) of variant k is win[y[i, j], x[i, j]]."""
+    hh, ww = d8_shape(k, th, tw)
+    i, j = torch.meshgrid(torch.arange(hh), torch.arange(ww), indexing="ij")
+    ii = hh - 1 - i if k & 2 else i
+    jj = ww - 1 - j if k & 1 else j
+    return (jj, ii) if k & 4 else (ii, jj)
+
+
+def d8_apply(win, k: int):
+    """Variant k of win [..., th, tw] (torch tensor or numpy array) by the index maps: [..., th', tw']."""
+    y, x = d8_index(k, win.shape[-2], win.shape[-1])
+    return win[..., y, x] if torch.is_tensor(win) else win[..., y.numpy(), x.numpy()]
+
+
+def d8_invert(var, k: int):
+    """The window [..., th, tw] whose variant k is var [..., th', tw']: every pixel put back where d8_index took it from."""
+    hh, ww = var.shape[-2], var.shape[-1]
+    th, tw = (ww, hh) if k & 4 else (hh, ww)
+    y, x = d8_index(k, th, tw)
+    if torch.is_tensor(var):
+        out = var.new_empty(tuple(var.shape[:-2]) + (th, tw))
+        out[..., y, x] = var
+    else:
+        out = np.empty(var.shape[:-2] + (th, tw), var.dtype)
+        out[..., y.numpy(), x.numpy()] = var
+    return out
 
 
 def plan_axis(n: int, tile: int, halo: int):

@@ -875,13 +875,15 @@ class SRTrainer:
                 torch.cuda.set_rng_state(rng_dev, self.device)
 
     @torch.no_grad()
-    def evaluate(self, batches, ema=True, shave=0, max_batches=None, r_precision=None, generator=None):
+    def evaluate(self, batches, ema=True, shave=0, max_batches=None, r_precision=None, generator=None, ensemble=1):
         """Score a validation set: `batches` yields (captions, cap_lens, LR, LRb, hr_pyramid); the generators run in eval mode
         (SRPipeline.from_modules over this trainer's modules, no copies) with the EMA weights (`ema`, the ones `snapshot` saves by
         default) or the current ones, and every output scale is scored against hr_pyramid[k] on the device (tgsr_amd.metrics:
         PSNR / RMSE on RGB and Y, SSIM on Y, `shave` border pixels removed) - no synchronisation per batch, one at the end.
         Returns {"fine": [per scale], "fake": [per scale]}, per scale {"psnr": [N], "rmse", "psnr_y", "rmse_y", "ssim_y", "n": N,
         "mean": {...}} over the N images seen.  Afterwards the trainer is exactly as it was (`_eval_weights`).
+        ensemble=8 scores the geometric self-ensemble (SRPipeline.self_ensemble: the mean over the eight flips and rotations, the
+        "+" rows of an SR table) in place of the plain forward; everything else is unchanged.
         Data parallel: every rank passes ITS batches; the rows are gathered in rank order and every rank returns the same dict.
         `r_precision` = K (default None: nothing below happens) asks whether the output is consistent with its caption: the batches
         then carry `class_ids` as a sixth element, the finest `fine` image of every batch goes through `image_encoder` (required), and
@@ -892,6 +894,9 @@ class SRTrainer:
             self._eval_pipe = SRPipeline.from_modules(self.text_encoder, self.netGL, self.netGH, device=self.device)
         if r_precision is not None and self.image_encoder is None:
             raise ValueError("evaluate(r_precision=%r) needs the trainer's image_encoder" % (r_precision,))
+        if ensemble not in (1, 8):
+            raise ValueError("evaluate: ensemble is 1 or 8 (the eight flips and rotations), got %r" % (ensemble,))
+        forward = self._eval_pipe if ensemble == 1 else self._eval_pipe.self_ensemble
         book = metrics.ScoreBook(shave)
         nscales = 0
         seen = {"regions": [], "codes": [], "words": [], "sents": [], "lens": [], "class_ids": []}
@@ -903,7 +908,7 @@ class SRTrainer:
                     captions, cap_lens, LR, LRb, hr_pyramid, class_ids = batch
                 if max_batches is not None and k >= max_batches:
                     break
-                out = self._eval_pipe(captions, cap_lens, LR, LRb)
+                out = forward(captions, cap_lens, LR, LRb)
                 if r_precision is not None:
                     words_embs, sent_emb, _mask = self._text(captions, cap_lens)
                     feats, code = self.image_encoder(out["fine"][-1])

@@ -272,7 +272,7 @@ class SRPipeline:
 
     @torch.no_grad()
     def upscale(self, lr, caption, cap_len, lr_blur=None, tile=None, halo=None, tile_batch=4, out="f32", with_att=False,
-                graph=False):
+                graph=False, ensemble=1):
         """Super-resolve ONE image of any size (the reference's arbitrary-size example path, datasets.py:200-278
         get_imgsexampletest*, + gen_exampleSRHL on the whole image): the image is cut into overlapping `tile` x `tile` LR windows
         (ops.tile_gather), the windows run through this pipeline's own `__call__` in fixed-shape batches of `tile_batch`, and every
@@ -290,9 +290,17 @@ class SRPipeline:
         window, so every batch has one shape.  graph=True: one tile-batch step is captured (GraphedStep, kept per shape
         while the networks' weights stay what they were at the capture, `_tile_step`) and replayed per batch.
         out: "f32" (float32, un-clamped, the bits `__call__` returns) or "u8" (`to_uint8`'s bytes, converted in the stitch).
+        ensemble: 1, or 8 for the geometric self-ensemble (the "+" variant: tiles.py states the transform) - every window runs in its
+        eight flips and rotations, as ONE pipeline batch of 8 * tile_batch rows where the window is square, as two batches of
+        4 * tile_batch (th x tw and tw x th) where an image side shorter than the tile makes it rectangular; each output pixel is
+        the mean of the eight outputs mapped back, summed in a fixed order in float32 (ops.d8_gather / ops.d8_merge in place of
+        tile_gather / tile_stitch).  The blur is taken once, on the untransformed image; `att` is averaged like the images and
+        out="u8" quantises the mean.
         Returns {"fine": [3 x [3, sH, sW]], "fake": [...]} for s = 2, 4, 8, + "att": [3 x [cap_len, sH, sW]] (s = 1, 2, 4; float32)
         with with_att."""
         from . import tiles as T
+        if ensemble not in (1, 8):
+            raise ValueError("upscale: ensemble is 1 or 8 (the eight flips and rotations), got %r" % (ensemble,))
         if self.branch_num != 4:
             raise ValueError("upscale: the x16 generators (models16.py) are not tiled here - their receptive field and 16 x 16 "
                              "design size are out of this method's scope; use the x8 pipeline (branch_num=4)")
@@ -336,12 +344,16 @@ class SRPipeline:
                 table = torch.cat([table, table[-1:].expand(pad, -1)])             # repeat the last window: one batch shape
             table = ops.check_tile_table(table, H, W, th, tw)
             table_dev = table.to(lr.device)
-            caps = caption.reshape(1, -1).to(device=lr.device, dtype=torch.int64).expand(tb, -1).contiguous()
-            lens = [int(cap_len)] * tb
+            nrows = tb * (1 if ensemble == 1 else 8 if th == tw else 4)        # rows of one pipeline batch
+            caps = caption.reshape(1, -1).to(device=lr.device, dtype=torch.int64).expand(nrows, -1).contiguous()
+            lens = [int(cap_len)] * nrows
             odt = torch.uint8 if out == "u8" else torch.float32
             res = {k: [torch.empty(3, s * H, s * W, dtype=odt, device=lr.device) for s in (2, 4, 8)] for k in ("fine", "fake")}
             if with_att:
                 res["att"] = [torch.empty(lens[0], s * H, s * W, dtype=torch.float32, device=lr.device) for s in (1, 2, 4)]
+            if ensemble == 8:
+                self._upscale_d8(lr, lr_blur, table, table_dev, tb, th, tw, caps, lens, res, with_att, graph)
+                return res
             step = None
             for b in range(0, table.shape[0], tb):
                 rows, rows_dev = table[b:b + tb], table_dev[b:b + tb]
@@ -361,6 +373,67 @@ class SRPipeline:
                     srcs += list(o["att"])
                     dsts = dsts + res["att"]
                 C.tile_stitch(srcs, dsts, rows, rows_dev, H, W, th, tw)
+        return res
+
+    def _upscale_d8(self, lr, lr_blur, table, table_dev, tb, th, tw, caps, lens, res, with_att, graph):
+        """upscale(ensemble=8)'s loop over the tile batches: per batch one variant batch of 8 tb rows (square windows) or the two
+        groups of 4 tb rows (k = 0..3 at th x tw, k = 4..7 at tw x th), each through `__call__` or its captured step, then ONE
+        merge launch over every output."""
+        H, W = int(lr.shape[1]), int(lr.shape[2])
+        groups = ((0, 8),) if th == tw else ((0, 4), (4, 4))
+        imgs = lr.unsqueeze(0)
+        blurs = None if lr_blur is None else lr_blur.unsqueeze(0)
+        names = ("fine", "fake") + (("att",) if with_att else ())
+        dsts = [t.unsqueeze(0) for k in names for t in res[k]]
+        steps = {}
+        for b in range(0, table.shape[0], tb):
+            rows, rows_dev = table[b:b + tb], table_dev[b:b + tb]
+            outs = []
+            for k0, nk in groups:
+                LR, LRb = C.d8_gather(imgs, blurs, rows, rows_dev, th, tw, k0, nk)
+                LR = LR.flatten(0, 2)
+                LRb = LR if blurs is None else LRb.flatten(0, 2)                # low == "lr": the blurred image is not read
+                if not graph:
+                    o = self(caps, lens, LR, LRb)
+                elif k0 not in steps:
+                    steps[k0] = self._tile_step(caps, lens, LR, LRb)
+                    o = steps[k0].replay(caps, lens, LR, LRb)
+                else:
+                    o = steps[k0].replay(LR=LR, LRb=LRb)
+                outs.append([t for k in names for t in o[k]])
+            C.d8_merge(outs[0], outs[1] if len(outs) > 1 else [], dsts, rows, rows_dev, H, W, th, tw)
+
+    @torch.no_grad()
+    def self_ensemble(self, captions, cap_lens, LR, LRb):
+        """`__call__` with the geometric self-ensemble (the "+" variant; tiles.py states the transform): every sample of the batch
+        LR / LRb [B, 3, h, w] (float32, or uint8 - normalised like the loader's ToTensor + Normalize) runs in its eight flips and
+        rotations - one batch of 8 B rows for square images, two of 4 B (h x w and w x h) otherwise, a sample's variants
+        consecutive, so captions sorted by length stay sorted - and every image output (and attention map) is the mean of the
+        eight outputs mapped back, summed in a fixed order in float32 (ops.d8_gather / ops.d8_merge with the one-row table
+        (0, 0, 0, h, 0, w)).  Returns the dict `__call__` returns: fine, fake and att are the ensemble, the text outputs
+        (words_emb, sent_emb, mask, mu, logvar) the batch's own."""
+        if not torch.is_tensor(LR) or LR.dim() != 4 or LR.shape[1] != 3 or not LR.is_cuda:
+            raise ValueError("self_ensemble: LR must be a [B, 3, h, w] device tensor")
+        B, h, w = int(LR.shape[0]), int(LR.shape[2]), int(LR.shape[3])
+        groups = ((0, 8),) if h == w else ((0, 4), (4, 4))
+        nk = groups[0][1]
+        host = _host_lens(cap_lens)
+        with torch.cuda.device(LR.device):
+            table = torch.tensor([[0, 0, 0, h, 0, w]], dtype=torch.int32)
+            table_dev = table.to(LR.device)
+            caps = captions.to(device=LR.device, dtype=torch.int64).repeat_interleave(nk, 0)
+            lens = [n for n in host for _ in range(nk)]
+            outs, first = [], None
+            for k0, _nk in groups:
+                x, xb = C.d8_gather(LR, LRb, table, table_dev, h, w, k0, nk)
+                o = self(caps, lens, x.flatten(0, 2), xb.flatten(0, 2))
+                first = o if first is None else first
+                outs.append(list(o["fine"]) + list(o["fake"]) + list(o["att"]))
+            nf, na = len(first["fine"]), len(first["att"])
+            dsts = [t.new_empty((B, t.shape[1], t.shape[2], t.shape[3])) for t in outs[0]]
+            C.d8_merge(outs[0], outs[1] if len(outs) > 1 else [], dsts, table, table_dev, h, w, h, w)
+            res = {k: None if first[k] is None else first[k][::nk] for k in ("words_emb", "sent_emb", "mask", "mu", "logvar")}
+            res.update(fine=dsts[:nf], fake=dsts[nf:2 * nf], att=dsts[2 * nf:2 * nf + na])
         return res
 
     @torch.no_grad()
