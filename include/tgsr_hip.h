@@ -457,6 +457,35 @@ int tgsr_sent_gallery_fwd(const float* cnn, const float* rnn, const int32_t* can
 int tgsr_retrieval_ranks(const float* sim, const int32_t* target, int N, int K, int32_t* rank, void* stream);
 
 /*
+ * Distribution distances (csrc/tgsr_featdist.hip): the statistics behind the Frechet and the kernel distance of two feature sets
+ * (tgsr_amd/featdist.py finishes them).  Evaluation only, no backward.  Features are float32 and are widened to fp64 on read
+ * (exact; the product of two widened values is exact in fp64); every sum is an fp64 sum on v_mfma_f64_16x16x4_f64 or an fp64 add
+ * in an order the shapes alone fix.  No allocation, no synchronisation, no atomics: the same bits on every run; everything on
+ * `stream`, capturable.
+ *
+ * tgsr_feat_moments_add   sum[i] += sum_r x[r][i],   outer[i][j] += sum_r x[r][i] x[r][j]   (X^T X, the contraction over the rows).
+ *     x float32 [n][D] with row stride ldx >= D floats, sum fp64 [D], outer fp64 [D][D] row-major; any n >= 1, D >= 1 (D <= 64 *
+ *     65535).  DEFINED ELEMENTS OF outer: the block-upper part, i / 64 <= j / 64 (it contains the upper triangle i <= j); the
+ *     elements below the block diagonal are neither read nor written.  A reader mirrors the upper triangle (featdist.py does).
+ *     One launch: a read-modify-write of the block-upper part, each element owned by one lane.
+ * tgsr_poly_mmd_sums      S subsets of m rows each: subset s takes rows ix[s][0..m) of x and iy[s][0..m) of y (int32 tables
+ *     [S][m]; x float32 [nx][D] stride ldx, y float32 [ny][D] stride ldy).  With k(a, b) = (<a, b> / D + 1)^3 in fp64:
+ *       out[s][0] = sum_{i != j} k(x_i, x_j),   out[s][1] = sum_{i != j} k(y_i, y_j),   out[s][2] = sum_{i, j} k(x_i, y_j),
+ *     i, j POSITIONS in the subset (a row listed twice is two items).  out fp64 [S][3], written completely.  The m x m kernel
+ *     matrix is never stored: each 64 x 64 tile leaves one partial in `work` (tgsr_poly_mmd_ws_elems(S, m) doubles; 0 = a
+ *     shape the entry refuses), a second launch adds a sum's partials in tile order.  out[s] depends on the subset's rows alone,
+ *     not on s or on the other subsets.  Any m >= 2, S >= 1 (<= 65535), D >= 1.  A table entry outside [0, nx) / [0, ny) is
+ *     outside the contract and is checked on the host, where the table is made (ops.poly_mmd_sums); the kernel forms no
+ *     address from it and scores the item as a row of zeros.
+ * Both return TGSR_EINVAL without launching (and without touching an output) for a NULL pointer, n < 1, nx < 1, ny < 1, S < 1, m < 2,
+ * D < 1 or a row stride below D.
+ */
+int tgsr_feat_moments_add(const float* x, int n, int D, int64_t ldx, double* sum, double* outer, void* stream);
+int64_t tgsr_poly_mmd_ws_elems(int S, int m);
+int tgsr_poly_mmd_sums(const float* x, int nx, int64_t ldx, const float* y, int ny, int64_t ldy, const int32_t* ix,
+                       const int32_t* iy, int S, int m, int D, double* work, double* out, void* stream);
+
+/*
  * The two trainable heads of CNN_ENCODER (util.py:300-301, 364-367) as fp32 MFMA GEMMs with bias:
  * tgsr_conv1x1_fwd : emb_features, conv1x1 Cin -> Cout on [B][Cin][S] (S = ih*iw, 17*17) -> out [B][Cout][S]
  * tgsr_linear_fwd  : emb_cnn_code, out[b][o] = sum_k w[o][k] x[b][k] + bias[o]; x [B][K], w [Cout][K]

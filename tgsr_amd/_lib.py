@@ -89,6 +89,9 @@ SIGNATURES = {
     "tgsr_damsm_gallery_fwd": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _f, _f, _vp, _vp]),
     "tgsr_sent_gallery_fwd": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _f, _f, _vp, _vp]),
     "tgsr_retrieval_ranks": (_i, [_vp, _vp, _i, _i, _vp, _vp]),
+    "tgsr_feat_moments_add": (_i, [_vp, _i, _i, _i64, _vp, _vp, _vp]),
+    "tgsr_poly_mmd_ws_elems": (_i64, [_i, _i]),
+    "tgsr_poly_mmd_sums": (_i, [_vp, _i, _i64, _vp, _i, _i64, _vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
     "tgsr_conv1x1_fwd": (_i, [_vp, _i, _i, _i, _vp, _vp, _i, _vp, _vp]),
     "tgsr_linear_fwd": (_i, [_vp, _i, _i, _vp, _vp, _i, _vp, _vp]),
     "tgsr_rowdot_fwd": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp]),

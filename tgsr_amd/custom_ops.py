@@ -447,6 +447,13 @@ sent_gallery = _define("sent_gallery(Tensor cnn_code, Tensor rnn_code, float eps
                        lambda x, y, eps, g3, cand=None: x.new_empty(x.shape[0], y.shape[0] if cand is None else cand.shape[1]))
 retrieval_ranks = _define("retrieval_ranks(Tensor sim, Tensor target) -> Tensor", lambda sim, t: ops.retrieval_ranks(sim, t),
                           lambda sim, t: sim.new_empty(sim.shape[0], dtype=torch.int32))
+# distribution distances (tgsr_amd.featdist reads them; evaluation only, no autograd formula): the fp64 moments of a feature batch added
+# into `sum` [D] / `outer` [D, D] (its block-upper part), and the three kernel sums of KID for S subsets (`ix`, `iy` int [S, m]) -> [S, 3]
+feat_moments_add = _define("feat_moments_add(Tensor x, Tensor(a!) sum, Tensor(b!) outer) -> ()",
+                           lambda x, s, o: ops.feat_moments_add(x, s, o), lambda x, s, o: None)
+poly_mmd_sums = _define("poly_mmd_sums(Tensor x, Tensor y, Tensor ix, Tensor iy) -> Tensor",
+                        lambda x, y, ix, iy: ops.poly_mmd_sums(x, y, ix, iy),
+                        lambda x, y, ix, iy: x.new_empty((ix.shape[0], 3), dtype=torch.float64))
 
 
 # attention panels (tgsr_amd.attnviz reads it): (panel, conf, order, maps) - one tile per caption word, the word's attention map

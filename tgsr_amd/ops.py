@@ -1012,6 +1012,80 @@ def retrieval_ranks(sim: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
     return rank
 
 
+# ----------------------------------------------------------------------------------------- distribution distances
+def _feature_rows(t: torch.Tensor, name: str):
+    """(tensor, row stride in floats) of a float32 [n, D] feature matrix: a view with unit column stride is taken as it is (a
+    column slice of a wider matrix), anything else is copied."""
+    if t.dim() != 2 or t.shape[0] < 1 or t.shape[1] < 1:
+        raise TgsrError("%s must be a float32 [n >= 1, D >= 1] matrix, got %s" % (name, tuple(t.shape)))
+    t = _f32(t.detach(), name)
+    if t.stride(1) != 1 or (t.shape[0] > 1 and t.stride(0) < t.shape[1]):
+        t = t.contiguous()
+    return t, (t.stride(0) if t.shape[0] > 1 else t.shape[1])
+
+
+def feat_moments_add(x: torch.Tensor, sum: torch.Tensor, outer: torch.Tensor) -> None:
+    """sum[i] += sum_r x[r][i] and outer[i][j] += sum_r x[r][i] x[r][j] in fp64, one launch (tgsr_feat_moments_add).  x float32
+    [n, D] (any row stride >= D), sum float64 [D], outer float64 [D, D], both dense and updated in place.  Of `outer` only the
+    block-upper part (i // 64 <= j // 64) is read and written: featdist.FeatureMoments mirrors the upper triangle."""
+    _need_hip(x, sum, outer)
+    xs, ldx = _feature_rows(x, "x")
+    n, D = xs.shape
+    if (sum.dtype != torch.float64 or outer.dtype != torch.float64 or tuple(sum.shape) != (D,) or tuple(outer.shape) != (D, D)
+            or not sum.is_contiguous() or not outer.is_contiguous()):
+        raise TgsrError("feat_moments_add: sum float64 [%d] and outer float64 [%d, %d], dense, expected; got %s %s and %s %s"
+                        % (D, D, D, sum.dtype, tuple(sum.shape), outer.dtype, tuple(outer.shape)))
+    rc = _lib.lib().tgsr_feat_moments_add(_p(xs), n, D, ldx, _p(sum), _p(outer), _stream())
+    check(rc, "tgsr_feat_moments_add")
+
+
+def check_subset_table(table: torch.Tensor, n: int, name: str = "table") -> torch.Tensor:
+    """The host check of a subset table: int [S >= 1, m >= 2] with entries in [0, n).  Returns it as a contiguous int32 host
+    tensor or raises TgsrError.  Touches no device."""
+    if table.is_cuda:
+        raise TgsrError("check_subset_table reads a host tensor (a device table is taken as it is)")
+    if table.dtype not in (torch.int32, torch.int64) or table.dim() != 2 or table.shape[0] < 1 or table.shape[1] < 2:
+        raise TgsrError("%s must be an int32 / int64 [S >= 1, m >= 2] tensor, got %s %s" % (name, table.dtype, tuple(table.shape)))
+    lo, hi = int(table.min()), int(table.max())
+    if lo < 0 or hi >= n:
+        raise TgsrError("%s entries must be in [0, %d), got [%d, %d]" % (name, n, lo, hi))
+    return table.to(torch.int32).contiguous()
+
+
+def _subset_table(table, n, name, dev):
+    if not table.is_cuda:
+        return check_subset_table(table, n, name).to(dev)
+    if table.dtype != torch.int32 or table.dim() != 2 or table.shape[0] < 1 or table.shape[1] < 2:
+        raise TgsrError("a device %s must be an int32 [S >= 1, m >= 2] tensor, got %s %s" % (name, table.dtype, tuple(table.shape)))
+    return table.contiguous()
+
+
+def poly_mmd_sums(x: torch.Tensor, y: torch.Tensor, ix: torch.Tensor, iy: torch.Tensor) -> torch.Tensor:
+    """The three kernel sums of KID for S subsets of m rows (tgsr_poly_mmd_sums): out float64 [S, 3] = (sum_{i != j} k(x_i, x_j),
+    sum_{i != j} k(y_i, y_j), sum_{i, j} k(x_i, y_j)) over the rows ix[s] of x and iy[s] of y, k(a, b) = (<a, b> / D + 1)^3 in fp64.
+    x float32 [nx, D], y float32 [ny, D]; ix, iy int [S, m] (host: checked to lie in [0, nx) / [0, ny), then uploaded; device: int32,
+    taken as they are - the kernel scores an entry outside the set as a row of zeros)."""
+    _need_hip(x, y, ix if ix.is_cuda else None, iy if iy.is_cuda else None)
+    xs, ldx = _feature_rows(x, "x")
+    ys, ldy = _feature_rows(y, "y")
+    (nx, D), ny = xs.shape, ys.shape[0]
+    if ys.shape[1] != D:
+        raise TgsrError("poly_mmd_sums: x %s and y %s differ in their feature width" % (tuple(xs.shape), tuple(ys.shape)))
+    tx, ty = _subset_table(ix, nx, "ix", xs.device), _subset_table(iy, ny, "iy", xs.device)
+    if tuple(tx.shape) != tuple(ty.shape):
+        raise TgsrError("poly_mmd_sums: ix %s and iy %s differ in shape" % (tuple(tx.shape), tuple(ty.shape)))
+    S, m = tx.shape
+    L = _lib.lib()
+    ws = L.tgsr_poly_mmd_ws_elems(S, m)
+    if ws < 1:
+        raise TgsrError("poly_mmd_sums: %d subsets of %d rows refused" % (S, m))
+    work = torch.empty(ws, dtype=torch.float64, device=xs.device)
+    out = torch.empty(S, 3, dtype=torch.float64, device=xs.device)
+    rc = L.tgsr_poly_mmd_sums(_p(xs), nx, ldx, _p(ys), ny, ldy, _p(tx), _p(ty), S, m, D, _p(work), _p(out), _stream())
+    check(rc, "tgsr_poly_mmd_sums")
+    return out
+
+
 # ----------------------------------------------------------------------------------------- CNN_ENCODER heads
 CONV1X1_GCONV = os.environ.get("TGSR_CONV1X1_GCONV", "1") != "0"
 

@@ -185,6 +185,22 @@ class SRPipeline:
                 res[name] = [metrics.image_scores(im.contiguous(), hr.contiguous(), shave) for im, hr in zip(imgs, hr_pyramid)]
         return res
 
+    def realism(self, out, hr, image_encoder, moments=None):
+        """The distribution side of scoring, for callers without a trainer: the finest `fine` image of a forward's outputs and the
+        ground-truth image `hr` (float32 in [-1, 1] or uint8, the finest scale) go through `image_encoder.run_trunk`, and the two
+        pooled [B, 2048] features are added to the pair of featdist.FeatureMoments `moments` = (outputs, ground truth) - a new pair
+        on this pipeline's device without one.  One launch per side, no synchronisation.  Returns the pair; after the last batch
+        featdist.frechet_distance(*pair) is the Frechet distance (tgsr_amd.featdist states the feature space)."""
+        from . import featdist
+        with torch.cuda.device(self.device), torch.no_grad():
+            hr = hr if hr.dtype == torch.float32 else ops.u8_normalize(hr)
+            pooled = [image_encoder.run_trunk(img)[1] for img in (out["fine"][-1], hr)]
+            if moments is None:
+                moments = tuple(featdist.FeatureMoments(p.shape[1], self.device) for p in pooled)
+            for mom, p in zip(moments, pooled):
+                mom.add(p)
+        return moments
+
     def load_state_dicts(self, sd_E=None, sd_GL=None, sd_GH=None):
         """strict for E and GL; the x8 GH tolerates only a missing `a` (never saved by the reference, model.py:246-248);
         the x16 GH registers `a` as a parameter (models16.py:126) and loads it.  The weight-map forms load their maps
