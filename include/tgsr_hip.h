@@ -915,6 +915,29 @@ int tgsr_sr_metrics(const void* sr, int sr_f32, const void* hr, int hr_f32, int 
 int tgsr_rgb_to_y_u8(const uint8_t* rgb, int B, int H, int W, uint8_t* y, void* stream);
 
 /*
+ * No-reference image quality (csrc/tgsr_niqe.hip): the block features of NIQE (Mittal, Soundararajan and Bovik 2013) as MATLAB's
+ * niqe / computefeature and BasicSR's calculate_niqe define them; tgsr_amd/niqe.py fits the pristine model and scores.  The head
+ * of the kernel file and DESIGN.md 3.17 state the arithmetic; everything is fp64.  Evaluation only, no backward.
+ *   img: dense NCHW [B][3][H][W], float32 (is_f32 != 0: quantised in the kernel by tgsr_to_uint8's rule) or uint8; the plane is
+ *   the Y of tgsr_sr_metrics.  shave >= 0 pixels leave every border, the rest is cropped at the top-left to whole 96 x 96 blocks:
+ *   nblk = floor((H - 2 shave) / 96) floor((W - 2 shave) / 96), row-major.
+ *   gam, r_gam: fp64 [n_gam] ON THE DEVICE - the shape grid of the generalised Gaussian fit (np.arange(0.2, 10.001, 0.001), numpy's
+ *   own values) and r_gam[k] = G(2 / gam[k])^2 / (G(1 / gam[k]) G(3 / gam[k])), strictly increasing; the fit takes
+ *   argmin_k (r_gam[k] - rn)^2 by a binary search and one neighbour comparison, the lower index on a tie, index 0 for a NaN rn.
+ *   feats: fp64 [B][nblk][36], scale 1 first; per scale (alpha, (beta_l + beta_r) / 2) of the MSCN block, then for the shifts
+ *   (0,1), (1,0), (1,1), (1,-1) (alpha, (beta_r - beta_l) G(2 / alpha) / G(1 / alpha), beta_l, beta_r) of the block times its circular
+ *   shift.  sharp: fp64 [B][nblk], the mean of the scale-1 local deviation sigma over the block (the model fit selects blocks by it).
+ *   A block without a negative or without a positive element, or with mean(x^2) = 0, gives NaN by IEEE arithmetic (alpha is then
+ *   gam[0]); nothing traps.  ws: tgsr_niqe_ws_elems(...) float64 (the moments of every (image, block, scale); 0 = a shape the
+ *   entry refuses).  Two launches on `stream`, no atomics, no host synchronisation: capturable, and the same bits on every run.
+ * TGSR_EINVAL without launching for a NULL pointer, B < 1 (or > 65535), shave < 0, n_gam < 1 or fewer than 96 pixels on a side after
+ * shaving.
+ */
+int64_t tgsr_niqe_ws_elems(int B, int H, int W, int shave);
+int tgsr_niqe_features(const void* img, int is_f32, int B, int H, int W, int shave, const double* gam, const double* r_gam, int n_gam,
+                       double* ws, double* feats, double* sharp, void* stream);
+
+/*
  * Attention panels (csrc/tgsr_attnviz.hip): one tile per caption word, the word's attention map thresholded, expanded, blurred,
  * stretched to bytes and pasted over the image - build_super_imagesall / build_super_images2 (miscc/utils.py:202-451) on the
  * device.  The arithmetic is stated in tgsr_amd/attnviz.py and DESIGN.md 3.12.

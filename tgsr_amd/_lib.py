@@ -178,6 +178,8 @@ SIGNATURES = {
     "tgsr_sr_metrics_ws_elems": (_i64, [_i, _i, _i, _i]),
     "tgsr_sr_metrics": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     "tgsr_rgb_to_y_u8": (_i, [_vp, _i, _i, _i, _vp, _vp]),
+    "tgsr_niqe_ws_elems": (_i64, [_i, _i, _i, _i]),
+    "tgsr_niqe_features": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
     "tgsr_attn_panels_ws_elems": (_i64, [_i, _i, _i, _i, _i]),
     "tgsr_attn_panels": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "tgsr_attn_confidence": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp]),

@@ -13,6 +13,7 @@
 // the windows centred in the tile) into the caller's workspace; sr_metrics_finish_kernel adds a image's tiles in tile order.
 // No atomics, every reduction in a fixed order: the same bits on every run, on any stream, inside a captured graph.
 #include "tgsr_common.h"
+#include "tgsr_y_plane.h"
 
 namespace tgsr {
 
@@ -24,27 +25,6 @@ constexpr int kME = kMT + 2 * kMR;      // tile + halo edge
 struct GaussTaps {
   double g[kMW];
 };
-
-__device__ __forceinline__ uint8_t quantise_u8(float v) {
-  const float t = __fmul_rn(__fadd_rn(v, 1.0f), 127.5f);
-  return (uint8_t)(int)rintf(fminf(255.f, fmaxf(0.f, t)));
-}
-
-// The reference's rgb2y on one pixel (see the head of the file); every operation is rounded on its own.
-__device__ __forceinline__ uint8_t y_of_rgb(uint8_t r, uint8_t g, uint8_t b) {
-  const float fr = __fdiv_rn((float)r, 255.0f), fg = __fdiv_rn((float)g, 255.0f), fb = __fdiv_rn((float)b, 255.0f);
-  double y = __dmul_rn((double)fr, 65.481 / 255.0);
-  y = __dadd_rn(y, __dmul_rn((double)fg, 128.553 / 255.0));
-  y = __dadd_rn(y, __dmul_rn((double)fb, 24.966 / 255.0));
-  y = __dadd_rn(y, 16 / 255.0);
-  return (uint8_t)(int)__dadd_rn(__dmul_rn(y, 255.0), 0.5);
-}
-
-template <bool F32>
-__device__ __forceinline__ uint8_t load_u8(const void* __restrict__ p, int64_t i) {
-  if (F32) return quantise_u8(static_cast<const float*>(p)[i]);
-  return static_cast<const uint8_t*>(p)[i];
-}
 
 template <bool SR_F32, bool HR_F32>
 __global__ __launch_bounds__(256) void sr_metrics_tile_kernel(const void* __restrict__ sr, const void* __restrict__ hr, int H, int W,

@@ -614,6 +614,16 @@ sr_metrics = _define("sr_metrics(Tensor sr, Tensor hr, int shave=0) -> Tensor", 
 rgb_to_y = _define("rgb_to_y(Tensor rgb) -> Tensor", lambda rgb: ops.rgb_to_y(rgb),
                    lambda rgb: rgb.new_empty(rgb.shape[0], rgb.shape[2], rgb.shape[3], dtype=torch.uint8))
 
+
+# no-reference image quality (tgsr_amd.niqe reads it): (feats float64 [B, nblk, 36], sharp float64 [B, nblk]) over the 96 x 96 blocks
+def _niqe_features_fake(img, shave=0):
+    nblk = ((img.shape[2] - 2 * shave) // ops.NIQE_BLOCK) * ((img.shape[3] - 2 * shave) // ops.NIQE_BLOCK)
+    return (img.new_empty((img.shape[0], nblk, 36), dtype=torch.float64), img.new_empty((img.shape[0], nblk), dtype=torch.float64))
+
+
+niqe_features = _define("niqe_features(Tensor img, int shave=0) -> (Tensor, Tensor)", lambda img, shave=0: ops.niqe_features(img, shave),
+                        _niqe_features_fake)
+
 # the objectives that read the generator's word-attention maps (miscc.losses.weight_MSE / words_reweight_loss): cap_lens is an int32
 # DEVICE tensor; weight_mse returns (term [], wmax [B, h, w], widx uint8 [B, h, w], wlast [B, 1, H, W] or [0]); autograd.WeightMSE
 # is the differentiable form over weight_mse / weight_mse_bwd (absent gradients come back as [0])

@@ -2264,6 +2264,52 @@ def rgb_to_y(rgb: torch.Tensor) -> torch.Tensor:
     return out
 
 
+NIQE_BLOCK = 96
+_NIQE_TABLE = {}          # device -> (gam, r_gam) float64 tensors there
+
+
+def niqe_gamma_table():
+    """(gam, r_gam) as float64 numpy arrays: gam = np.arange(0.2, 10.001, 0.001) (9801 entries, numpy's own values) and
+    r_gam = G(2 / gam)^2 / (G(1 / gam) G(3 / gam)), through lgamma in fp64 - strictly increasing, smallest step 1.7e-6."""
+    import math
+    import numpy as np
+    gam = np.arange(0.2, 10.001, 0.001)
+    r_gam = np.array([math.exp(2.0 * math.lgamma(2.0 / g) - math.lgamma(1.0 / g) - math.lgamma(3.0 / g)) for g in gam.tolist()])
+    return gam, r_gam
+
+
+def niqe_table_on(device):
+    """The table on `device` (a tensor's own), built on the host and uploaded once per device (before any capture: the first call
+    is eager)."""
+    if device not in _NIQE_TABLE:
+        _NIQE_TABLE[device] = tuple(torch.from_numpy(a).to(device) for a in niqe_gamma_table())
+    return _NIQE_TABLE[device]
+
+
+def niqe_features(img: torch.Tensor, shave: int = 0) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(feats float64 [B, nblk, 36], sharp float64 [B, nblk]) of `img`, uint8 NCHW or float32 NCHW in [-1, 1] (quantised in the kernel
+    like `to_uint8`): the NIQE features and the sharpness of every 96 x 96 block of the Y plane (tgsr_niqe_features; tgsr_amd.niqe
+    states the definition).  `shave` pixels leave every border first; fewer than 96 on a side afterwards is a ValueError."""
+    _need_hip(img)
+    img = _metrics_image(img, "img", (torch.float32, torch.uint8))
+    shave = int(shave)
+    B, _, H, W = img.shape
+    if shave < 0 or H - 2 * shave < NIQE_BLOCK or W - 2 * shave < NIQE_BLOCK:
+        raise ValueError("niqe_features: %d x %d images shaved by %d leave a crop under %d x %d" % (H, W, shave, NIQE_BLOCK, NIQE_BLOCK))
+    nblk = ((H - 2 * shave) // NIQE_BLOCK) * ((W - 2 * shave) // NIQE_BLOCK)
+    L = _lib.lib()
+    n_ws = L.tgsr_niqe_ws_elems(B, H, W, shave)
+    if n_ws < 1:
+        raise TgsrError("niqe_features: %d images of %d x %d shaved by %d refused" % (B, H, W, shave))
+    gam, r_gam = niqe_table_on(img.device)
+    ws = torch.empty(n_ws, dtype=torch.float64, device=img.device)
+    feats = torch.empty(B, nblk, 36, dtype=torch.float64, device=img.device)
+    sharp = torch.empty(B, nblk, dtype=torch.float64, device=img.device)
+    check(L.tgsr_niqe_features(_p(img), int(img.dtype == torch.float32), B, H, W, shave, _p(gam), _p(r_gam), gam.numel(), _p(ws),
+                               _p(feats), _p(sharp), _stream()), "tgsr_niqe_features")
+    return feats, sharp
+
+
 # ----------------------------------------------------------------------------------------- attention panels
 ATTN_MAX_SIDE, ATTN_MAX_TILE, ATTN_MAX_WORDS = 128, 512, 64
 

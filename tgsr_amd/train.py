@@ -24,7 +24,7 @@ import numpy as np
 import torch
 import torch.distributed as dist
 
-from . import autograd, featdist, metrics, model, ops, parallel, retrieval
+from . import autograd, featdist, metrics, model, niqe as niqe_mod, ops, parallel, retrieval
 from .miscc import losses
 from .miscc.config import cfg
 from .miscc.utils import copy_G_params, load_params  # noqa: F401  (miscc/utils.py:467-474: the generator EMA helpers)
@@ -876,7 +876,7 @@ class SRTrainer:
 
     @torch.no_grad()
     def evaluate(self, batches, ema=True, shave=0, max_batches=None, r_precision=None, generator=None, ensemble=1, fid=None,
-                 kid=None):
+                 kid=None, niqe=None):
         """Score a validation set: `batches` yields (captions, cap_lens, LR, LRb, hr_pyramid); the generators run in eval mode
         (SRPipeline.from_modules over this trainer's modules, no copies) with the EMA weights (`ema`, the ones `snapshot` saves by
         default) or the current ones, and every output scale is scored against hr_pyramid[k] on the device (tgsr_amd.metrics:
@@ -900,7 +900,15 @@ class SRTrainer:
         "kid": featdist.kernel_distance's result (subsets drawn from `generator`).  With `r_precision` as well the SR image is walked
         once: run_trunk, then heads.
         Data parallel: the moments are all-reduced, so every rank returns the same "fid"; "kid" scores the calling rank's items only,
-        as "r_precision" does."""
+        as "r_precision" does.
+        `niqe` (default None: nothing below happens) asks how natural each image looks on its own (tgsr_amd.niqe states the
+        definition; lower is better; `shave` applies; the finest scale needs 96 pixels on a side after it).  niqe=<a NIQEModel or the
+        path of one>: the finest `fine` image and the finest ground-truth image of every batch are scored against it.  niqe=True: the
+        model is fitted from the ground-truth images seen - the block features of both sides are kept (36 doubles per block), the
+        fit and the scores happen at the end.  The dict gains "niqe": {"fine": [N], "hr": [N], "mean": {"fine", "hr"}, "n": N} - the
+        ground truth's own score is the row a table prints beside the method's; an image with fewer than two finite blocks scores
+        NaN, and so does a mean over it.  Data parallel: the rows are gathered in rank order, and with niqe=True the fit's moments
+        are all-reduced first, so every rank scores against the same model."""
         if getattr(self, "_eval_pipe", None) is None:
             self._eval_pipe = SRPipeline.from_modules(self.text_encoder, self.netGL, self.netGH, device=self.device)
         if r_precision is not None and self.image_encoder is None:
@@ -914,6 +922,12 @@ class SRTrainer:
             raise ValueError("evaluate(fid=%r, kid=%r) needs the trainer's image_encoder" % (fid, kid))
         if kid is not None and not (isinstance(kid, dict) and set(kid) <= {"subsets", "subset_size"}):
             raise ValueError("evaluate: kid is True or a dict of subsets / subset_size, got %r" % (kid,))
+        niqe = None if niqe is False else niqe
+        niqe_model, niqe_seen = None, {"fine": [], "hr": []}
+        if niqe is not None and niqe is not True:
+            if not isinstance(niqe, (niqe_mod.NIQEModel, str, os.PathLike)):
+                raise ValueError("evaluate: niqe is True, a NIQEModel or the path of one, got %r" % (niqe,))
+            niqe_model = niqe if isinstance(niqe, niqe_mod.NIQEModel) else niqe_mod.NIQEModel.load(niqe, self.device)
         mom_sr = mom_gt = bank_sr = bank_gt = None
         if fid is not None and fid is not True:                     # the two accumulated sets take their width from the first batch
             mom_gt = fid if isinstance(fid, featdist.FeatureMoments) else featdist.FeatureMoments.load(os.fspath(fid), self.device)
@@ -955,6 +969,9 @@ class SRTrainer:
                     seen["regions"].append(feats); seen["codes"].append(code); seen["words"].append(words_embs); seen["sents"].append(sent_emb)
                     seen["lens"] += [int(v) for v in (cap_lens.tolist() if torch.is_tensor(cap_lens) else cap_lens)]
                     seen["class_ids"] += [int(v) for v in (class_ids.tolist() if torch.is_tensor(class_ids) else class_ids)]
+                if niqe is not None:
+                    niqe_seen["fine"].append(niqe_mod.niqe_features(out["fine"][-1], shave))
+                    niqe_seen["hr"].append(niqe_mod.niqe_features(hr_pyramid[-1], shave))
                 nscales = len(hr_pyramid)
                 for name in ("fine", "fake"):
                     if len(out[name]) != nscales:
@@ -988,6 +1005,20 @@ class SRTrainer:
                     scores["fid"] = {"fine": featdist.frechet_distance(mom_sr, mom_gt), "n": mom_sr.n}
                 if kid is not None:
                     scores["kid"] = featdist.kernel_distance(bank_sr, bank_gt, generator=generator, **kid)
+        if niqe is not None:
+            with torch.cuda.device(self.device):
+                if niqe_model is None:
+                    niqe_model = niqe_mod.NIQEModel(device=self.device)
+                    for feats, sharp in niqe_seen["hr"]:
+                        niqe_model.add(feats, sharp)
+                    if dp_world() > 1:
+                        niqe_model.all_reduce()
+                rows = {k: torch.cat([niqe_model.score_features(f) for f, _s in v]).cpu().numpy() for k, v in niqe_seen.items()}
+            if dp_world() > 1:
+                every = [None] * dist.get_world_size()
+                dist.all_gather_object(every, rows)
+                rows = {k: np.concatenate([r[k] for r in every]) for k in rows}
+            scores["niqe"] = dict(rows, mean={k: float(np.mean(v)) for k, v in rows.items()}, n=int(rows["fine"].shape[0]))
         return scores
 
     def snapshot_due(self, epoch, max_epoch=None):

@@ -201,6 +201,14 @@ class SRPipeline:
                 mom.add(p)
         return moments
 
+    def niqe(self, out, model, shave=0):
+        """The no-reference side of scoring: the NIQE score (tgsr_amd.niqe, lower is better) of the finest `fine` image of a
+        forward's outputs ([B, 3, H, W]) or of an `upscale` result ([3, H, W]; float32 or out="u8" bytes) against the pristine model
+        `model` (a niqe.NIQEModel): float64 [B] on the device, no synchronisation.  The image needs 96 pixels on a side after `shave`."""
+        img = out["fine"][-1]
+        with torch.cuda.device(self.device):
+            return model.score(img[None] if img.dim() == 3 else img, shave)
+
     def load_state_dicts(self, sd_E=None, sd_GL=None, sd_GH=None):
         """strict for E and GL; the x8 GH tolerates only a missing `a` (never saved by the reference, model.py:246-248);
         the x16 GH registers `a` as a parameter (models16.py:126) and loads it.  The weight-map forms load their maps
