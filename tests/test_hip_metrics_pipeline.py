@@ -209,6 +209,70 @@ def test_evaluate_equals_a_fresh_pipeline_on_the_snapshot(ema, tmp_path, cfg_fac
                 assert res[name][k]["mean"][key] == float(np.mean(res[name][k][key]))
 
 
+def _same_entry(a, b, path):
+    """Arrays and tensors element for element (NaNs in the same places), everything else ==."""
+    assert type(a) is type(b), path
+    if isinstance(a, dict):
+        assert list(a) == list(b), path
+        for k in a:
+            _same_entry(a[k], b[k], path + (k,))
+    elif isinstance(a, list):
+        assert len(a) == len(b), path
+        for i, (x, y) in enumerate(zip(a, b)):
+            _same_entry(x, y, path + (i,))
+    elif torch.is_tensor(a):
+        assert torch.equal(a, b), path
+    elif isinstance(a, np.ndarray):
+        assert a.dtype == b.dtype and np.array_equal(a, b, equal_nan=True), path
+    else:
+        assert a == b or (isinstance(a, float) and np.isnan(a) and np.isnan(b)), (path, a, b)
+
+
+def test_evaluate_with_every_score_is_one_call_per_score(cfg_face):
+    """One call with r_precision, fid, kid and niqe returns, entry by entry, what the plain call and the four calls with one of
+    them each return, and leaves the trainer as it was.  LR 32 gives 64 / 128 / 256: the finest scale has NIQE's 96 pixels.  An
+    untrained output may have no finite NIQE block (its rows are then NaN in both calls); the ground truth's rows are finite."""
+    from test_hip_featdist import _Encoder
+    from tgsr_amd import retrieval, train
+    cfg_face.TREE.BASE_SIZE = 32
+    NB, B, K, SEED = 2, 4, 3, 1
+    kid = {"subsets": 4, "subset_size": 6}
+    torch.manual_seed(3)
+    enc = _Encoder().to(DEV).eval()
+    for p in enc.parameters():
+        p.requires_grad = False
+    ids = [[B * k + i for i in range(B)] for k in range(NB)]
+
+    def batches(with_ids=False):
+        for k, b in enumerate(_val_batches(NB, B)):
+            yield b + (ids[k],) if with_ids else b
+    torch.manual_seed(7)
+    tr = train.SRTrainer(41, device=DEV, image_encoder=enc)
+    state = [p.detach().clone() for p in tr.params] + [b.detach().clone() for m in (tr.netGL, tr.netGH) for b in m.buffers()]
+    every = tr.evaluate(batches(True), shave=2, r_precision=K, fid=True, kid=kid, niqe=True,
+                        generator=torch.Generator().manual_seed(SEED))
+    assert list(every) == ["fine", "fake", "r_precision", "fid", "kid", "niqe"] and enc.trunk_calls == 2 * NB
+    after = [p.detach() for p in tr.params] + [b.detach() for m in (tr.netGL, tr.netGH) for b in m.buffers()]
+    assert len(state) == len(after) and all(torch.equal(a, b) for a, b in zip(state, after))
+    # `generator` is drawn from by r_precision's candidate table first, then by kid's subset tables: the call with kid alone gets
+    # a generator of the same seed that has already given that candidate table, so its subset tables are the same ones
+    past_candidates = torch.Generator().manual_seed(SEED)
+    retrieval.sample_candidates(sum(ids, []), K, past_candidates)
+    alone = {"plain": tr.evaluate(batches(), shave=2),
+             "r_precision": tr.evaluate(batches(True), shave=2, r_precision=K, generator=torch.Generator().manual_seed(SEED)),
+             "fid": tr.evaluate(batches(), shave=2, fid=True),
+             "kid": tr.evaluate(batches(), shave=2, kid=kid, generator=past_candidates),
+             "niqe": tr.evaluate(batches(), shave=2, niqe=True)}
+    assert every["fine"][0]["n"] == NB * B and every["fid"]["n"] == NB * B and every["niqe"]["n"] == NB * B
+    assert every["kid"]["per_subset"].shape == (4,) and np.isfinite(every["niqe"]["hr"]).all()
+    for name, res in alone.items():
+        assert list(res) == ["fine", "fake"] + ([] if name == "plain" else [name]), name
+        for key in res:
+            _same_entry(every[key], res[key], (name, key))
+    after = [p.detach() for p in tr.params] + [b.detach() for m in (tr.netGL, tr.netGH) for b in m.buffers()]
+    assert all(torch.equal(a, b) for a, b in zip(state, after))
+
+
 def test_resume_in_place_then_replay_equals_eager(tmp_path, cfg_face):
     from tgsr_amd import train
     src = _trainer(False, False, seed=11)

@@ -14,15 +14,19 @@ differs in three pooling layers and in its weights; that variant is not built he
   kernel_distance    the unbiased MMD^2 under k(a, b) = (<a, b> / D + 1)^3 over random subsets (torch.ops.tgsr.poly_mmd_sums: one
                      call for all subsets), mean and standard deviation over the subsets
   FeatureBank        the feature batches kernel_distance reads, concatenated once
+  RealismScores      what SRTrainer.evaluate(fid=, kid=) accumulates batch by batch and reports at the end
 
 CPU tensors run the same arithmetic in torch fp64 (host tests, the gloo group); device tensors run the kernels of
 csrc/tgsr_featdist.hip - a missing library is an error, never a fall-back.
 """
+import os
+
 import numpy as np
 import torch
 import torch.distributed as dist
 
 from . import custom_ops as C
+from . import ops
 
 _SOLVER = {}          # device -> the device the symmetric eigensolver runs on
 
@@ -213,3 +217,64 @@ def kernel_distance(fx, fy, subsets=100, subset_size=1000, generator=None):
     per = sums[:, 0] / (m * (m - 1.0)) + sums[:, 1] / (m * (m - 1.0)) - 2.0 * sums[:, 2] / (float(m) * m)
     mean, std = torch.stack([per.mean(), per.std(unbiased=False)]).tolist()          # the synchronisation
     return {"mean": mean, "std": std, "per_subset": per}
+
+
+# ----------------------------------------------------------------------------------------- what a validation loop accumulates
+def pooled_of_truth(image_encoder, hr):
+    """The pooled features of a ground-truth batch `hr` (float32 in [-1, 1], or uint8: normalised first): one trunk walk."""
+    return image_encoder.run_trunk(hr if hr.dtype == torch.float32 else ops.u8_normalize(hr))[1]
+
+
+def moments_add(moments, pooled, device):
+    """`pooled` added to `moments` - a new FeatureMoments of the batch's width on `device` without one.  Returns the moments."""
+    return (FeatureMoments(pooled.shape[1], device) if moments is None else moments).add(pooled)
+
+
+def realism_args(fid, kid):
+    """(fid, kid) as RealismScores reads them: False is None (not asked for), kid=True is {} (kernel_distance's defaults)."""
+    return None if fid is False else fid, None if kid is False else ({} if kid is True else kid)
+
+
+class RealismScores:
+    """SRTrainer.evaluate's `fid` / `kid`: `add` per batch (one launch per moment set, no synchronisation), `result` once at the end.
+    fid=True: the Frechet distance between the outputs' moments and the ground truth's, both accumulated here.  fid=<a
+    FeatureMoments or the path of a saved one>: the ground-truth side comes from those statistics.  kid=True or {"subsets": ...,
+    "subset_size": ...}: both feature banks are kept for kernel_distance.  `needs_truth` says whether `add` wants the ground truth's
+    features - with saved statistics and no `kid` it does not, and the caller skips that trunk walk."""
+
+    def __init__(self, fid=None, kid=None, device="cuda"):
+        self.fid, self.kid = realism_args(fid, kid)
+        self.device = torch.device(device)
+        if self.kid is not None and not (isinstance(self.kid, dict) and set(self.kid) <= {"subsets", "subset_size"}):
+            raise ValueError("evaluate: kid is True or a dict of subsets / subset_size, got %r" % (self.kid,))
+        self.mom_sr = self.mom_gt = self.bank_sr = self.bank_gt = None
+        if self.fid is not None and self.fid is not True:
+            self.mom_gt = self.fid if isinstance(self.fid, FeatureMoments) else FeatureMoments.load(os.fspath(self.fid), self.device)
+        if self.kid is not None:
+            self.bank_sr, self.bank_gt = FeatureBank(), FeatureBank()
+        self.needs_truth = self.fid is True or self.kid is not None
+
+    def add(self, pooled_sr, pooled_gt=None):
+        """The pooled features [B, D] of a batch of outputs and - `needs_truth` - of its ground truth.  The moment sets take their
+        width from the first batch."""
+        if self.fid is not None:
+            self.mom_sr = moments_add(self.mom_sr, pooled_sr, self.device)
+        if self.fid is True:
+            self.mom_gt = moments_add(self.mom_gt, pooled_gt, self.device)
+        if self.kid is not None:
+            self.bank_sr.add(pooled_sr)
+            self.bank_gt.add(pooled_gt)
+
+    def result(self, generator=None):
+        """{"fid": {"fine": the Frechet distance, "n": the images seen}} and / or {"kid": kernel_distance's result, subsets drawn
+        from `generator`}, as asked for.  Data parallel: the accumulated moments are all-reduced first (call it once, on every
+        rank), so every rank returns the same "fid"; "kid" scores the calling rank's items only."""
+        out = {}
+        if self.fid is not None:
+            self.mom_sr.all_reduce()
+            if self.fid is True:
+                self.mom_gt.all_reduce()
+            out["fid"] = {"fine": frechet_distance(self.mom_sr, self.mom_gt), "n": self.mom_sr.n}
+        if self.kid is not None:
+            out["kid"] = kernel_distance(self.bank_sr, self.bank_gt, generator=generator, **self.kid)
+        return out

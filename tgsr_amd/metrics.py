@@ -11,6 +11,7 @@ import numpy as np
 import torch
 
 from . import custom_ops as _C  # noqa: F401   (registers torch.ops.tgsr.*)
+from .parallel import dp_world, gather_rows
 
 WINDOW = 11
 KEYS = ("psnr", "rmse", "psnr_y", "rmse_y", "ssim_y")
@@ -95,6 +96,19 @@ class ScoreBook:
             sc["mean"] = {k: float(np.mean(sc[k])) if sc["n"] else float("nan") for k in KEYS}
             out[scale] = sc
         return out
+
+    def all_gather(self):
+        """The book of every rank's rows, merged in rank order: a host-side book, the same on every rank (one all_gather_object;
+        synchronises).  Without an initialised group: this book itself."""
+        if dp_world() == 1:
+            return self
+        rows, sizes = gather_rows({s: self.rows(s) for s in self.scales()}, self._size)
+        size = {}
+        for rank_sizes in sizes:
+            for scale, hw in rank_sizes.items():
+                if size.setdefault(scale, hw) != hw:
+                    raise ValueError("ScoreBook.all_gather: scale %r holds %s and %s images" % (scale, size[scale], hw))
+        return ScoreBook.from_rows(rows, size, self.shave)
 
     @classmethod
     def from_rows(cls, rows_by_scale, sizes, shave=0):

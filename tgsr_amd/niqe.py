@@ -34,6 +34,7 @@ import torch.distributed as dist
 from . import custom_ops as C
 from . import ops
 from .featdist import solver_device
+from .parallel import gather_rows
 
 BLOCK = ops.NIQE_BLOCK
 NFEAT = 36
@@ -293,3 +294,37 @@ class NIQEModel:
         """The NIQE score of every image of `img` [B, 3, H, W] (uint8 or float32 in [-1, 1]) against this model: float64 [B] on the
         image's device, lower is better."""
         return self.score_features(niqe_features(img, shave)[0])
+
+
+class NIQEScores:
+    """SRTrainer.evaluate's `niqe`: `add` per batch (the block features of the output and of its ground truth: 36 doubles per block,
+    two launches per side, no synchronisation), `result` once at the end.  niqe=<a NIQEModel or the path of one>: both sides are
+    scored against it.  niqe=True: the model is fitted from the ground-truth images seen; the fit and the scores happen in `result`,
+    which leaves it in `model`."""
+
+    def __init__(self, niqe=True, shave=0, device="cuda"):
+        self.shave, self.device, self.model = int(shave), torch.device(device), None
+        if niqe is not True:
+            if not isinstance(niqe, (NIQEModel, str, os.PathLike)):
+                raise ValueError("evaluate: niqe is True, a NIQEModel or the path of one, got %r" % (niqe,))
+            self.model = niqe if isinstance(niqe, NIQEModel) else NIQEModel.load(niqe, self.device)
+        self.seen = {"fine": [], "hr": []}
+
+    def add(self, sr, hr):
+        """A batch of outputs and its ground truth, [B, 3, H, W] each: 96 pixels on a side at least after `shave`."""
+        self.seen["fine"].append(niqe_features(sr, self.shave))
+        self.seen["hr"].append(niqe_features(hr, self.shave))
+
+    def result(self):
+        """{"fine": [N], "hr": [N], "mean": {"fine", "hr"}, "n": N}: the ground truth's own score is the row a table prints beside the
+        method's; an image with fewer than two finite blocks scores NaN, and so does a mean over it.  Data parallel (call it once, on
+        every rank): with niqe=True the fit's moments are all-reduced first, so every rank scores against the same model, and the rows
+        are gathered in rank order."""
+        if self.model is None:
+            self.model = NIQEModel(device=self.device)
+            for feats, sharp in self.seen["hr"]:
+                self.model.add(feats, sharp)
+            self.model.all_reduce()
+        rows = {k: torch.cat([self.model.score_features(f) for f, _s in v]).cpu().numpy() for k, v in self.seen.items()}
+        rows, _ = gather_rows(rows)
+        return dict(rows, mean={k: float(np.mean(v)) for k, v in rows.items()}, n=int(rows["fine"].shape[0]))

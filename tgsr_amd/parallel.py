@@ -278,6 +278,19 @@ def dp_world() -> int:
     return dist.get_world_size() if (dist.is_available() and dist.is_initialized()) else 1
 
 
+def gather_rows(rows, meta=None):
+    """Host rows over the ranks: `rows` {key: numpy [n, ...]} -> ({key: the rows of every rank, concatenated in rank order}, [the
+    `meta` of every rank, in rank order]) by ONE all_gather_object; every rank returns the same.  A key some rank lacks takes the
+    rows of those that hold it.  Without an initialised group: (rows, [meta])."""
+    if dp_world() == 1:
+        return rows, [meta]
+    import numpy as np
+    every = [None] * dist.get_world_size()
+    dist.all_gather_object(every, (rows, meta))
+    keys = dict.fromkeys(k for r, _m in every for k in r)
+    return {k: np.concatenate([r[k] for r, _m in every if k in r]) for k in keys}, [m for _r, m in every]
+
+
 class _AllGatherCat(torch.autograd.Function):
     """cat(all_gather(x), 0) whose backward hands every rank the gradient rows of ITS slice.  Correct when every rank goes
     on to evaluate the SAME function of the gathered tensor (the replicated contrastive loss below): rank r's copy of

@@ -39,7 +39,34 @@ def sample_candidates(class_ids, n_candidates=100, generator=None):
     return table
 
 
-def _similarity(mode, regions, codes, words_emb, sent_emb, cap_lens, cand):
+class Gallery:
+    """The items of many batches for ONE gallery: the batches are kept as they come (no copy, no launch, no synchronisation) and
+    concatenated once.  What DAMSMTrainer.evaluate_retrieval and SRTrainer.evaluate(r_precision=) collect."""
+
+    def __init__(self):
+        self.regions, self.codes, self.words, self.sents, self.lens, self.class_ids = [], [], [], [], [], []
+
+    def __len__(self):
+        return len(self.lens)
+
+    def add(self, regions, codes, words_emb, sent_emb, cap_lens, take=None, class_ids=None):
+        """One batch: region features, image codes, word and sentence embeddings, caption lengths (a tensor or a list; kept as
+        ints) and - for sample_candidates - class ids.  `take`: only the first `take` items of the batch."""
+        for held, t in zip((self.regions, self.codes, self.words, self.sents), (regions, codes, words_emb, sent_emb)):
+            held.append(t if take is None else t[:take])
+        for held, v in ((self.lens, cap_lens), (self.class_ids, class_ids)):
+            if v is not None:
+                held += [int(i) for i in (v.tolist() if torch.is_tensor(v) else v)][:take]
+
+    def cat(self):
+        """(regions, codes, words_emb, sent_emb, cap_lens): what r_precision and retrieval_scores take.  Batches may differ in
+        their longest caption: the word axis is zero-padded to the longest."""
+        Tw = max(w.shape[2] for w in self.words)
+        words = [w if w.shape[2] == Tw else torch.nn.functional.pad(w, (0, Tw - w.shape[2])) for w in self.words]
+        return torch.cat(self.regions), torch.cat(self.codes), torch.cat(words), torch.cat(self.sents), self.lens
+
+
+def _similarity(mode,regions, codes, words_emb, sent_emb, cap_lens, cand):
     sm = cfg.TRAIN.SMOOTH
     if mode == "sent":
         return C.sent_gallery(codes, sent_emb, 1e-8, float(sm.GAMMA3), cand)

@@ -24,7 +24,7 @@ import numpy as np
 import torch
 import torch.distributed as dist
 
-from . import autograd, featdist, metrics, model, niqe as niqe_mod, ops, parallel, retrieval
+from . import autograd, featdist, metrics, model, niqe as niqe_mod, parallel, retrieval
 from .miscc import losses
 from .miscc.config import cfg
 from .miscc.utils import copy_G_params, load_params  # noqa: F401  (miscc/utils.py:467-474: the generator EMA helpers)
@@ -885,140 +885,77 @@ class SRTrainer:
         "mean": {...}} over the N images seen.  Afterwards the trainer is exactly as it was (`_eval_weights`).
         ensemble=8 scores the geometric self-ensemble (SRPipeline.self_ensemble: the mean over the eight flips and rotations, the
         "+" rows of an SR table) in place of the plain forward; everything else is unchanged.
-        Data parallel: every rank passes ITS batches; the rows are gathered in rank order and every rank returns the same dict.
-        `r_precision` = K (default None: nothing below happens) asks whether the output is consistent with its caption: the batches
-        then carry `class_ids` as a sixth element, the finest `fine` image of every batch goes through `image_encoder` (required), and
-        the dict gains "r_precision": {"sent": ..., "words": ...} - each the result of retrieval.r_precision over the images seen,
-        against the candidate table sample_candidates(class_ids, K, generator): the own caption and K - 1 captions of other classes.
-        Data parallel: that entry scores the calling rank's items only (region features are not gathered across ranks).
-        `fid` / `kid` (default None: nothing below happens) ask whether the output looks like a real image (tgsr_amd.featdist, which
-        states the feature space: the pooled 2048 of `image_encoder`'s trunk - required).  fid=True: the finest `fine` image and the
-        finest ground-truth image of every batch go through `image_encoder.run_trunk`, only `pooled` is kept and added to two
-        FeatureMoments (one launch each, no synchronisation per batch); the dict gains "fid": {"fine": the Frechet distance, "n": the
-        images seen}.  fid=<a FeatureMoments or the path of a saved one>: the ground-truth side comes from those statistics and its
-        trunk walks are skipped.  kid=True or {"subsets": ..., "subset_size": ...}: both feature banks are kept and the dict gains
-        "kid": featdist.kernel_distance's result (subsets drawn from `generator`).  With `r_precision` as well the SR image is walked
-        once: run_trunk, then heads.
-        Data parallel: the moments are all-reduced, so every rank returns the same "fid"; "kid" scores the calling rank's items only,
-        as "r_precision" does.
-        `niqe` (default None: nothing below happens) asks how natural each image looks on its own (tgsr_amd.niqe states the
-        definition; lower is better; `shave` applies; the finest scale needs 96 pixels on a side after it).  niqe=<a NIQEModel or the
-        path of one>: the finest `fine` image and the finest ground-truth image of every batch are scored against it.  niqe=True: the
-        model is fitted from the ground-truth images seen - the block features of both sides are kept (36 doubles per block), the
-        fit and the scores happen at the end.  The dict gains "niqe": {"fine": [N], "hr": [N], "mean": {"fine", "hr"}, "n": N} - the
-        ground truth's own score is the row a table prints beside the method's; an image with fewer than two finite blocks scores
-        NaN, and so does a mean over it.  Data parallel: the rows are gathered in rank order, and with niqe=True the fit's moments
-        are all-reduced first, so every rank scores against the same model."""
+        Every further score is off by default (None: nothing of it happens), reads the finest `fine` image and the finest
+        ground-truth image of every batch, and is kept by one accumulator, which states the rest:
+        `r_precision` = K - is the output consistent with its caption?  The batches carry `class_ids` as a sixth element, the image
+          goes through `image_encoder` (required); the dict gains "r_precision": {"sent": ..., "words": ...}, each
+          retrieval.r_precision over the images seen (retrieval.Gallery) against sample_candidates(class_ids, K, generator): the own
+          caption and K - 1 captions of other classes.
+        `fid` = True, a FeatureMoments or the path of a saved one, `kid` = True or {"subsets": ..., "subset_size": ...} - does the
+          output look like a real image?  Both images go through `image_encoder.run_trunk` (required; tgsr_amd.featdist states the
+          feature space), only `pooled` is kept; with saved statistics alone the ground truth's walks are skipped, and with
+          `r_precision` as well the SR image is walked once: run_trunk, then heads.  The dict gains "fid": {"fine": the Frechet
+          distance, "n": the images seen} and "kid": featdist.kernel_distance's result, subsets drawn from `generator` after
+          r_precision's candidates (featdist.RealismScores).
+        `niqe` = True (the model is fitted from the ground-truth images seen), a NIQEModel or the path of one - how natural does each
+          image look on its own?  Lower is better; `shave` applies; the finest scale needs 96 pixels on a side after it.  The dict
+          gains "niqe": {"fine": [N], "hr": [N], "mean": {"fine", "hr"}, "n": N} (niqe.NIQEScores).
+        Data parallel: every rank passes ITS batches; the PSNR / SSIM and NIQE rows are gathered in rank order and the moments behind
+        "fid" and niqe=True's fit are all-reduced, so every rank returns the same of those; "r_precision" and "kid" score the
+        calling rank's items only (region features and feature banks are not gathered across ranks)."""
         if getattr(self, "_eval_pipe", None) is None:
             self._eval_pipe = SRPipeline.from_modules(self.text_encoder, self.netGL, self.netGH, device=self.device)
         if r_precision is not None and self.image_encoder is None:
             raise ValueError("evaluate(r_precision=%r) needs the trainer's image_encoder" % (r_precision,))
         if ensemble not in (1, 8):
             raise ValueError("evaluate: ensemble is 1 or 8 (the eight flips and rotations), got %r" % (ensemble,))
-        fid = None if fid is False else fid
-        kid = None if kid is False else ({} if kid is True else kid)
-        realism = fid is not None or kid is not None
-        if realism and self.image_encoder is None:
+        fid, kid = featdist.realism_args(fid, kid)
+        if (fid is not None or kid is not None) and self.image_encoder is None:
             raise ValueError("evaluate(fid=%r, kid=%r) needs the trainer's image_encoder" % (fid, kid))
-        if kid is not None and not (isinstance(kid, dict) and set(kid) <= {"subsets", "subset_size"}):
-            raise ValueError("evaluate: kid is True or a dict of subsets / subset_size, got %r" % (kid,))
-        niqe = None if niqe is False else niqe
-        niqe_model, niqe_seen = None, {"fine": [], "hr": []}
-        if niqe is not None and niqe is not True:
-            if not isinstance(niqe, (niqe_mod.NIQEModel, str, os.PathLike)):
-                raise ValueError("evaluate: niqe is True, a NIQEModel or the path of one, got %r" % (niqe,))
-            niqe_model = niqe if isinstance(niqe, niqe_mod.NIQEModel) else niqe_mod.NIQEModel.load(niqe, self.device)
-        mom_sr = mom_gt = bank_sr = bank_gt = None
-        if fid is not None and fid is not True:                     # the two accumulated sets take their width from the first batch
-            mom_gt = fid if isinstance(fid, featdist.FeatureMoments) else featdist.FeatureMoments.load(os.fspath(fid), self.device)
-        if kid is not None:
-            bank_sr, bank_gt = featdist.FeatureBank(), featdist.FeatureBank()
+        realism = featdist.RealismScores(fid, kid, self.device) if fid is not None or kid is not None else None
+        naturalness = niqe_mod.NIQEScores(niqe, shave, self.device) if niqe is not None and niqe is not False else None
+        gallery = retrieval.Gallery() if r_precision is not None else None
         forward = self._eval_pipe if ensemble == 1 else self._eval_pipe.self_ensemble
         book = metrics.ScoreBook(shave)
-        nscales = 0
-        seen = {"regions": [], "codes": [], "words": [], "sents": [], "lens": [], "class_ids": []}
         with torch.cuda.device(self.device), self._eval_weights(ema):
             for k, batch in enumerate(batches):
-                if r_precision is None:
+                if gallery is None:
                     captions, cap_lens, LR, LRb, hr_pyramid = batch
                 else:
                     captions, cap_lens, LR, LRb, hr_pyramid, class_ids = batch
                 if max_batches is not None and k >= max_batches:
                     break
                 out = forward(captions, cap_lens, LR, LRb)
-                if realism:
-                    trunk_feats, pooled = self.image_encoder.run_trunk(out["fine"][-1])
-                    if fid is not None:
-                        if mom_sr is None:
-                            mom_sr = featdist.FeatureMoments(pooled.shape[1], self.device)
-                        mom_sr.add(pooled)
-                    if kid is not None:
-                        bank_sr.add(pooled)
-                    if fid is True or kid is not None:
-                        hr = hr_pyramid[-1]
-                        _f, pooled_gt = self.image_encoder.run_trunk(hr if hr.dtype == torch.float32 else ops.u8_normalize(hr))
-                        if fid is True:
-                            if mom_gt is None:
-                                mom_gt = featdist.FeatureMoments(pooled_gt.shape[1], self.device)
-                            mom_gt.add(pooled_gt)
-                        if kid is not None:
-                            bank_gt.add(pooled_gt)
-                if r_precision is not None:
+                sr, hr = out["fine"][-1], hr_pyramid[-1]
+                if realism is not None:
+                    trunk_feats, pooled = self.image_encoder.run_trunk(sr)
+                    realism.add(pooled, featdist.pooled_of_truth(self.image_encoder, hr) if realism.needs_truth else None)
+                if gallery is not None:
                     words_embs, sent_emb, _mask = self._text(captions, cap_lens)
-                    feats, code = self.image_encoder.heads(trunk_feats, pooled) if realism else self.image_encoder(out["fine"][-1])
-                    seen["regions"].append(feats); seen["codes"].append(code); seen["words"].append(words_embs); seen["sents"].append(sent_emb)
-                    seen["lens"] += [int(v) for v in (cap_lens.tolist() if torch.is_tensor(cap_lens) else cap_lens)]
-                    seen["class_ids"] += [int(v) for v in (class_ids.tolist() if torch.is_tensor(class_ids) else class_ids)]
-                if niqe is not None:
-                    niqe_seen["fine"].append(niqe_mod.niqe_features(out["fine"][-1], shave))
-                    niqe_seen["hr"].append(niqe_mod.niqe_features(hr_pyramid[-1], shave))
-                nscales = len(hr_pyramid)
+                    feats, code = self.image_encoder.heads(trunk_feats, pooled) if realism is not None else self.image_encoder(sr)
+                    gallery.add(feats, code, words_embs, sent_emb, cap_lens, class_ids=class_ids)
+                if naturalness is not None:
+                    naturalness.add(sr, hr)
                 for name in ("fine", "fake"):
-                    if len(out[name]) != nscales:
-                        raise ValueError("evaluate: %d %s images against %d ground-truth scales" % (len(out[name]), name, nscales))
-                    for i, hr in enumerate(hr_pyramid):
-                        book.add((name, i), out[name][i].contiguous(), hr.contiguous())
-        if dp_world() > 1:
-            mine = ({s: book.rows(s) for s in book.scales()}, dict(book._size))
-            every = [None] * dist.get_world_size()
-            dist.all_gather_object(every, mine)
-            book = metrics.ScoreBook.merge([metrics.ScoreBook.from_rows(r, sizes, shave) for r, sizes in every])
-            nscales = max([i for _n, i in book.scales()], default=-1) + 1
-        res = book.result()
-        if not res:
-            raise ValueError("evaluate: no validation batch")
-        scores = {name: [res[(name, i)] for i in range(nscales)] for name in ("fine", "fake")}
-        if r_precision is not None:
-            cand = retrieval.sample_candidates(seen["class_ids"], int(r_precision), generator)
-            Tw = max(w.shape[2] for w in seen["words"])
-            words = [w if w.shape[2] == Tw else torch.nn.functional.pad(w, (0, Tw - w.shape[2])) for w in seen["words"]]
-            with torch.cuda.device(self.device):
-                feats = [torch.cat(seen[key]) for key in ("regions", "codes")] + [torch.cat(words), torch.cat(seen["sents"])]
-                scores["r_precision"] = {mode: retrieval.r_precision(*feats, seen["lens"], cand, mode=mode) for mode in retrieval.MODES}
-        if realism:
-            with torch.cuda.device(self.device):
-                if fid is not None:
-                    if dp_world() > 1:
-                        mom_sr.all_reduce()
-                        if fid is True:
-                            mom_gt.all_reduce()
-                    scores["fid"] = {"fine": featdist.frechet_distance(mom_sr, mom_gt), "n": mom_sr.n}
-                if kid is not None:
-                    scores["kid"] = featdist.kernel_distance(bank_sr, bank_gt, generator=generator, **kid)
-        if niqe is not None:
-            with torch.cuda.device(self.device):
-                if niqe_model is None:
-                    niqe_model = niqe_mod.NIQEModel(device=self.device)
-                    for feats, sharp in niqe_seen["hr"]:
-                        niqe_model.add(feats, sharp)
-                    if dp_world() > 1:
-                        niqe_model.all_reduce()
-                rows = {k: torch.cat([niqe_model.score_features(f) for f, _s in v]).cpu().numpy() for k, v in niqe_seen.items()}
-            if dp_world() > 1:
-                every = [None] * dist.get_world_size()
-                dist.all_gather_object(every, rows)
-                rows = {k: np.concatenate([r[k] for r in every]) for k in rows}
-            scores["niqe"] = dict(rows, mean={k: float(np.mean(v)) for k, v in rows.items()}, n=int(rows["fine"].shape[0]))
+                    if len(out[name]) != len(hr_pyramid):
+                        raise ValueError("evaluate: %d %s images against %d ground-truth scales"
+                                         % (len(out[name]), name, len(hr_pyramid)))
+                    for i, truth in enumerate(hr_pyramid):
+                        book.add((name, i), out[name][i].contiguous(), truth.contiguous())
+        with torch.cuda.device(self.device):
+            res = book.all_gather().result()
+            if not res:
+                raise ValueError("evaluate: no validation batch")
+            nscales = 1 + max(i for _name, i in res)
+            scores = {name: [res[name, i] for i in range(nscales)] for name in ("fine", "fake")}
+            if gallery is not None:
+                cand = retrieval.sample_candidates(gallery.class_ids, int(r_precision), generator)
+                items = gallery.cat()
+                scores["r_precision"] = {mode: retrieval.r_precision(*items, cand, mode=mode) for mode in retrieval.MODES}
+            if realism is not None:
+                scores.update(realism.result(generator))
+            if naturalness is not None:
+                scores["niqe"] = naturalness.result()
         return scores
 
     def snapshot_due(self, epoch, max_epoch=None):
@@ -1177,10 +1114,10 @@ class DAMSMTrainer:
         the word similarity.  Data parallel: every rank scores the items of ITS batches only (no gather of region features)."""
         self.text_encoder.eval()
         self.image_encoder.eval()
-        regions, codes, words, sents, lens, n = [], [], [], [], [], 0
+        gallery = retrieval.Gallery()
         with torch.cuda.device(self.device):
             for batch in batches:
-                if max_items is not None and n >= max_items:
+                if max_items is not None and len(gallery) >= max_items:
                     break
                 if len(batch) == 4:
                     imgs, captions, cap_lens, _cls = batch
@@ -1188,17 +1125,12 @@ class DAMSMTrainer:
                 else:
                     features, pooled, captions, cap_lens, _cls = batch
                 B = captions.shape[0]
-                take = B if max_items is None else min(B, max_items - n)
                 wf, code = self.image_encoder.heads(features, pooled)
                 we, se = self.text_encoder(captions, cap_lens, self.text_encoder.init_hidden(B))
-                regions.append(wf[:take]); codes.append(code[:take]); words.append(we[:take]); sents.append(se[:take])
-                lens += [int(v) for v in (cap_lens.tolist() if torch.is_tensor(cap_lens) else cap_lens)][:take]
-                n += take
-            if n == 0:
+                gallery.add(wf, code, we, se, cap_lens, take=B if max_items is None else min(B, max_items - len(gallery)))
+            if not len(gallery):
                 raise ValueError("evaluate_retrieval: no validation batch")
-            Tw = max(w.shape[2] for w in words)            # batches may differ in their longest caption: pad the word axis
-            words = [w if w.shape[2] == Tw else torch.nn.functional.pad(w, (0, Tw - w.shape[2])) for w in words]
-            return retrieval.retrieval_scores(torch.cat(regions), torch.cat(codes), torch.cat(words), torch.cat(sents), lens, ks)
+            return retrieval.retrieval_scores(*gallery.cat(), ks)
 
     def snapshot_due(self, epoch, max_epoch=None):
         return snapshot_due(epoch, max_epoch)

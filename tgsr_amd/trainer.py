@@ -193,13 +193,8 @@ class SRPipeline:
         featdist.frechet_distance(*pair) is the Frechet distance (tgsr_amd.featdist states the feature space)."""
         from . import featdist
         with torch.cuda.device(self.device), torch.no_grad():
-            hr = hr if hr.dtype == torch.float32 else ops.u8_normalize(hr)
-            pooled = [image_encoder.run_trunk(img)[1] for img in (out["fine"][-1], hr)]
-            if moments is None:
-                moments = tuple(featdist.FeatureMoments(p.shape[1], self.device) for p in pooled)
-            for mom, p in zip(moments, pooled):
-                mom.add(p)
-        return moments
+            pooled = (image_encoder.run_trunk(out["fine"][-1])[1], featdist.pooled_of_truth(image_encoder, hr))
+            return tuple(featdist.moments_add(m, p, self.device) for m, p in zip(moments or (None, None), pooled))
 
     def niqe(self, out, model, shave=0):
         """The no-reference side of scoring: the NIQE score (tgsr_amd.niqe, lower is better) of the finest `fine` image of a
