@@ -859,12 +859,23 @@ int tgsr_to_uint8(const float* x, uint8_t* out, int64_t n, void* stream);
  *   tgsr_resize_bilinear_u8  transforms.Resize on a PIL image = PIL resize(BILINEAR): horizontal then vertical pass of
  *       a triangle filter in 22-bit fixed point.  hbounds / vbounds: int32 [out][2] = (first input index, tap count);
  *       hcoef / vcoef: int32 [out][hk | vk] taps (the host computes both in double exactly like Pillow's
- *       precompute_coeffs; a pass whose size does not change is skipped and its tables may be NULL).  tmp: N*Hin*Wout
- *       bytes when both passes run.
+ *       precompute_coeffs; a pass whose size does not change is skipped and its tables may be NULL).  tmp: exactly
+ *       N*Hin*Wout bytes when both passes run, unused (may be NULL) otherwise.  With neither pass `out` is a copy of `in`.
+ *       Checked (TGSR_EINVAL, nothing written): in, out non-NULL; N and every size >= 1; the tables of a pass that runs
+ *       non-NULL and its hk | vk >= 1; tmp non-NULL when both passes run; the bytes of `in` and `out` do not overlap, and
+ *       when both passes run those of `tmp` overlap neither.  The caller's duty: the device tables are trusted - for every
+ *       output index, first >= 0, first + count <= the input size of that axis and 0 <= count <= hk | vk; the taps may be
+ *       any int32 (the sum of at most count products 255 x tap must fit int32; the result is clipped to [0, 255]).
  *   tgsr_gaussian_blur_u8    ImageFilter.GaussianBlur(radius): `passes` extended-box-blur passes per axis with integer
  *       radius, centre weight ww and far-pixel weight fw in 24-bit fixed point (radius 2, 3 passes: 1, 4473924, 1677722);
- *       clamped borders.  tmp: N*H*W bytes.  `in` may not alias `out` or `tmp`.
+ *       clamped borders.  tmp: exactly N*H*W bytes.
+ *       Checked (TGSR_EINVAL, nothing written): in, tmp, out non-NULL; N, H, W, passes >= 1; radius >= 0;
+ *       (2 radius + 1) ww + 2 fw <= 2^24 in 64-bit arithmetic (what keeps the kernel's uint32 sum from wrapping; Pillow's
+ *       weights add up to 2^24 or one less) and radius < 2^23; no two of `in`, `tmp`, `out` share a byte.
  *   tgsr_u8_normalize        ToTensor + Normalize(0.5, 0.5): float32 (u8 / 255 - 0.5) / 0.5 (datasets.py:286-288).
+ *       Checked: in, out non-NULL, n >= 1.  out is float32, 4-byte aligned.
+ * The uint8 operands need no alignment: the kernels load and store single bytes, so `in`, `tmp` and `out` may start at any
+ * address.  The int32 tables are 4-byte aligned.
  */
 int tgsr_resize_bilinear_u8(const uint8_t* in, int N, int Hin, int Win, int Hout, int Wout, const int32_t* hbounds,
                             const int32_t* hcoef, int hk, const int32_t* vbounds, const int32_t* vcoef, int vk,

@@ -45,16 +45,35 @@ def resize_coeffs(in_size: int, out_size: int):
     return bounds, ik
 
 
-def _resample_axis(a: np.ndarray, out_size: int, axis: int) -> np.ndarray:
+def resample_axis_tables(a: np.ndarray, bounds: np.ndarray, ik: np.ndarray, axis: int) -> np.ndarray:
+    """One pass of `ImagingResample` along `axis` from the CALLER's tables: bounds [out, 2] = (first input index, tap count), ik
+    [out, ksize] taps in 22-bit fixed point - any integers, Pillow's or not: out = clip8((2^21 + sum_t a[first + t] ik[t]) >> 22)
+    with an arithmetic shift.  The sum is formed exactly; one that leaves int32 (the C code's accumulator) is refused."""
     a = np.moveaxis(a, axis, 0)
-    bounds, ik = resize_coeffs(a.shape[0], out_size)
-    out = np.empty((out_size,) + a.shape[1:], np.uint8)
-    for xx, (xmin, xmax) in enumerate(bounds):
+    out = np.empty((len(bounds),) + a.shape[1:], np.uint8)
+    for xx, (xmin, xmax) in enumerate(np.asarray(bounds).tolist()):
+        assert 0 <= xmin and 0 <= xmax <= ik.shape[1] and xmin + xmax <= a.shape[0], "row %d reads outside the input" % xx
         ss = np.full(a.shape[1:], 1 << (PRECISION_BITS - 1), np.int64)
         for x in range(xmax):
             ss = ss + a[xmin + x].astype(np.int64) * int(ik[xx, x])
+            assert int(np.abs(ss).max(initial=0)) < 1 << 31, "row %d leaves int32" % xx
         out[xx] = np.clip(ss >> PRECISION_BITS, 0, 255).astype(np.uint8)
     return np.moveaxis(out, 0, axis)
+
+
+def resize_bilinear_tables(a: np.ndarray, htab=None, vtab=None) -> np.ndarray:
+    """a [..., H, W] uint8 through the horizontal pass of htab = (bounds, taps), then the vertical pass of vtab; None: that pass
+    is skipped.  `resize_bilinear` is this with Pillow's tables."""
+    if htab is not None:
+        a = resample_axis_tables(a, htab[0], htab[1], a.ndim - 1)
+    if vtab is not None:
+        a = resample_axis_tables(a, vtab[0], vtab[1], a.ndim - 2)
+    return a
+
+
+def _resample_axis(a: np.ndarray, out_size: int, axis: int) -> np.ndarray:
+    bounds, ik = resize_coeffs(a.shape[axis], out_size)
+    return resample_axis_tables(a, bounds, ik, axis)
 
 
 def resize_bilinear(a: np.ndarray, out_h: int, out_w: int) -> np.ndarray:
@@ -81,6 +100,27 @@ def gaussian_box_params(radius: float = 2.0, passes: int = 3):
     return r, ww, fw
 
 
+def box_blur_params(radius: float):
+    """`ImageFilter.BoxBlur(radius)` = one pass of `ImagingHorizontalBoxBlur` per axis at that float radius: (int radius, ww, fw)
+    as its C code derives them in float32."""
+    f = np.float32
+    r = int(f(radius))
+    ww = int(f(1 << 24) / (f(radius) * f(2) + f(1)))
+    fw = ((1 << 24) - (r * 2 + 1) * ww) // 2
+    return r, ww, fw
+
+
+def box_blur(a: np.ndarray, r: int, ww: int, fw: int, passes: int = 1) -> np.ndarray:
+    """a [..., H, W] uint8: `passes` extended-box-blur passes of (r, ww, fw) along the horizontal axis, then as many along the
+    vertical one.  passes = 1 with box_blur_params(radius) is PIL `filter(ImageFilter.BoxBlur(radius))`."""
+    for _ in range(passes):
+        a = _hbox(a, r, ww, fw)
+    a = np.swapaxes(a, -1, -2)
+    for _ in range(passes):
+        a = _hbox(a, r, ww, fw)
+    return np.ascontiguousarray(np.swapaxes(a, -1, -2))
+
+
 def _hbox(a: np.ndarray, r: int, ww: int, fw: int) -> np.ndarray:
     """One horizontal extended-box-blur pass along the last axis, clamped borders, uint32 arithmetic."""
     W = a.shape[-1]
@@ -96,13 +136,7 @@ def _hbox(a: np.ndarray, r: int, ww: int, fw: int) -> np.ndarray:
 def gaussian_blur(a: np.ndarray, radius: float = 2.0, passes: int = 3) -> np.ndarray:
     """a [..., H, W] uint8 like PIL `filter(ImageFilter.GaussianBlur(radius))`: `passes` horizontal box passes, then the
     same number along the vertical axis."""
-    r, ww, fw = gaussian_box_params(radius, passes)
-    for _ in range(passes):
-        a = _hbox(a, r, ww, fw)
-    a = np.swapaxes(a, -1, -2)
-    for _ in range(passes):
-        a = _hbox(a, r, ww, fw)
-    return np.ascontiguousarray(np.swapaxes(a, -1, -2))
+    return box_blur(a, *gaussian_box_params(radius, passes), passes)
 
 
 def normalize(a: np.ndarray) -> np.ndarray:

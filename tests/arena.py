@@ -25,6 +25,8 @@ no conversion produces (theirs are 0x7FC0 / 0x7E00).
     pk = a.place_output16(n, torch.bfloat16)                                               # a dense pack of n elements
     m = a.place_output_u8((B, T))                                                          # a byte output, padded to whole words
     img = a.place_output_u8((n,), lead=1, expect=ref)                                      # ... one byte off a word, of any byte values
+    src = a.place_input_u8(image, lead=3)                                                  # a byte input three bytes off a word
+    tmp = a.place_ws_u8(n, lead=2)                                                         # a workspace of exactly n BYTES
 
 An lp image holds zeros on its one-pixel border, the values of `reads` (NCHW tensors, exactly representable) in their channel
 ranges and PATTERN16 in every other channel of the interior; the call may write the interior pixels x the channel ranges of
@@ -286,6 +288,28 @@ class Arena:
             must[lead:lead + n] = expect.reshape(-1) != img[lead:lead + n]
         return self._place16(Region16(self, _OUTPUT if written else _ABSENT, 0, shape, torch.uint8, img, mask, must, False, lead),
                              align, skew)
+
+    def place_input_u8(self, t, align=16, skew=0, lead=0):
+        """A byte input (an image) the call only reads, starting `lead` (0..3) BYTES behind the word `align` and `skew` place: the
+        bytes in front of it and behind its last element hold PATTERN's and are guarded like every byte of the operand itself."""
+        t = t.detach().cpu().contiguous()
+        assert t.dtype == torch.uint8 and t.numel() >= 1 and 0 <= lead <= 3
+        n = t.numel()
+        img = torch.full(((lead + n + 3) // 4,), PATTERN, dtype=torch.int32).view(torch.uint8).clone()
+        img[lead:lead + n] = t.reshape(-1)
+        mask, must = torch.zeros_like(img), torch.zeros(img.shape, dtype=torch.bool)
+        shape = tuple(int(s) for s in t.shape) or (1,)
+        return self._place16(Region16(self, _INPUT, 0, shape, torch.uint8, img, mask, must, False, lead), align, skew)
+
+    def place_ws_u8(self, n, align=16, skew=0, lead=0):
+        """A workspace of exactly `n` BYTES, `lead` bytes off a word, holding PATTERN's bytes: the call may write those n bytes, all
+        of them or some, and not the byte in front of them nor the one behind."""
+        n = int(n)
+        assert n >= 1 and 0 <= lead <= 3
+        img = torch.full(((lead + n + 3) // 4,), PATTERN, dtype=torch.int32).view(torch.uint8).clone()
+        mask, must = torch.zeros_like(img), torch.zeros(img.shape, dtype=torch.bool)
+        mask[lead:lead + n] = 255
+        return self._place16(Region16(self, _WS, 0, (n,), torch.uint8, img, mask, must, False, lead), align, skew)
 
     def place_ws(self, n, align=16, skew=0):
         """A workspace of exactly `n` floats, PATTERN-prefilled (a NaN: whatever is read before it is written poisons the result)."""

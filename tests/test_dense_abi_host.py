@@ -100,6 +100,36 @@ def test_arena_byte_output_off_a_word():
         assert any("outside every output" in v for v in a.violations()), where
 
 
+def test_arena_byte_input_and_workspace_off_a_word():
+    """place_input_u8(lead=) and place_ws_u8(n, lead=): both start `lead` bytes into their first word; a byte input must hold every
+    byte, the bytes in front of it and behind it too; a byte workspace may be written in its n bytes and nowhere else."""
+    from arena import PATTERN, Arena
+    pat = torch.tensor([PATTERN], dtype=torch.int32).view(torch.uint8)
+    data = torch.tensor([9, 8, 7, 6, 5], dtype=torch.uint8)
+
+    def fresh():
+        a = Arena("cpu", guard=4)
+        x = a.place_input_u8(data, lead=3)
+        ws = a.place_ws_u8(6, lead=1)
+        assert x.address % 4 == 3 and ws.address % 4 == 1 and x.span == 2 and ws.span == 2
+        buf = a.buffer()
+        return a, x, ws, buf[x.offset:x.offset + 2].view(torch.uint8), buf[ws.offset:ws.offset + 2].view(torch.uint8)
+    a, x, ws, rx, rw = fresh()
+    a.check()
+    assert torch.equal(x.read(), data) and torch.equal(rx[3:8], data) and torch.equal(rx[:3], pat[:3])
+    assert torch.equal(rw, torch.cat([pat, pat])) and ws.kind == "ws"
+    rw[1:7] = 0                                                                 # all n bytes written: fine; none written: fine too (above)
+    a.check()
+    for which, where in ((0, 2), (0, 3), (0, 7), (1, 0), (1, 7)):               # in front of the input, its first and last byte; around ws
+        a, x, ws, rx, rw = fresh()
+        (rx, rw)[which][where] ^= 1
+        assert any("outside every output" in v for v in a.violations()), (which, where)
+    a, x, ws, rx, rw = fresh()
+    rw[1:7] = 3
+    a.rearm()
+    assert torch.equal(rw, torch.cat([pat, pat]))
+
+
 # ---- the launch arithmetic ----
 def test_gemm_rows_have_the_tails_they_name():
     g = A.gemm_plan

@@ -96,6 +96,31 @@ def test_wrappers_and_operators_refuse_cpu_tensors():
         torch.ops.tgsr.rgb_to_y(u)
 
 
+def test_pyramid_wrappers_check_their_arguments_and_refuse_cpu_tensors():
+    """ops.resize_bilinear_u8 / gaussian_blur_u8 / u8_normalize: a tensor that is not uint8 (its bytes would be read as pixels), has
+    too few dimensions or is empty, and a size or a pass count below 1, are named as such - with no device at all - and a good
+    uint8 tensor on the CPU is refused for where it lives."""
+    from tgsr_amd import ops
+    from tgsr_amd._lib import TgsrError
+    u = torch.zeros(2, 3, 8, 8, dtype=torch.uint8)
+    blur = (1, 4473924, 1677722)
+    for bad, what in ((u.float(), "uint8"), (u.to(torch.int8), "uint8"), (u[0, 0, 0], "dimension"), (u[:0], "empty"), (u, "HIP tensors")):
+        with pytest.raises(TgsrError, match=what):
+            ops.resize_bilinear_u8(bad, 4, 4, None, None)
+        with pytest.raises(TgsrError, match=what):
+            ops.gaussian_blur_u8(bad, *blur, 3)
+    for bad, what in ((u.float(), "uint8"), (u.double(), "uint8"), (torch.tensor(3, dtype=torch.uint8), "dimension"), (u[:, :0], "empty"),
+                      (u[0, 0, 0], "HIP tensors")):
+        with pytest.raises(TgsrError, match=what):
+            ops.u8_normalize(bad)
+    for oh, ow in ((0, 4), (4, 0), (-2, 4)):
+        with pytest.raises(TgsrError, match="at least 1 x 1"):
+            ops.resize_bilinear_u8(u, oh, ow, None, None)
+    for passes in (0, -1):
+        with pytest.raises(TgsrError, match="passes"):
+            ops.gaussian_blur_u8(u, *blur, passes)
+
+
 def test_both_schemas_are_registered():
     from tgsr_amd import custom_ops  # noqa: F401
     have = {str(s) for s in torch._C._jit_get_all_schemas() if s.name.startswith("tgsr::")}

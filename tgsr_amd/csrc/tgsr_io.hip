@@ -66,6 +66,12 @@ static inline int io_grid(int64_t n) {
   return (int)(g < 1 ? 1 : (g > 8192 ? 8192 : g));
 }
 
+// do the byte ranges [a, a + na) and [b, b + nb) share a byte?
+static inline bool io_overlap(const void* a, int64_t na, const void* b, int64_t nb) {
+  const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
+  return pa < pb + (uintptr_t)nb && pb < pa + (uintptr_t)na;
+}
+
 }  // namespace tgsr
 
 using namespace tgsr;
@@ -77,6 +83,9 @@ extern "C" int tgsr_resize_bilinear_u8(const uint8_t* in, int N, int Hin, int Wi
   const bool doh = Wout != Win, dov = Hout != Hin;
   if ((doh && (!hbounds || !hcoef || hk < 1)) || (dov && (!vbounds || !vcoef || vk < 1))) return TGSR_EINVAL;
   if (doh && dov && !tmp) return TGSR_EINVAL;
+  const int64_t nin = (int64_t)N * Hin * Win, nout = (int64_t)N * Hout * Wout, ntmp = (int64_t)N * Hin * Wout;
+  if (io_overlap(in, nin, out, nout)) return TGSR_EINVAL;             // the copy branch included: `in` is const
+  if (doh && dov && (io_overlap(tmp, ntmp, in, nin) || io_overlap(tmp, ntmp, out, nout))) return TGSR_EINVAL;
   hipStream_t s = as_stream(stream);
   const uint8_t* cur = in;
   if (doh) {                                      // Pillow: horizontal pass first, into an image of [Hin][Wout]
@@ -98,8 +107,14 @@ extern "C" int tgsr_resize_bilinear_u8(const uint8_t* in, int N, int Hin, int Wi
 extern "C" int tgsr_gaussian_blur_u8(const uint8_t* in, int N, int H, int W, int radius, uint32_t ww, uint32_t fw,
                                      int passes, uint8_t* tmp, uint8_t* out, void* stream) {
   if (!in || !tmp || !out || N < 1 || H < 1 || W < 1 || radius < 0 || passes < 1) return TGSR_EINVAL;
+  // box_blur_kernel adds 255 x ((2 radius + 1) ww + 2 fw) + 2^23 at the most, in uint32: that cannot wrap while the weights of one
+  // output add up to at most 2^24 (Pillow's add up to 2^24 or 2^24 - 1).  With ww >= 1 this also keeps radius below 2^23, and
+  // c - radius - 1 inside int; ww == 0 says nothing about radius, hence the second test.
+  if ((2 * (uint64_t)radius + 1) * (uint64_t)ww + 2 * (uint64_t)fw > (1ull << 24) || radius >= (1 << 23)) return TGSR_EINVAL;
+  const int64_t n = (int64_t)N * H * W;
+  if (io_overlap(in, n, out, n) || io_overlap(in, n, tmp, n) || io_overlap(tmp, n, out, n)) return TGSR_EINVAL;
   hipStream_t s = as_stream(stream);
-  const int g = io_grid((int64_t)N * H * W);
+  const int g = io_grid(n);
   // 2 * passes launches ping-ponging between tmp and out, arranged so that the last one writes `out`
   const uint8_t* cur = in;
   const int launches = 2 * passes;

@@ -1824,13 +1824,25 @@ def bilinear_bwd(dy: torch.Tensor, H: int, W: int) -> torch.Tensor:
 
 
 # ----------------------------------------------------------------------------------------- image pyramid (uint8)
+def _u8_images(x: torch.Tensor, what: str, min_dim: int = 2) -> torch.Tensor:
+    """The image operand of the pyramid wrappers: uint8 (any other type would be read as bytes), at least `min_dim` dimensions,
+    not empty, on the HIP device; returned dense."""
+    if x.dtype != torch.uint8:
+        raise TgsrError("%s: uint8 images expected, got %s" % (what, x.dtype))
+    if x.dim() < min_dim:
+        raise TgsrError("%s: at least %d dimension%s expected, got shape %s" % (what, min_dim, "s" if min_dim > 1 else "", tuple(x.shape)))
+    if x.numel() < 1:
+        raise TgsrError("%s: an empty tensor, shape %s" % (what, tuple(x.shape)))
+    _need_hip(x)
+    return x.contiguous()
+
+
 def resize_bilinear_u8(x: torch.Tensor, out_h: int, out_w: int, htab, vtab) -> torch.Tensor:
     """Pillow's `resize(BILINEAR)` of planar uint8 images [..., H, W]; htab / vtab = (bounds, coefficients, ksize) device
     tables of the horizontal / vertical pass, or None when that size does not change."""
-    _need_hip(x)
-    if x.dtype != torch.uint8:
-        raise TgsrError("resize: uint8 images expected, got %s" % x.dtype)
-    x = x.contiguous()
+    if out_h < 1 or out_w < 1:
+        raise TgsrError("resize: the output size must be at least 1 x 1, got %d x %d" % (out_h, out_w))
+    x = _u8_images(x, "resize")
     H, W = x.shape[-2], x.shape[-1]
     N = x.numel() // (H * W)
     out = torch.empty(x.shape[:-2] + (out_h, out_w), dtype=torch.uint8, device=x.device)
@@ -1844,8 +1856,9 @@ def resize_bilinear_u8(x: torch.Tensor, out_h: int, out_w: int, htab, vtab) -> t
 
 def gaussian_blur_u8(x: torch.Tensor, r: int, ww: int, fw: int, passes: int = 3) -> torch.Tensor:
     """Pillow's GaussianBlur (extended box blur, `passes` per axis) of planar uint8 images [..., H, W]."""
-    _need_hip(x)
-    x = x.contiguous()
+    if passes < 1:
+        raise TgsrError("gaussian_blur: passes must be at least 1, got %d" % passes)
+    x = _u8_images(x, "gaussian_blur")
     H, W = x.shape[-2], x.shape[-1]
     out, tmp = torch.empty_like(x), torch.empty_like(x)
     check(_lib.lib().tgsr_gaussian_blur_u8(_p(x), x.numel() // (H * W), H, W, r, ww, fw, passes, _p(tmp), _p(out), _stream()),
@@ -1855,8 +1868,7 @@ def gaussian_blur_u8(x: torch.Tensor, r: int, ww: int, fw: int, passes: int = 3)
 
 def u8_normalize(x: torch.Tensor) -> torch.Tensor:
     """ToTensor + Normalize((0.5,)*3, (0.5,)*3) (datasets.py:286-288): uint8 -> float32 in [-1, 1]."""
-    _need_hip(x)
-    x = x.contiguous()
+    x = _u8_images(x, "u8_normalize", 1)
     out = torch.empty(x.shape, dtype=torch.float32, device=x.device)
     check(_lib.lib().tgsr_u8_normalize(_p(x), _p(out), x.numel(), _stream()), "tgsr_u8_normalize")
     return out
