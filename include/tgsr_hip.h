@@ -187,6 +187,11 @@ int tgsr_wino4_wide_conv3x3_stats_fwd(const float* x, int64_t x_bstride, int B, 
 int tgsr_wino4_wide_conv3x3_fwd(const float* x, int64_t x_bstride, int B, int Cin, int H, int W, const float* upack, int Cout,
                                 const float* scale, const float* shift, const float* residual, int64_t res_bstride,
                                 float* out, int64_t out_bstride, int epilogue, void* stream);
+/* tgsr_wino4w_set_persist(cap): how many workgroups a register-fed launch starts for the workgroup tiles of its plan (the plan's
+ * grid stays the tile count).  -1 (the default): as many as the device holds at once - one 8-wave or two 4-wave workgroups per
+ * CU - each walking tiles id, id + n, ...; 0: one tile per workgroup; n > 0: at most n workgroups.  TGSR_WINO4W_PERSIST in the
+ * environment selects the same values at load.  The outputs are bit-identical whatever the value.  Returns the previous value. */
+int tgsr_wino4w_set_persist(int cap);
 
 /*
  * The planner of the seven forms above.  Every launch of theirs is planned once, by one host function (csrc/tgsr_conv_plan.h, which

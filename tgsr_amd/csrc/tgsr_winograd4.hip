@@ -32,6 +32,7 @@
 #include "tgsr_common.h"
 #include "tgsr_conv_plan.h"
 
+#include <atomic>
 #include <type_traits>
 
 namespace tgsr {
@@ -70,6 +71,7 @@ struct Wino4Args {
   int tiles_x, tiles_y, nstages, ngroups;
   float* stat;            // STATS: [Cout][nslots][2] per-wave (sum, sum of squares) of the outputs, else unused
   int nslots;
+  int ntiles;             // wide form: workgroup tiles of the plan (its grid); the launched grid walks them
 };
 
 constexpr int k4CK = 4;                                   // input channels per stage
@@ -478,14 +480,47 @@ constexpr int k4wUW = 9 * 256;                                          // float
 // groups (Cout % 128 != 0: the +residual convolutions): 4-wave workgroups, two per CU that share nothing, so one's prologue and
 // epilogue - the residual variant's 131 KB in / 131 KB out burst - run under the other's main loop; the transform is not amortised
 // further than in the narrow form (three of four waves transform), what it saves is the 36 U copies and the A reads from LDS.
+//
+// The tile walk.  A launch starts min(tiles, what the chip holds at once: one 8-wave or two 4-wave workgroups per CU) workgroups
+// (wino4_launch, tgsr_wino4w_set_persist); workgroup i takes the plan's workgroup tiles i, i + gridDim.x, ... - each through the remap
+// and the decomposition a workgroup of its own would give blockIdx.x, from its own prologue to its own epilogue, so every tile keeps its
+// arithmetic and the order in which tiles meet L2 stays.  Measured on the parent at 128^2, B = 16 (profiles/HISTORY.md "Later: the
+// register-fed F(4x4) kernels walk their tiles"): between a workgroup's last instruction and its successor's first on the same CU lie
+// 2.1 us (64 -> 128, four rounds) to 4.3 us (64 -> 64 + residual, two co-resident workgroups that end together), and the prologue
+// costs 2.4 us more.  The walk keeps the prologue and removes the first: the next tile's raw copies and fragment loads are in flight
+// while the epilogue's stores drain.  Two forms of the hand-over were built:
+//   kept:    the plain walk above - per tile the kernel is the one-tile kernel, nothing but the tile id lives across the epilogue,
+//            242-245 VGPRs and no scratch as before.  The default step: 1.279-1.282 ms against 1.303-1.313 ms in four alternating pairs.
+//   dropped: the hand-over inside the stage loop (stages n-2 / n-1 issue the next tile's raw(0), raw(1) and transform its V(0); stage
+//            0's fragments either kept across the epilogue or re-issued behind it).  With 144 accumulator + 36 fragment registers
+//            live, whatever else has to survive the epilogue (raw addresses, the lane offsets of the stage loop, the next tile's
+//            coordinates) no longer fits: hipcc spilled 45-69 VGPRs (fragments kept: 48-87), unswitched the stage loop into four
+//            copies, and the reloads sat on the hand-over's critical path - 64 -> 128 at 128^2 alone: 126.7 us against 128.9 us,
+//            first workgroup start to last end 121.0 against 119.7 us, and 135.5 us with one tile per workgroup.  Not a gain.
+// The lane id inside the walk comes from mbcnt behind an empty asm: derived from threadIdx.x, every lane-only address is an invariant
+// of the walk that hipcc may compute once in front of it and keep - in the dropped form it kept them in scratch, the stage loop
+// having no register to spare.
 template <bool GLU, int NB, bool STATS = false>
 __global__ __launch_bounds__(64 * NB, 2) void wino4w_conv3x3_kernel(Wino4Args a) {
   static_assert(!(GLU && STATS), "batch statistics are taken of the raw (plain-epilogue) convolution output");
   constexpr int NR = 16 * NB;                              // accumulator rows of a workgroup (128 | 64)
   __shared__ __attribute__((aligned(16))) float smem[k4wSMEM];
-  const int tid = threadIdx.x, lane = tid & 63, l15 = lane & 15, lg = lane >> 4;
-  const int cb = __builtin_amdgcn_readfirstlane(tid >> 6);             // channel block of this wave
-  int t = xcd_remap(blockIdx.x, gridDim.x);
+  const int cb = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);     // channel block of this wave
+  TGSR_W4STAMP(0);
+  // ---- the tile walk: the workgroup takes the plan's workgroup tiles w = blockIdx.x, + gridDim.x, ... < ntiles, each from its
+  // prologue to its epilogue exactly as a workgroup of its own would (same remap, same decomposition, same arithmetic) - what the
+  // walk saves is what lies between two workgroups on a CU: the old one's stores draining before its slot is free, the dispatcher,
+  // the LDS allocation and the wave launch.  Here the next tile's prologue loads are in flight while those stores drain.
+  // Workgroups never meet: a grid larger than what is resident finishes all the same.
+  for (unsigned w = blockIdx.x; w < (unsigned)a.ntiles; w += gridDim.x) {
+  // every wave is through the previous tile's LDS (raw, V, the affine table); its stores may still be on their way
+  if (w != blockIdx.x) asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+  // the lane id from the hardware, behind an empty asm, per tile (see the header: nothing lane-only is to be kept across tiles)
+  unsigned lane_z = 0;
+  asm volatile("" : "+v"(lane_z));
+  const int lane = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, lane_z));
+  const int tid = cb * 64 + lane, l15 = lane & 15, lg = lane >> 4;
+  int t = xcd_remap((int)w, a.ntiles);
   const int grp = t % a.ngroups;
   t /= a.ngroups;
   const int tx = t % a.tiles_x;
@@ -626,6 +661,7 @@ __global__ __launch_bounds__(64 * NB, 2) void wino4w_conv3x3_kernel(Wino4Args a)
       t_write(rc, d, vs);
     }
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+    TGSR_W4STAMP(1);
     // an EVEN number of stages (host-checked): exactly two copies of the stage, P0 -> P1 -> back edge.  A third copy behind the
     // loop (an odd tail) got other physical registers for af[] and hipcc bridged them with v_mov - of fragments that had not
     // arrived yet (every output wrong at Cin = 12; the parity tests of the wide form would catch a recurrence)
@@ -639,8 +675,7 @@ __global__ __launch_bounds__(64 * NB, 2) void wino4w_conv3x3_kernel(Wino4Args a)
   else if (cb == 2) run(std::integral_constant<int, 2>{});
   else run(std::integral_constant<int, 3>{});
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");       // the last stage's (unused) fragment loads: see the header
-#undef TGSR_W4W_LOAD
-#undef TGSR_W4W_WAIT
+  TGSR_W4STAMP(2);
 
   auto ytile = [&](int i, float (&y)[4][4]) {
     float c[4][6];
@@ -713,7 +748,7 @@ __global__ __launch_bounds__(64 * NB, 2) void wino4w_conv3x3_kernel(Wino4Args a)
   }
   if (STATS) {
     // BatchNorm's batch statistics (as in the narrow form): one (sum, sumsq) pair per channel and wave - slot = (sample, tile
-    // row, 64-column chunk): the narrow form's pairs in another order
+    // row, 64-column chunk): the narrow form's pairs in another order; from the tile's coordinates, never the workgroup's id
     const int slot = (b * a.tiles_y + ty) * a.tiles_x + tx;
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
@@ -729,6 +764,10 @@ __global__ __launch_bounds__(64 * NB, 2) void wino4w_conv3x3_kernel(Wino4Args a)
       }
     }
   }
+  }  // the tile walk
+  TGSR_W4STAMP(3);
+#undef TGSR_W4W_LOAD
+#undef TGSR_W4W_WAIT
 }
 
 // wide pack: upack[stage][group of 16 nb rows][cb nb][quad 9][lane 64 = (ci lane >> 4, row lane & 15)][4], nb = 8 (Cout % 128 == 0)
@@ -823,7 +862,34 @@ extern "C" int tgsr_wino4_stats_nslots(int B, int H, int W, int Cout) {
   return conv_tiles(TGSR_CONV_FORM_WINO4, B, H, W, Cout, TGSR_EPI_AFFINE, 0, 1).nslots;
 }
 
-// Both kernels' launcher (form = TGSR_CONV_FORM_WINO4 | _WINO4W).  stat != NULL: the statistics entry (plain epilogue, no affine, no residual)
+// tgsr_wino4w_set_persist: 0 = one tile per workgroup, -1 = as many workgroups as the chip holds at once, n > 0 = at most n
+static std::atomic<int> g_w4w_persist{[] {
+  const char* e = getenv("TGSR_WINO4W_PERSIST");
+  const int v = e ? atoi(e) : -1;
+  return v < -1 ? -1 : v;
+}()};
+
+extern "C" int tgsr_wino4w_set_persist(int cap) { return g_w4w_persist.exchange(cap < -1 ? -1 : cap); }
+
+// How many workgroups of wino4w_conv3x3_kernel<., nb, .> walk a launch's tiles (0: one each; < 0: the device would not say).  Automatic =
+// what is resident at once: 2 waves per SIMD by the kernel's launch bounds = one 8-wave or two 4-wave workgroups per CU.  The CU
+// count is read once per device - an attribute query, which a stream capture in progress allows - and kept.
+static int wino4w_walkers(int nb) {
+  const int cap = g_w4w_persist.load(std::memory_order_relaxed);
+  if (cap >= 0) return cap;
+  constexpr int kMaxDev = 64;
+  static std::atomic<int> cus[kMaxDev];
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDev) return -1;
+  int n = cus[dev].load(std::memory_order_relaxed);
+  if (n == 0) {
+    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n < 1) return -1;
+    cus[dev].store(n, std::memory_order_relaxed);
+  }
+  return n * (nb == 8 ? 1 : 2);
+}
+
+// Both kernels' launcher (form =TGSR_CONV_FORM_WINO4 | _WINO4W).  stat != NULL: the statistics entry (plain epilogue, no affine, no residual)
 static int wino4_launch(int form, const ConvCall& c, float* stat, void* stream) {
   static_assert(k4CK == kConvStage && k4TR == 8 + 2 && k4TC == 64 + 8, "the plan's stage and tile are the kernels'");
   const ConvPlan p = conv_plan(form, c);
@@ -833,16 +899,24 @@ static int wino4_launch(int form, const ConvCall& c, float* stat, void* stream) 
   conv_fill(a, c, p);
   a.upack = c.pack; a.res = c.res; a.rbs = c.rbs; a.nstages = p.stages; a.ngroups = p.groups; a.stat = stat; a.nslots = p.nslots;
   hipStream_t s = as_stream(stream);
+  // the wide form walks the plan's tiles with the workgroups the chip holds at once (wino4w_walkers); the plan's grid stays the tile count
+  a.ntiles = (int)p.grid.x;
+  dim3 wg = p.grid;
+  if (wide) {
+    const int n = wino4w_walkers(p.t[1]);
+    if (n < 0) return note_error("wino4w_conv3x3_kernel", "the device does not say how many compute units it has", n);
+    if (n > 0 && (unsigned)n < wg.x) wg.x = (unsigned)n;
+  }
   switch ((wide ? p.t[1] * 10 : 0) + p.t[0] * 2 + p.t[wide ? 2 : 1]) {           // <GLU, STATS> | <GLU, NB, STATS>
     case 2: hipLaunchKernelGGL((wino4_conv3x3_kernel<true>), p.grid, p.block, 0, s, a); break;
     case 1: hipLaunchKernelGGL((wino4_conv3x3_kernel<false, true>), p.grid, p.block, 0, s, a); break;
     case 0: hipLaunchKernelGGL((wino4_conv3x3_kernel<false>), p.grid, p.block, 0, s, a); break;
-    case 82: hipLaunchKernelGGL((wino4w_conv3x3_kernel<true, 8>), p.grid, p.block, 0, s, a); break;
-    case 81: hipLaunchKernelGGL((wino4w_conv3x3_kernel<false, 8, true>), p.grid, p.block, 0, s, a); break;
-    case 80: hipLaunchKernelGGL((wino4w_conv3x3_kernel<false, 8>), p.grid, p.block, 0, s, a); break;
-    case 42: hipLaunchKernelGGL((wino4w_conv3x3_kernel<true, 4>), p.grid, p.block, 0, s, a); break;
-    case 41: hipLaunchKernelGGL((wino4w_conv3x3_kernel<false, 4, true>), p.grid, p.block, 0, s, a); break;
-    case 40: hipLaunchKernelGGL((wino4w_conv3x3_kernel<false, 4>), p.grid, p.block, 0, s, a); break;
+    case 82: hipLaunchKernelGGL((wino4w_conv3x3_kernel<true, 8>), wg, p.block, 0, s, a); break;
+    case 81: hipLaunchKernelGGL((wino4w_conv3x3_kernel<false, 8, true>), wg, p.block, 0, s, a); break;
+    case 80: hipLaunchKernelGGL((wino4w_conv3x3_kernel<false, 8>), wg, p.block, 0, s, a); break;
+    case 42: hipLaunchKernelGGL((wino4w_conv3x3_kernel<true, 4>), wg, p.block, 0, s, a); break;
+    case 41: hipLaunchKernelGGL((wino4w_conv3x3_kernel<false, 4, true>), wg, p.block, 0, s, a); break;
+    case 40: hipLaunchKernelGGL((wino4w_conv3x3_kernel<false, 4>), wg, p.block, 0, s, a); break;
     default: return note_error("wino4_conv3x3_kernel", "the plan names no instance", 0);
   }
   return note_launch(hipGetLastError(), wide ? "wino4w_conv3x3_kernel" : "wino4_conv3x3_kernel");

@@ -1171,6 +1171,12 @@ def conv_to3_pipe() -> bool:
     return bool(was)
 
 
+def wino4w_set_persist(cap: int) -> int:
+    """How many workgroups a register-fed F(4x4) launch starts for its plan's tiles: -1 what the device holds at once (default), 0 one
+    per tile, n > 0 at most n.  Bit-identical outputs either way; returns the previous value."""
+    return int(_lib.lib().tgsr_wino4w_set_persist(int(cap)))
+
+
 def bn_set_fuse_small(on: bool) -> bool:
     """Small BatchNorm layers (one workgroup per channel) as one launch per direction (default) or two; returns the previous setting."""
     return bool(_lib.lib().tgsr_bn_set_fuse_small(1 if on else 0))
