@@ -954,6 +954,40 @@ int tgsr_niqe_features(const void* img, int is_f32, int B, int H, int W, int sha
                        double* ws, double* feats, double* sharp, void* stream);
 
 /*
+ * Learned perceptual distance (csrc/tgsr_lpips.hip): the tail of LPIPS v0.1 (Zhang, Isola, Efros, Shechtman and Wang 2018), one tapped
+ * layer per call, and the 2 x 2 max pool of its VGG16 trunk; tgsr_amd/lpips.py walks the trunk on tgsr_gconv.  The head of the kernel
+ * file and DESIGN.md 3.18 state the arithmetic.
+ * tgsr_maxpool2s2_*: F.max_pool2d(x, 2) for any H, W >= 2 (floor), the signatures of tgsr_maxpool3s2_*: x dense planes with a batch
+ *   stride, out / dy based at a channel slice.  The backward routes dy to the FIRST maximum of a window in row-major order (torch's
+ *   rule), adds where accumulate != 0, keeps the value where mask > 0 (mask nullable, laid out like dx with dx's batch stride) and
+ *   with accumulate = 0 writes dx whole - the zeros of an odd trailing row or column included: no memset.
+ * tgsr_lpips_layer_fwd: f0, f1 fp32 [B][C][HW] (samples f0_bstride / f1_bstride floats apart), w fp32 [C] >= 0;
+ *   partial fp64 [B][nslots], nslots = tgsr_lpips_nslots(C, HW) (0 = a shape the entries refuse): slot k of image b holds
+ *   sum_p sum_c w[c] (n(f0) - n(f1))^2 over the slot's pixels, n(f) = f / (sqrt(sum_c f^2) + 1e-10), not yet divided by HW.  Each
+ *   feature is read once; the five channel sums of a pixel are fp64 sums of exactly widened floats.
+ *   nslots = ceil(tiles / t): tiles of 16 (HW <= 1024) or 64 pixels, t = ceil(tiles / 512) tiles per slot, at least 4 where
+ *   HW >= 32768 (there a wave takes whole tiles: a tile per wave).
+ * tgsr_lpips_finish: one launch for L <= 8 taps (partial, nslots <= 512, HW: HOST arrays of L entries, copied into the launch):
+ *   per_layer[l][b] = (the tap's slots summed in index order) / HW[l] (fp32 [L][B], nullable), total[b] = their sum in tap order.
+ * tgsr_lpips_layer_bwd: df0[b] (+)= g[b] d(d_l[b]) / d(f0[b]) (g fp32 [B] ON THE DEVICE; df0 laid out like f0 with its own batch
+ *   stride; mask nullable, like df0: kept where mask > 0 - a tap's own ReLU is applied by passing f0).  accumulate = 0 writes every
+ *   element of df0; a pixel whose whole f0 column is 0 gets 0 (autograd: NaN).
+ * No atomics, fixed slots and orders: the same bits on every run; no host synchronisation and no allocation: capturable.
+ * Alignment: every pointer 4 bytes (all accesses are dwords), partial 8 bytes; else TGSR_EUNSUPPORTED.  TGSR_EINVAL for a NULL
+ * pointer, B < 1 (the tail: B > 65535), C < 1, HW < 1, H or W < 2 (the pool), L outside 1..8.  A refusal launches and writes nothing.
+ */
+int tgsr_maxpool2s2_fwd(const float* x, int64_t x_bstride, int B, int C, int H, int W, float* out, int64_t o_bstride, void* stream);
+int tgsr_maxpool2s2_bwd(const float* x, int64_t x_bstride, const float* dy, int64_t dy_bstride, int B, int C, int H, int W, float* dx,
+                        int64_t dx_bstride, int accumulate, const float* mask, void* stream);
+int tgsr_lpips_nslots(int C, int HW);
+int tgsr_lpips_layer_fwd(const float* f0, int64_t f0_bstride, const float* f1, int64_t f1_bstride, const float* w, int B, int C, int HW,
+                         double* partial, void* stream);
+int tgsr_lpips_finish(const double* const* partial, const int* nslots, const int* HW, int L, int B, float* per_layer, float* total,
+                      void* stream);
+int tgsr_lpips_layer_bwd(const float* g, const float* f0, int64_t f0_bstride, const float* f1, int64_t f1_bstride, const float* w, int B,
+                         int C, int HW, float* df0, int64_t df0_bstride, int accumulate, const float* mask, void* stream);
+
+/*
  * Attention panels (csrc/tgsr_attnviz.hip): one tile per caption word, the word's attention map thresholded, expanded, blurred,
  * stretched to bytes and pasted over the image - build_super_imagesall / build_super_images2 (miscc/utils.py:202-451) on the
  * device.  The arithmetic is stated in tgsr_amd/attnviz.py and DESIGN.md 3.12.

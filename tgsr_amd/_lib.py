@@ -181,6 +181,12 @@ SIGNATURES = {
     "tgsr_rgb_to_y_u8": (_i, [_vp, _i, _i, _i, _vp, _vp]),
     "tgsr_niqe_ws_elems": (_i64, [_i, _i, _i, _i]),
     "tgsr_niqe_features": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
+    "tgsr_maxpool2s2_fwd": (_i, [_vp, _i64, _i, _i, _i, _i, _vp, _i64, _vp]),
+    "tgsr_maxpool2s2_bwd": (_i, [_vp, _i64, _vp, _i64, _i, _i, _i, _i, _vp, _i64, _i, _vp, _vp]),
+    "tgsr_lpips_nslots": (_i, [_i, _i]),
+    "tgsr_lpips_layer_fwd": (_i, [_vp, _i64, _vp, _i64, _vp, _i, _i, _i, _vp, _vp]),
+    "tgsr_lpips_finish": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp]),
+    "tgsr_lpips_layer_bwd": (_i, [_vp, _vp, _i64, _vp, _i64, _vp, _i, _i, _i, _vp, _i64, _i, _vp, _vp]),
     "tgsr_attn_panels_ws_elems": (_i64, [_i, _i, _i, _i, _i]),
     "tgsr_attn_panels": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "tgsr_attn_confidence": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp]),

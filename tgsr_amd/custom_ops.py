@@ -529,6 +529,20 @@ maxpool3s2 = _define("maxpool3s2(Tensor x, Tensor(a!) out, int o_coff) -> ()", l
                      lambda *a: None)
 maxpool3s2_bwd = _define("maxpool3s2_bwd(Tensor x, Tensor dy, int dy_coff, Tensor(a!) dx, bool accumulate, Tensor? mask) -> ()",
                          lambda x, dy, dc, dx, acc, mask: ops.maxpool3s2_bwd(x, dy, dc, dx, acc, mask), lambda *a: None)
+# the VGG16 trunk's pool and the LPIPS tail (tgsr_lpips.hip; tgsr_amd/lpips.py walks them)
+maxpool2s2 = _define("maxpool2s2(Tensor x, Tensor(a!) out, int o_coff) -> ()", lambda x, out, oc: ops.maxpool2s2(x, out, oc),
+                     lambda *a: None)
+maxpool2s2_bwd = _define("maxpool2s2_bwd(Tensor x, Tensor dy, int dy_coff, Tensor(a!) dx, bool accumulate, Tensor? mask) -> ()",
+                         lambda x, dy, dc, dx, acc, mask: ops.maxpool2s2_bwd(x, dy, dc, dx, acc, mask), lambda *a: None)
+lpips_layer = _define("lpips_layer(Tensor f0, Tensor f1, Tensor w) -> Tensor", lambda f0, f1, w: ops.lpips_layer(f0, f1, w),
+                      lambda f0, f1, w: f0.new_empty(f0.shape[0], ops.lpips_nslots(f0.shape[1], f0.shape[2] * f0.shape[3]),
+                                                     dtype=torch.float64))
+lpips_finish = _define("lpips_finish(Tensor[] partials, int[] hws) -> (Tensor, Tensor)",
+                       lambda ps, hws: ops.lpips_finish(list(ps), list(hws)),
+                       lambda ps, hws: (ps[0].new_empty(len(ps), ps[0].shape[0], dtype=torch.float32),
+                                        ps[0].new_empty(ps[0].shape[0], dtype=torch.float32)))
+lpips_layer_bwd = _define("lpips_layer_bwd(Tensor g, Tensor f0, Tensor f1, Tensor w, Tensor(a!) df0, bool accumulate, Tensor? mask) -> ()",
+                          lambda g, f0, f1, w, df0, acc, mask: ops.lpips_layer_bwd(g, f0, f1, w, df0, acc, mask), lambda *a: None)
 avgpool3 = _define("avgpool3(Tensor x, Tensor(a!) out, bool accumulate, Tensor? mask) -> ()",
                    lambda x, out, acc, mask: ops.avgpool3(x, out, acc, mask), lambda *a: None)
 plane_mean = _define("plane_mean(Tensor x) -> Tensor", lambda x: ops.plane_mean(x), lambda x: x.new_empty(x.shape[0], x.shape[1]))

@@ -2328,6 +2328,112 @@ def niqe_features(img: torch.Tensor, shave: int = 0) -> Tuple[torch.Tensor, torc
     return feats, sharp
 
 
+# ----------------------------------------------------------------------------------------- LPIPS (tgsr_lpips.hip)
+LPIPS_MAX_TAPS = 8       # taps of one tgsr_lpips_finish launch
+
+
+def maxpool2s2(x: torch.Tensor, out: torch.Tensor, o_coff: int):
+    """F.max_pool2d(x, 2) of a dense fp32 NCHW x (H, W >= 2, floor) into channels [o_coff, o_coff + C) of out (tgsr_maxpool2s2_fwd)."""
+    _need_hip(x, out)
+    xp, xbs = _slice_ptr(x, 0)
+    B, Cc, H, W = x.shape
+    op, obs = _slice_ptr(out, o_coff)
+    if H < 2 or W < 2 or out.shape[0] != B or out.shape[2] != H // 2 or out.shape[3] != W // 2 or o_coff < 0 or o_coff + Cc > out.shape[1]:
+        raise TgsrError("maxpool2s2: %s -> channels %d.. of %s" % (tuple(x.shape), o_coff, tuple(out.shape)))
+    check(_lib.lib().tgsr_maxpool2s2_fwd(xp, xbs, B, Cc, H, W, op, obs, _stream()), "tgsr_maxpool2s2_fwd")
+
+
+def maxpool2s2_bwd(x: torch.Tensor, dy: torch.Tensor, dy_coff: int, dx: torch.Tensor, accumulate: bool, mask: Optional[torch.Tensor] = None):
+    """dx (+)= the gradient of maxpool2s2 at x for dy = channels [dy_coff, dy_coff + C) of `dy`: to the first maximum of every window,
+    kept where mask > 0 (mask dense, shaped like dx).  accumulate False writes dx whole (tgsr_maxpool2s2_bwd)."""
+    _need_hip(x, dy, dx, mask)
+    if mask is not None and (mask.shape != dx.shape or not mask.is_contiguous() or mask.dtype != torch.float32):
+        raise TgsrError("maxpool2s2_bwd: the mask must be a dense fp32 tensor shaped like dx")
+    xp, xbs = _slice_ptr(x, 0)
+    B, Cc, H, W = x.shape
+    gp, gbs = _slice_ptr(dy, dy_coff)
+    dp, dbs = _slice_ptr(dx, 0)
+    if (H < 2 or W < 2 or dx.shape != x.shape or dy.shape[0] != B or dy.shape[2] != H // 2 or dy.shape[3] != W // 2 or dy_coff < 0
+            or dy_coff + Cc > dy.shape[1]):
+        raise TgsrError("maxpool2s2_bwd: x %s, dy %s from channel %d, dx %s" % (tuple(x.shape), tuple(dy.shape), dy_coff, tuple(dx.shape)))
+    check(_lib.lib().tgsr_maxpool2s2_bwd(xp, xbs, gp, gbs, B, Cc, H, W, dp, dbs, 1 if accumulate else 0, _p(mask), _stream()),
+          "tgsr_maxpool2s2_bwd")
+
+
+def lpips_nslots(C: int, HW: int) -> int:
+    """Slots per image of lpips_layer's partial sums (tgsr_lpips_nslots): ceil(tiles / t) <= 512 for tiles of 16 (HW <= 1024) or 64
+    pixels and t = ceil(tiles / 512) tiles per slot, at least 4 where HW >= 32768.  0 for a shape the kernels refuse."""
+    return int(_lib.lib().tgsr_lpips_nslots(int(C), int(HW)))
+
+
+def _lpips_feature(t, name, what):
+    """(pointer, batch stride, B, C, HW) of a float32 [B, C, H, W] whose samples are dense (any batch stride, any 4-byte base)."""
+    _dense_f32(t, name, what, "[B, C, H, W]")
+    B, C, H, W = t.shape
+    if t.stride(3) != 1 or t.stride(2) != W or t.stride(1) != H * W or (B > 1 and t.stride(0) < C * H * W):
+        raise TgsrError("%s: %s %s with strides %s: dense samples expected (any batch stride)" % (what, name, tuple(t.shape), t.stride()))
+    return _p(t), (t.stride(0) if B > 1 else C * H * W), B, C, H * W
+
+
+def lpips_layer(f0: torch.Tensor, f1: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
+    """One LPIPS tap (tgsr_lpips_layer_fwd): f0, f1 float32 [B, C, H, W] (dense samples, any batch stride), w float32 [C].  Returns
+    partial float64 [B, lpips_nslots(C, H W)]: per slot sum_p sum_c w[c] (n(f0) - n(f1))^2, n(f) = f / (sqrt(sum_c f^2) + 1e-10) -
+    `lpips_finish` sums the slots and divides by H W.  One launch, every feature read once."""
+    p0, bs0, B, C, HW = _lpips_feature(f0, "f0", "lpips_layer")
+    p1, bs1 = _lpips_feature(f1, "f1", "lpips_layer")[:2]
+    if f1.shape != f0.shape or not torch.is_tensor(w) or w.dtype != torch.float32 or w.numel() != C or not w.is_contiguous():
+        raise TgsrError("lpips_layer: f0 %s, f1 %s and a dense float32 w of %d weights expected" % (tuple(f0.shape), tuple(f1.shape), C))
+    _need_hip(f0, f1, w)
+    ns = lpips_nslots(C, HW)
+    if ns < 1 or B > 65535:
+        raise TgsrError("lpips_layer: %s refused" % (tuple(f0.shape),))
+    partial = torch.empty(B, ns, dtype=torch.float64, device=f0.device)
+    check(_lib.lib().tgsr_lpips_layer_fwd(p0, bs0, p1, bs1, _p(w), B, C, HW, _p(partial), _stream()), "tgsr_lpips_layer_fwd")
+    return partial
+
+
+def lpips_finish(partials, hws) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(per_layer float32 [L, B], total float32 [B]) of 1 to 8 taps' partial sums (lpips_layer) and their pixel counts H W: every tap's
+    slots summed in index order and divided by H W, the taps summed in order (tgsr_lpips_finish, one launch)."""
+    partials, hws = list(partials), [int(v) for v in hws]
+    L = len(partials)
+    if L < 1 or L > LPIPS_MAX_TAPS or len(hws) != L or min(hws) < 1:
+        raise TgsrError("lpips_finish: %d taps with %d pixel counts, 1 to %d of each expected" % (L, len(hws), LPIPS_MAX_TAPS))
+    B = partials[0].shape[0] if partials[0].dim() == 2 else 0
+    for t in partials:
+        if t.dim() != 2 or t.dtype != torch.float64 or not t.is_contiguous() or t.shape[0] != B or t.numel() == 0:
+            raise TgsrError("lpips_finish: dense float64 [B, nslots] partial sums of one batch size expected")
+    _need_hip(*partials)
+    per_layer = torch.empty(L, B, dtype=torch.float32, device=partials[0].device)
+    total = torch.empty(B, dtype=torch.float32, device=partials[0].device)
+    check(_lib.lib().tgsr_lpips_finish(_ptr_array(partials), _int_array([t.shape[1] for t in partials]), _int_array(hws), L, B,
+                                       _p(per_layer), _p(total), _stream()), "tgsr_lpips_finish")
+    return per_layer, total
+
+
+def lpips_layer_bwd(g: torch.Tensor, f0: torch.Tensor, f1: torch.Tensor, w: torch.Tensor, df0: torch.Tensor, accumulate: bool,
+                    mask: Optional[torch.Tensor] = None):
+    """df0 (+)= g[b] d(d_l[b]) / d(f0) of one LPIPS tap (tgsr_lpips_layer_bwd): g float32 [B] on the device, df0 shaped like f0 (dense
+    samples, any batch stride), mask (nullable, df0's shape and strides) keeps the value where mask > 0.  accumulate False writes
+    every element; a pixel whose f0 column is all zero gets 0."""
+    p0, bs0, B, C, HW = _lpips_feature(f0, "f0", "lpips_layer_bwd")
+    p1, bs1 = _lpips_feature(f1, "f1", "lpips_layer_bwd")[:2]
+    dp, dbs = _lpips_feature(df0, "df0", "lpips_layer_bwd")[:2]
+    if f1.shape != f0.shape or df0.shape != f0.shape or not torch.is_tensor(w) or w.dtype != torch.float32 or w.numel() != C or \
+            not w.is_contiguous():
+        raise TgsrError("lpips_layer_bwd: f0 %s, f1 %s, df0 %s and a dense float32 w of %d weights expected"
+                        % (tuple(f0.shape), tuple(f1.shape), tuple(df0.shape), C))
+    if not torch.is_tensor(g) or g.dtype != torch.float32 or g.numel() != B or not g.is_contiguous():
+        raise TgsrError("lpips_layer_bwd: g must be a dense float32 [%d]" % B)
+    if mask is not None and (_lpips_feature(mask, "mask", "lpips_layer_bwd")[1] != dbs or mask.shape != df0.shape):
+        raise TgsrError("lpips_layer_bwd: the mask must have df0's shape and batch stride")
+    _need_hip(g, f0, f1, w, df0, mask)
+    if lpips_nslots(C, HW) < 1 or B > 65535:
+        raise TgsrError("lpips_layer_bwd: %s refused" % (tuple(f0.shape),))
+    check(_lib.lib().tgsr_lpips_layer_bwd(_p(g), p0, bs0, p1, bs1, _p(w), B, C, HW, dp, dbs, 1 if accumulate else 0, _p(mask), _stream()),
+          "tgsr_lpips_layer_bwd")
+
+
 # ----------------------------------------------------------------------------------------- attention panels
 ATTN_MAX_SIDE, ATTN_MAX_TILE, ATTN_MAX_WORDS = 128, 512, 64
 

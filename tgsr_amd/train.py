@@ -24,7 +24,7 @@ import numpy as np
 import torch
 import torch.distributed as dist
 
-from . import autograd, featdist, metrics, model, niqe as niqe_mod, parallel, retrieval
+from . import autograd, featdist, lpips as lpips_mod, metrics, model, niqe as niqe_mod, parallel, retrieval
 from .miscc import losses
 from .miscc.config import cfg
 from .miscc.utils import copy_G_params, load_params  # noqa: F401  (miscc/utils.py:467-474: the generator EMA helpers)
@@ -115,7 +115,7 @@ class GraphPolicy:
 class SRTrainer:
     def __init__(self, n_words, device="cuda", low="lr", lr=None, ema_decay=0.999, image_encoder=None,
                  discriminators=False, d_lr=None, gather_negatives=None, weightmap=False, use_act=True, pixel_loss="mse",
-                 reweight=False, cycle=0.0):
+                 reweight=False, cycle=0.0, perceptual=None):
         """image_encoder: optional frozen module image [B,3,256,256] -> (region features [B,nef,17,17], cnn_code
         [B,nef]) (a CNN_ENCODER with its trunk): adds the DAMSM ranking term of generator_loss (losses.py:375-386)
         on the finest image, x TRAIN.SMOOTH.LAMBDA.
@@ -144,7 +144,28 @@ class SRTrainer:
         no training loop: which images it is applied to, and against which LR tensor, is the build's declaration, like the pairing
         above.  Each call is one forward and one backward launch of tgsr_cycle_mse.hip with nothing on the host that depends on
         data, so - unlike the attention-guided options - the term leaves the generators' update on the captured path.  It is a
-        per-shard batch mean like MSE: nothing to do for data parallelism."""
+        per-shard batch mean like MSE: nothing to do for data parallelism.
+        perceptual: None (default: the term does not exist and the trainer is what it is without the argument) or (model, weight), a
+        tgsr_amd.lpips.LPIPS (or the path of a saved one) and a finite weight >= 0.  The generators' loss gains
+        weight * mean_b LPIPS(fine_im[-1], HR[-1]): the raw float output of the finest scale against its ground truth, one term.  The
+        reference has no such term: this is the build's declaration.  The walk (trunk forward, tails, the tape in reverse) holds
+        nothing on the host that depends on data, so the term leaves the generators' update on the captured path; the filters are
+        packed here, before any capture.  A per-shard batch mean like MSE.  A meaningful term needs trained LPIPS weights, which are
+        not shipped."""
+        self.perceptual, self.perceptual_weight = None, 0.0
+        if perceptual is not None:
+            if not isinstance(perceptual, (tuple, list)) or len(perceptual) != 2:
+                raise ValueError("perceptual must be None or (an LPIPS model, a weight), got %r" % (perceptual,))
+            try:
+                self.perceptual_weight = float(perceptual[1])
+            except (TypeError, ValueError):
+                self.perceptual_weight = float("nan")
+            if not self.perceptual_weight >= 0.0 or self.perceptual_weight == float("inf"):
+                raise ValueError("perceptual: the weight must be finite and >= 0, got %r" % (perceptual[1],))
+            self.perceptual = lpips_mod.as_model(perceptual[0], device, "perceptual: the model")
+            if torch.device(device).type == "cuda":
+                with torch.cuda.device(torch.device(device)):
+                    self.perceptual.refresh()
         self.cycle = float(cycle)
         if not self.cycle >= 0.0 or self.cycle == float("inf"):
             raise ValueError("cycle must be a finite weight >= 0, got %r" % (cycle,))
@@ -631,7 +652,7 @@ class SRTrainer:
         if not use or self._attn_losses or (self.image_encoder is not None and self.gather_negatives and dp_world() > 1):
             # (DAMSM on the gathered global batch all-gathers inside generator_loss; the attention-guided losses are not captured yet)
             return None
-        hyper = self._opt_key(self.opt) + (self.ema_decay, self.cycle)
+        hyper = self._opt_key(self.opt) + (self.ema_decay, self.cycle, self.perceptual_weight)
         if hyper != self._ghyper:
             self._ggraphs, self._ghyper = {}, hyper
         key = self._g_key(gan, LR, words_embs, cap_lens, class_ids)
@@ -642,6 +663,8 @@ class SRTrainer:
 
     def _pixel_kl(self, fake_imgL, fine_im, mu, logvar, hr_pyramid):
         base = self._pixel_kl_base(fake_imgL, fine_im, mu, logvar, hr_pyramid)
+        if self.perceptual is not None and self.perceptual_weight > 0:
+            base = base + self.perceptual_weight * self.perceptual(fine_im[-1], hr_pyramid[-1]).mean()
         if self.cycle > 0:          # (cycle == 0: CycleMSE is not called and the loss is the expression it always was)
             return base + self.cycle * (losses.CycleMSE(fake_imgL, self._lr_in, fused=self.cycle_fused) +
                                         losses.CycleMSE(fine_im, self._lr_in, fused=self.cycle_fused))
@@ -876,7 +899,7 @@ class SRTrainer:
 
     @torch.no_grad()
     def evaluate(self, batches, ema=True, shave=0, max_batches=None, r_precision=None, generator=None, ensemble=1, fid=None,
-                 kid=None, niqe=None):
+                 kid=None, niqe=None, lpips=None):
         """Score a validation set: `batches` yields (captions, cap_lens, LR, LRb, hr_pyramid); the generators run in eval mode
         (SRPipeline.from_modules over this trainer's modules, no copies) with the EMA weights (`ema`, the ones `snapshot` saves by
         default) or the current ones, and every output scale is scored against hr_pyramid[k] on the device (tgsr_amd.metrics:
@@ -900,6 +923,11 @@ class SRTrainer:
         `niqe` = True (the model is fitted from the ground-truth images seen), a NIQEModel or the path of one - how natural does each
           image look on its own?  Lower is better; `shave` applies; the finest scale needs 96 pixels on a side after it.  The dict
           gains "niqe": {"fine": [N], "hr": [N], "mean": {"fine", "hr"}, "n": N} (niqe.NIQEScores).
+        `lpips` = a tgsr_amd.lpips.LPIPS or the path of a saved one - the learned perceptual distance to the ground truth (lower is
+          better).  Both images are scored as the saved PNGs would be: after the quantisation PSNR is scored on (`to_uint8`, mapped
+          back by u / 127.5 - 1), so the figure is the one a reader of the files computes; `shave` is NOT applied; 16 pixels on a
+          side at least.  The dict gains "lpips": {"fine": [N], "mean", "n": N, "per_layer": [5][N]} (lpips.PerceptualScores), rows
+          gathered in rank order.  A figure comparable with published LPIPS needs that package's trained weights, which are not shipped.
         Data parallel: every rank passes ITS batches; the PSNR / SSIM and NIQE rows are gathered in rank order and the moments behind
         "fid" and niqe=True's fit are all-reduced, so every rank returns the same of those; "r_precision" and "kid" score the
         calling rank's items only (region features and feature banks are not gathered across ranks)."""
@@ -914,6 +942,7 @@ class SRTrainer:
             raise ValueError("evaluate(fid=%r, kid=%r) needs the trainer's image_encoder" % (fid, kid))
         realism = featdist.RealismScores(fid, kid, self.device) if fid is not None or kid is not None else None
         naturalness = niqe_mod.NIQEScores(niqe, shave, self.device) if niqe is not None and niqe is not False else None
+        perceptual = lpips_mod.PerceptualScores(lpips, self.device) if lpips is not None else None
         gallery = retrieval.Gallery() if r_precision is not None else None
         forward = self._eval_pipe if ensemble == 1 else self._eval_pipe.self_ensemble
         book = metrics.ScoreBook(shave)
@@ -936,6 +965,8 @@ class SRTrainer:
                     gallery.add(feats, code, words_embs, sent_emb, cap_lens, class_ids=class_ids)
                 if naturalness is not None:
                     naturalness.add(sr, hr)
+                if perceptual is not None:
+                    perceptual.add(sr, hr)
                 for name in ("fine", "fake"):
                     if len(out[name]) != len(hr_pyramid):
                         raise ValueError("evaluate: %d %s images against %d ground-truth scales"
@@ -956,6 +987,8 @@ class SRTrainer:
                 scores.update(realism.result(generator))
             if naturalness is not None:
                 scores["niqe"] = naturalness.result()
+            if perceptual is not None:
+                scores["lpips"] = perceptual.result()
         return scores
 
     def snapshot_due(self, epoch, max_epoch=None):

@@ -204,6 +204,18 @@ class SRPipeline:
         with torch.cuda.device(self.device):
             return model.score(img[None] if img.dim() == 3 else img, shave)
 
+    def perceptual(self, out, hr, model):
+        """The learned full-reference side of scoring: LPIPS (tgsr_amd.lpips, lower is better) between the finest `fine` image of a
+        forward's outputs ([B, 3, H, W]) or an `upscale` result ([3, H, W]; float32 or out="u8" bytes) and its ground truth `hr`
+        (float32 in [-1, 1] or uint8, the same shape), both as the saved PNGs would hold them (lpips.quantised; no border is
+        shaved): float32 [B] on the device, no synchronisation.  `model`: an lpips.LPIPS on this device; 16 pixels on a side at
+        least."""
+        from . import lpips
+        img = out["fine"][-1] if isinstance(out, dict) else out
+        with torch.cuda.device(self.device), torch.no_grad():
+            img, hr = (t[None] if t.dim() == 3 else t for t in (img, hr))
+            return model(lpips.quantised(img), lpips.quantised(hr))
+
     def load_state_dicts(self, sd_E=None, sd_GL=None, sd_GH=None):
         """strict for E and GL; the x8 GH tolerates only a missing `a` (never saved by the reference, model.py:246-248);
         the x16 GH registers `a` as a parameter (models16.py:126) and loads it.  The weight-map forms load their maps
