@@ -921,9 +921,13 @@ int tgsr_resize_coeffs(int in_size, int out_size, int ksize, int32_t* bounds, in
  *       Y is the reference's rgb2y (trainer_objective.py:168-174) byte for byte; the SSEs are exact integers, so that
  *       rmse = sqrt(sse / n), psnr = 20 log10(255 / rmse) on the host equal the reference's psnr() (:177-181) bit for bit.
  *       SSIM on Y: Wang et al. 2004 as in ssim.m - 11 x 11 Gaussian window of sigma 1.5, 'valid' filtering, K1 = 0.01, K2 = 0.03,
- *       L = 255, fp64.  ws: tgsr_sr_metrics_ws_elems(...) float64 (per-tile partial sums, added in tile order).
+ *       L = 255, fp64.  ws: tgsr_sr_metrics_ws_elems(...) float64 (per-tile partial sums, added in tile order): exactly that
+ *       many are written, each before it is read - what ws held before the call does not matter.
  *       Two launches on `stream`, no atomics, no host synchronisation: capturable, and the same bits on every run.
  *   tgsr_rgb_to_y_u8  rgb uint8 [B][3][H][W] -> y uint8 [B][H][W], the same Y.
+ * Alignment: a uint8 image (sr, hr, rgb, y) may start at any byte, a float32 image on 4 bytes, ws and out on 8; nothing more.
+ * TGSR_EINVAL, nothing launched: a NULL pointer, B outside [1, 65535] (tgsr_rgb_to_y_u8: B < 1), H or W < 1, shave < 0, a crop
+ * under 11 on either side (tgsr_sr_metrics_ws_elems returns 0 for those shapes).
  */
 int64_t tgsr_sr_metrics_ws_elems(int B, int H, int W, int shave);
 int tgsr_sr_metrics(const void* sr, int sr_f32, const void* hr, int hr_f32, int B, int H, int W, int shave, double* ws,
@@ -1015,7 +1019,8 @@ int tgsr_attn_panels(const float* att, const int32_t* cap_lens, const void* img,
  * datasets.py:200-278, followed by the fully convolutional generators): the cut and the reassembly of a tile batch.
  * table: int32 [Tb][6] = (y0, x0, oy0, oy1, ox0, ox1) in LR pixels, once in host memory (table_host, checked here) and once in
  * device memory (table_dev, what the kernels read - they skip a row that fails the same checks, so no access leaves an
- * image).  Window t is rows [y0, y0 + th) x columns [x0, x0 + tw) of the H x W image; the rectangle it OWNS is
+ * image; what such a row would have written - its block of out / out2, its owned rectangle of every dst - keeps what it held:
+ * nothing is zeroed).  Window t is rows [y0, y0 + th) x columns [x0, x0 + tw) of the H x W image; the rectangle it OWNS is
  * [oy0, oy1) x [ox0, ox1).  TGSR_EINVAL unless 1 <= th <= min(H, 4096), 1 <= tw <= min(W, 4096), H, W <= 2^20, Tb in [1, 65535]
  * and for every row 0 <= y0 <= H - th, 0 <= x0 <= W - tw, y0 <= oy0 < oy1 <= y0 + th, x0 <= ox0 < ox1 <= x0 + tw.
  *   tgsr_tile_gather  img (and img2 unless NULL; out2 is NULL exactly when img2 is): planar [3][H][W], both uint8 (is_u8 != 0:
@@ -1026,10 +1031,13 @@ int tgsr_attn_panels(const float* att, const int32_t* cap_lens, const void* img,
  *       between tiles (so a channel crop of a wider buffer is taken in place); dst[e]: [C[e]][s H][s W], float32 (out_u8[e] == 0:
  *       a bit copy) or uint8 (tgsr_to_uint8's rule, the same bytes).  Only each tile's owned rectangle (times s) is written:
  *       where the owned rectangles partition the image (tgsr_amd.tiles.plan_tiles) every output pixel has exactly one source -
- *       no blending, no atomics, the same bits on every run.  Two rows may name the same window (a padded last batch): their
- *       pixels are written twice with the same values.
+ *       no blending, no atomics, the same bits on every run; a pixel no row owns keeps what dst[e] held.  Two rows may name the
+ *       same window (a padded last batch): their pixels are written twice with the same values.  src_stride[e] below the block
+ *       size is TGSR_EINVAL when Tb > 1; with Tb == 1 it is not used and may be anything.  TGSR_EINVAL too for n outside
+ *       [1, TGSR_STITCH_MAX], a NULL list or list entry, C[e] outside [1, 65535], scale[e] outside [1, 64].
  * Rows move as 16-byte accesses where the bases, the row pitches and the rectangle's first column are multiples of 4
- * elements, element by element otherwise (any H, W, offsets).  Plain loads and stores; capturable.
+ * elements, element by element otherwise (any H, W, offsets): no operand needs more than its element's alignment - a uint8
+ * image or destination may start at any byte.  Plain loads and stores; capturable.
  */
 #define TGSR_STITCH_MAX 12
 int tgsr_tile_gather(const void* img, const void* img2, int is_u8, int H, int W, const int32_t* table_host,
@@ -1060,12 +1068,14 @@ int tgsr_tile_stitch(int n, const float* const* src, const int64_t* src_stride, 
  *       a srcB[e] that is present with nk = 8 or missing with nk = 4 is TGSR_EINVAL.  A batch row is a dense (C, rows, columns)
  *       block; src_stride[e] >= its size: elements between consecutive batch rows of srcA[e] and of srcB[e].  s = scale[e] in
  *       [1, 64].  dst[e]: [N][C[e]][s H][s W], float32 (out_u8[e] == 0: the mean) or uint8 (tgsr_to_uint8's rule applied to the
- *       float32 mean).  Only each window's owned rectangle (times s) is written, each pixel once; two rows that name the same
- *       window (a padded last batch) write the same values twice.  No atomics, no workspace.
+ *       float32 mean).  Only each window's owned rectangle (times s) is written, each pixel once - a pixel no row owns, and the
+ *       rectangle of a row of table_dev that fails the checks, keep what dst[e] held; two rows that name the same window (a
+ *       padded last batch) write the same values twice.  src_stride[e] below the block size is TGSR_EINVAL whatever Tb.  No
+ *       atomics, no workspace.
  * Layout: a workgroup owns a 32 x 32 block on the window's side; every global access runs along rows of its image, as aligned
  * 16-byte quads where the bases, the row pitches and the row strides are multiples of 4 elements, element by element otherwise
- * (any H, W, offsets); the mirrors and the transpose happen between a padded LDS block and registers.  Plain loads and stores;
- * capturable.
+ * (any H, W, offsets; no operand needs more than its element's alignment); the mirrors and the transpose happen between a
+ * padded LDS block and registers.  Plain loads and stores; capturable.
  */
 int tgsr_d8_gather(const void* img, const void* img2, int is_u8, int N, int H, int W, const int32_t* table_host,
                    const int32_t* table_dev, int Tb, int th, int tw, int k0, int nk, float* out, float* out2, void* stream);

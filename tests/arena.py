@@ -27,6 +27,8 @@ no conversion produces (theirs are 0x7FC0 / 0x7E00).
     img = a.place_output_u8((n,), lead=1, expect=ref)                                      # ... one byte off a word, of any byte values
     src = a.place_input_u8(image, lead=3)                                                  # a byte input three bytes off a word
     tmp = a.place_ws_u8(n, lead=2)                                                         # a workspace of exactly n BYTES
+    img = a.place_inout_u8(prior, lead=1, may=owned, expect=ref)                           # a byte image with prior contents, partly owned
+    out = a.place_masked(base, may=owned)                                                  # a float32 output only `may` of which is the call's
 
 An lp image holds zeros on its one-pixel border, the values of `reads` (NCHW tensors, exactly representable) in their channel
 ranges and PATTERN16 in every other channel of the interior; the call may write the interior pixels x the channel ranges of
@@ -99,6 +101,28 @@ class Region:
         if unwritten:
             return ["%s #%d %s: %d of %d words never written" % (self.kind, i, self.shape, unwritten, w.numel())]
         if self.dtype.is_floating_point and not bool(torch.isfinite(w.view(self.dtype)).all()):
+            return ["%s #%d %s holds non-finite values" % (self.kind, i, self.shape)]
+        return []
+
+
+class RegionMasked(Region):
+    """A dense float32 operand whose elements the call may write only where `may` holds: `host` holds its initial words (PATTERN
+    where the caller gave no base), `must` the elements that have to be written - those it may write that start as PATTERN."""
+
+    def __init__(self, arena, offset, shape, host, may):
+        super().__init__(arena, _INOUT, offset, shape, 1, host.numel(), host.numel(), torch.float32, host)
+        self.may = may
+        self.must = may & (host == PATTERN)
+
+    def initial(self, k, n):
+        return self.host, torch.where(self.may, torch.tensor(-1, dtype=torch.int32), torch.tensor(0, dtype=torch.int32))
+
+    def complaints(self, i):
+        w = self.words()
+        unwritten = int(((w == PATTERN) & self.must).sum())
+        if unwritten:
+            return ["%s #%d %s: %d of %d elements never written" % (self.kind, i, self.shape, unwritten, int(self.must.sum()))]
+        if not bool(torch.isfinite(w.view(torch.float32)[self.may]).all()):
             return ["%s #%d %s holds non-finite values" % (self.kind, i, self.shape)]
         return []
 
@@ -300,6 +324,45 @@ class Arena:
         mask, must = torch.zeros_like(img), torch.zeros(img.shape, dtype=torch.bool)
         shape = tuple(int(s) for s in t.shape) or (1,)
         return self._place16(Region16(self, _INPUT, 0, shape, torch.uint8, img, mask, must, False, lead), align, skew)
+
+    def place_inout_u8(self, t, align=16, skew=0, lead=0, may=None, expect=None):
+        """A byte operand with prior contents `t` that the call writes in part (an image of which only owned rectangles are the
+        call's): `may` (bool, t's shape; all of it when None) says which bytes it may change, every other byte - and those in front
+        of the operand and behind it - must hold its bits.  `expect` (uint8, the right result): a byte the call may write counts as
+        unwritten where it still holds its prior value and the right one is another."""
+        t = t.detach().cpu().contiguous()
+        assert t.dtype == torch.uint8 and t.numel() >= 1 and 0 <= lead <= 3
+        n = t.numel()
+        img = torch.full(((lead + n + 3) // 4,), PATTERN, dtype=torch.int32).view(torch.uint8).clone()
+        img[lead:lead + n] = t.reshape(-1)
+        mask, must = torch.zeros_like(img), torch.zeros(img.shape, dtype=torch.bool)
+        may = torch.ones(n, dtype=torch.bool) if may is None else may.reshape(-1).bool()
+        assert may.numel() == n
+        mask[lead:lead + n] = torch.where(may, 255, 0).to(torch.uint8)
+        if expect is not None:
+            must[lead:lead + n] = may & (expect.reshape(-1) != t.reshape(-1))
+        shape = tuple(int(s) for s in t.shape) or (1,)
+        return self._place16(Region16(self, _INOUT, 0, shape, torch.uint8, img, mask, must, False, lead), align, skew)
+
+    def place_masked(self, base, may, align=16, skew=0):
+        """A float32 output of which the call owns only the elements where `may` (bool, base's shape) holds: `base` (float32, finite)
+        is what it holds before the call, or a shape - then PATTERN, and every element of `may` has to be written.  An element
+        outside `may` must hold its bits (a hole no tile owns, the block of a window the kernels skip)."""
+        assert self._buf is None, "place every operand before taking the first pointer"
+        if torch.is_tensor(base):
+            base = base.detach().cpu().contiguous()
+            assert base.dtype == torch.float32
+            shape, host = tuple(base.shape), base.reshape(-1).view(torch.int32).clone()
+        else:
+            shape = tuple(int(s) for s in base)
+            host = torch.full((int(np.prod(shape)),), PATTERN, dtype=torch.int32)
+        may = may.reshape(-1).bool()
+        assert may.numel() == host.numel() >= 1
+        a = align // 4
+        r = RegionMasked(self, (self._cursor + a - 1) // a * a + skew, shape, host, may)
+        self.regions.append(r)
+        self._cursor = r.offset + r.span + self.guard
+        return r
 
     def place_ws_u8(self, n, align=16, skew=0, lead=0):
         """A workspace of exactly `n` BYTES, `lead` bytes off a word, holding PATTERN's bytes: the call may write those n bytes, all

@@ -130,6 +130,72 @@ def test_arena_byte_input_and_workspace_off_a_word():
     assert torch.equal(rw, torch.cat([pat, pat]))
 
 
+def test_arena_byte_inout_with_a_mask():
+    """place_inout_u8(t, lead=, may=, expect=): a byte image with prior contents of which the call owns `may`: a byte outside `may`
+    (a hole) must keep its value, one inside that has to change and did not counts as unwritten, the bytes around the operand are
+    guarded; rearm() puts the prior contents back."""
+    from arena import Arena
+    prior = torch.tensor([10, 11, 12, 13, 14, 15, 16], dtype=torch.uint8)
+    may = torch.tensor([1, 1, 0, 0, 1, 1, 1], dtype=torch.bool)
+    expect = torch.tensor([20, 11, 12, 13, 24, 25, 26], dtype=torch.uint8)      # byte 1 is owned and the right value IS the prior one
+
+    def fresh():
+        a = Arena("cpu", guard=4)
+        img = a.place_inout_u8(prior, lead=2, may=may, expect=expect)
+        assert img.address % 4 == 2 and img.span == 3 and img.kind == "inout"
+        return a, img, a.buffer()[img.offset:img.offset + 3].view(torch.uint8)
+    a, img, raw = fresh()
+    assert torch.equal(img.read(), prior)
+    assert len(a.violations()) == 1 and "4 of 4 elements never written" in a.violations()[0]
+    raw[2:9] = expect
+    a.check()
+    assert torch.equal(img.read(), expect)
+    raw[6] = 14                                                                 # an owned byte that had to change holds the prior value
+    assert any("1 of 4 elements never written" in v for v in a.violations())
+    for where in (1, 4, 5, 9):                                                  # in front of the operand, the hole's two bytes, behind it
+        a, img, raw = fresh()
+        raw[2:9] = expect
+        raw[where] ^= 1
+        assert any("outside every output" in v for v in a.violations()), where
+    a, img, raw = fresh()
+    raw[2:9] = expect
+    a.rearm(ws_fill=1.5)
+    assert torch.equal(img.read(), prior)
+
+
+def test_arena_float_output_with_a_mask():
+    """place_masked(base or shape, may): only the elements of `may` are the call's.  Over a shape they start as PATTERN and have to
+    be written; over a finite base nothing has to, and an element outside `may` must keep its bits either way."""
+    from arena import PATTERN, Arena
+    may = torch.tensor([[1, 1, 0], [0, 1, 1]], dtype=torch.bool)
+    a = Arena("cpu", guard=4)
+    x = a.place_input(torch.zeros(3))
+    out = a.place_masked((2, 3), may, skew=1)
+    base = torch.arange(6, dtype=torch.float32).reshape(2, 3) + 0.5
+    over = a.place_masked(base, may)
+    assert x.address % 16 == 0 and out.address % 16 == 4 and over.address % 16 == 0 and out.kind == over.kind == "inout"
+    raw, rover = a.buffer()[out.offset:out.offset + 6], a.buffer()[over.offset:over.offset + 6]
+    assert bool((raw == PATTERN).all()) and torch.equal(over.read(), base)
+    v = a.violations()
+    assert len(v) == 1 and "4 of 4 elements never written" in v[0]              # the base is written nowhere and that is fine
+    raw.view(torch.float32)[may.reshape(-1)] = 2.0
+    a.check()
+    assert torch.equal(out.read()[may], torch.full((4,), 2.0)) and bool((out.words()[~may.reshape(-1)] == PATTERN).all())
+    rover.view(torch.float32)[4] = -1.0                                         # an owned element of the based output: allowed
+    a.check()
+    raw.view(torch.float32)[1] = float("inf")
+    assert any("non-finite" in m for m in a.violations())
+    raw.view(torch.float32)[1] = 2.0
+    for region, where in ((raw, 2), (raw, 3), (rover, 2), (rover, 3)):          # the elements outside `may`, PATTERN or base
+        keep = int(region[where])
+        region[where] = keep ^ 1
+        assert any("outside every output" in m for m in a.violations()), where
+        region[where] = keep
+    a.check()
+    a.rearm(ws_fill=1.5)
+    assert bool((raw == PATTERN).all()) and torch.equal(over.read(), base)
+
+
 # ---- the launch arithmetic ----
 def test_gemm_rows_have_the_tails_they_name():
     g = A.gemm_plan

@@ -2087,7 +2087,8 @@ def tile_stitch(tiles, outs, table, H: int, W: int, th: int, tw: int, table_dev:
     """The owned rectangle of every tile of every tile output, into the whole-image outputs, in one launch (tgsr_tile_stitch).
     tiles[e]: float32 [Tb, C, s th, s tw] with a dense (C, s th, s tw) block and any tile stride; outs[e]: dense [C, s H, s W],
     float32 (a bit copy) or uint8 (`to_uint8`'s bytes); the scale s is read off the shapes.  Pixels no tile owns keep what `outs`
-    held."""
+    held, and so does the rectangle of a row of `table_dev` that fails the window checks (the kernel skips it).  No alignment is
+    needed beyond the element's: a uint8 output may start at any byte."""
     tiles, outs = list(tiles), list(outs)
     n = len(tiles)
     if n < 1 or n != len(outs) or n > STITCH_MAX:
@@ -2175,7 +2176,8 @@ def d8_merge(srcs, outs, table, H: int, W: int, th: int, tw: int, srcs_t=None, t
     srcs[e]: float32 [N * Tb * nk, C, s th, s tw], the outputs of the variant batch `d8_gather` made - a dense (C, s th, s tw) block
     per batch row, any row stride.  Without srcs_t nk = 8 (square windows); with it nk = 4 and srcs_t[e] is the transposed group
     [N * Tb * 4, C, s tw, s th] with the same row stride.  outs[e]: dense [N, C, s H, s W], float32 (the mean) or uint8 (`to_uint8`
-    of the mean); N and the scale s are read off the shapes.  Pixels no window owns keep what `outs` held."""
+    of the mean); N and the scale s are read off the shapes.  Pixels no window owns keep what `outs` held, and so does the
+    rectangle of a row of `table_dev` that fails the window checks."""
     srcs, outs = list(srcs), list(outs)
     n = len(srcs)
     if n < 1 or n != len(outs) or n > STITCH_MAX:
@@ -2253,7 +2255,8 @@ def _metrics_image(t: torch.Tensor, name: str, dtypes) -> torch.Tensor:
 def sr_metrics(sr: torch.Tensor, hr: torch.Tensor, shave: int = 0) -> torch.Tensor:
     """float64 [B, 3] = (SSE over RGB, SSE over Y, sum of the SSIM-on-Y window values) of `sr` against `hr` (tgsr_sr_metrics), on
     uint8 images: each input is uint8 NCHW or float32 NCHW (quantised in the kernel like `to_uint8`); `shave` pixels leave every
-    border first.  The SSEs are exact integers; the crop has (H - 2 shave - 10)(W - 2 shave - 10) windows."""
+    border first.  The SSEs are exact integers; the crop has (H - 2 shave - 10)(W - 2 shave - 10) windows.  The workspace is
+    exactly tgsr_sr_metrics_ws_elems doubles, uninitialised: the kernels write every element before they read it."""
     _need_hip(sr, hr)
     sr = _metrics_image(sr, "sr", (torch.float32, torch.uint8))
     hr = _metrics_image(hr, "hr", (torch.float32, torch.uint8))
