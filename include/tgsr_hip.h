@@ -907,6 +907,12 @@ int tgsr_u8_normalize(const uint8_t* in, float* out, int64_t n, void* stream);
  *   tgsr_resize_coeffs  that coefficient step on its own: bounds int32 [out_size][2] = (first input index, tap count),
  *       taps int32 [out_size][ksize] in 22-bit fixed point, zero behind the count; ksize must be Pillow's
  *       2 ceil(max(in_size / out_size, 1)) + 1.  Sizes in [1, 65536], in_size <= 16 out_size.  Both device memory.
+ * Alignment: packed and out may start at any byte; table_host, table_dev, ws, bounds and taps start on 4 bytes (TGSR_EUNSUPPORTED
+ * otherwise).  Workspace: ws has exactly tgsr_augment_ws_elems words and what ws holds before a call does not matter - every word the
+ * second launch reads the first has written.  Outputs: out, bounds and taps are written whole, the zeros behind a tap count too;
+ * the out bytes of an image the kernels skip keep their prior contents.  Refusals (TGSR_EINVAL: a NULL pointer, nbytes outside
+ * [1, 2^31), B, S or a host descriptor outside the rules above, a size or ksize tgsr_resize_coeffs does not take):
+ * nothing is launched or written.
  */
 int64_t tgsr_augment_ws_elems(int B, int S);
 int tgsr_augment_u8(const uint8_t* packed, int64_t nbytes, const int32_t* table_host, const int32_t* table_dev, int B, int S,
@@ -1008,6 +1014,12 @@ int tgsr_lpips_layer_bwd(const float* g, const float* f0, int64_t f0_bstride, co
  * Two launches on `stream`, no atomics, no host synchronisation: capturable, the same bits on every run.  Refused before any launch:
  * TGSR_EINVAL for a missing pointer, B, T, K < 1, K > T, u < 1, alpha outside [0, 255]; TGSR_EUNSUPPORTED for h or w outside
  * [2, 128], Vh or Vw > 512, T > 64 (tgsr_attn_panels_ws_elems returns 0 for those shapes).
+ * Alignment: panel, maps and a uint8 img may start at any byte (the kernel stores 16 bytes at a time where the address allows and
+ * single bytes at the ends of a row group); att, cap_lens, order and a float32 img start on 4 bytes; Mh, Mw, ws and conf start on
+ * 8 bytes (TGSR_EUNSUPPORTED otherwise, after the checks above).  Workspace: ws has exactly tgsr_attn_panels_ws_elems doubles;
+ * the tile and the min / max pairs of a word behind its caption are neither written nor read, what ws holds before a call does not
+ * matter.  Outputs: conf and order are written whole (0 and -1 behind the caption), panel and maps whole.  On a refusal
+ * nothing is launched or written.
  */
 int64_t tgsr_attn_panels_ws_elems(int B, int T, int h, int w, int u);
 int tgsr_attn_panels(const float* att, const int32_t* cap_lens, const void* img, int img_f32, const double* Mh, const double* Mw,

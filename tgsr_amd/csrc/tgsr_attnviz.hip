@@ -341,6 +341,9 @@ extern "C" int tgsr_attn_panels(const float* att, const int32_t* cap_lens, const
   if (!att || !cap_lens || !img || !Mh || !Mw || !ws || !panel || !conf || !order) return TGSR_EINVAL;
   if (B < 1 || T < 1 || K < 1 || K > T || u < 1 || alpha < 0 || alpha > 255) return TGSR_EINVAL;
   if (!attn_shape_ok(B, T, h, w, u)) return TGSR_EUNSUPPORTED;
+  const auto low = [](const void* p) { return reinterpret_cast<uintptr_t>(p); };
+  if ((low(att) | low(cap_lens) | low(order) | (img_f32 ? low(img) : 0)) & 3) return TGSR_EUNSUPPORTED;   // 4-byte elements
+  if ((low(Mh) | low(Mw) | low(ws) | low(conf)) & 7) return TGSR_EUNSUPPORTED;                              // fp64
   const int Vh = u * h, Vw = u * w;
   const int nblk = (Vh + kAR - 1) / kAR, nrc = (Vh + kPR - 1) / kPR;
   if ((int64_t)B * T * nblk > 0x7fffffffLL || (int64_t)B * nrc > 0x7fffffffLL) return TGSR_EUNSUPPORTED;

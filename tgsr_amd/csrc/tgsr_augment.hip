@@ -159,6 +159,10 @@ static inline int aug_ksize(int in, int out) {                     // Pillow: (i
   return 2 * c + 1;
 }
 
+static inline bool aug_aligned4(const void* a, const void* b, const void* c = nullptr) {   // the int32 operands
+  return ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b) | reinterpret_cast<uintptr_t>(c)) & 3) == 0;
+}
+
 }  // namespace tgsr
 
 using namespace tgsr;
@@ -166,6 +170,7 @@ using namespace tgsr;
 extern "C" int tgsr_resize_coeffs(int in_size, int out_size, int ksize, int32_t* bounds, int32_t* taps, void* stream) {
   if (!bounds || !taps || in_size < 1 || out_size < 1 || in_size > kAugMaxOut || out_size > kAugMaxOut) return TGSR_EINVAL;
   if ((int64_t)in_size > (int64_t)kAugMaxRatio * out_size || ksize != aug_ksize(in_size, out_size)) return TGSR_EINVAL;
+  if (!aug_aligned4(bounds, taps)) return TGSR_EUNSUPPORTED;
   hipLaunchKernelGGL(resize_coeffs_kernel, dim3((out_size + 255) / 256), dim3(256), 0, as_stream(stream), in_size, out_size,
                      ksize, bounds, taps);
   return note_launch(hipGetLastError(), "resize_coeffs_kernel");
@@ -180,6 +185,7 @@ extern "C" int tgsr_augment_u8(const uint8_t* packed, int64_t nbytes, const int3
                                int B, int S, int32_t* ws, uint8_t* out, void* stream) {
   if (!packed || !table_host || !table_dev || !ws || !out || nbytes < 1 || nbytes > INT32_MAX) return TGSR_EINVAL;
   if (B < 1 || B > 65535 || S < 1 || S > kAugMaxSide) return TGSR_EINVAL;
+  if (!aug_aligned4(table_host, table_dev, ws)) return TGSR_EUNSUPPORTED;
   for (int b = 0; b < B; ++b)
     if (!aug_desc_ok(table_host + (int64_t)b * kAugDesc, S, nbytes)) return TGSR_EINVAL;
   hipStream_t s = as_stream(stream);

@@ -1928,7 +1928,10 @@ def augment_u8(packed: torch.Tensor, table, S: int, out: Optional[torch.Tensor] 
     """One launch of crop -> Pillow `resize(BILINEAR)` -> window -> mirror over a ragged batch: `packed` uint8, the decoded
     H x W x 3 images back to back on the device; `table` the host int32 [B, 12] descriptors (check_augment_table).  Returns
     planar uint8 [B, 3, S, S] (`out` if given: dense, on the same device), per image the bytes of
-    `img.crop((x1, y1, x2, y2)).resize((ow, oh), BILINEAR).crop((left, top, left + S, top + S))`, mirrored where flip is set."""
+    `img.crop((x1, y1, x2, y2)).resize((ow, oh), BILINEAR).crop((left, top, left + S, top + S))`, mirrored where flip is set.
+    The C entry takes `packed` and `out` at any byte and the int32 tables and workspace on 4 bytes; what the workspace holds before
+    the call does not matter; `out` is written whole (the kernels would leave an image whose device descriptor fails the checks as
+    it was - here both copies are the checked table); on a refusal nothing is launched or written."""
     if not torch.is_tensor(packed) or packed.dtype != torch.uint8 or packed.dim() != 1:
         raise TgsrError("augment: the packed buffer is a flat uint8 tensor")
     packed = packed.contiguous()
@@ -2453,7 +2456,10 @@ def attn_panels(images: torch.Tensor, att: torch.Tensor, cap_lens, Mh: torch.Ten
                 by_conf: bool, with_maps: bool):
     """tgsr_attn_panels: (panel uint8 [B, Vh, K (Vw + 2), 3], conf float64 [B, T], order int32 [B, T], maps uint8 [B, T, Vh, Vw] or
     [0]) from att [B, T, h, w] float32, cap_lens (B host ints in [1, T]), images [B, 3, u h, u w] float32 or uint8 and the fp64
-    operators Mh [u h, h], Mw [u w, w] (attnviz.expand_operator).  The arithmetic: tgsr_amd/attnviz.py."""
+    operators Mh [u h, h], Mw [u w, w] (attnviz.expand_operator).  The arithmetic: tgsr_amd/attnviz.py.
+    The C entry takes panel, maps and a uint8 image at any byte, att, cap_lens, order and a float32 image on 4 bytes, Mh, Mw, the
+    workspace and conf on 8 bytes (TGSR_EUNSUPPORTED otherwise); the workspace tiles of words behind a caption are neither written nor
+    read; conf and order are written whole; on a refusal nothing is launched or written."""
     if att.dim() != 4:
         raise TgsrError("attn_panels: att [B, T, h, w] expected, got %s" % (tuple(att.shape),))
     B, T, h, w = att.shape
